@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- SDXL training-step throughput on MI355X (BASELINE.json metric: train images/sec).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts N fresh rank processes itself, see launch_ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]          (N > 1: starts N fresh rank processes itself, see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1]): SDXL-base UNet (2.567 B parameters, random init), 1024x1024 synthetic
@@ -408,7 +408,31 @@ def parse_args(argv=None):
     ap.add_argument("--alt-steps", type=int, default=5,
                     help="N > 1: behind the timed steps, run this many steps in each of the OTHER exchange configurations (dp-mode x wire dtype) in the "
                          "same process and report them as comm.alt (0 = off)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs), so that two builds can be "
+                         "compared output for output on the same seeded inputs")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22      # elements per sampled flat buffer: 16 MB of float32 each
+
+
+def dump_outputs(directory, loss, store, sample=DUMP_SAMPLE, seed=0) -> dict:
+    """What one training step hands its caller, as float32 .npy files: the loss it returned (`loss`), and the fp32 master weights the
+    optimizer wrote (`master_sample`) and the fp32 weight gradients of the step (`grad_sample`) at the same fixed, seeded set of flat
+    indices (the whole buffers are ~10 GB each).  Returns {name: shape}."""
+    import numpy as np
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    idx = torch.randint(store.numel, (min(sample, store.numel),), generator=torch.Generator().manual_seed(seed)).to(store.master.device)
+    arrays = {"loss": loss.detach().float().reshape(1), "master_sample": store.master[idx], "grad_sample": store.grad[idx]}
+    for name, t in arrays.items():
+        np.save(out / f"{name}.npy", t.float().cpu().numpy())
+    return {name: tuple(t.shape) for name, t in arrays.items()}
 
 
 def main(argv=None):
@@ -460,6 +484,8 @@ def main(argv=None):
     if dp is not None and dp.sharded:
         if args.optimizer != "adafactor":
             raise SystemExit("--dp-mode rs_ag needs --optimizer adafactor (the chunked fused optimizer)")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs needs --dp-mode allreduce (under rs_ag a rank holds the new masters and reduced gradients of its own shard only)")
         dp.attach_optimizer(eng.adafactor)
     if args.serialize:
         eng.store.state.wgrad_stream = None
@@ -538,6 +564,9 @@ def main(argv=None):
     torch.cuda.set_sync_debug_mode("default")
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # before the roofline replays below, which take further optimizer steps
+        shapes = dump_outputs(args.dump_outputs, last, eng.store)
+        print(f"[bench] last timed step's outputs -> {args.dump_outputs}: {shapes}", file=sys.stderr, flush=True)
     if dp is not None:
         dp.reducer.record_timing = False
     # per-step GPU times (event to event on the compute stream), this rank

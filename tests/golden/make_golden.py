@@ -219,6 +219,23 @@ def op_cases(nd):
     print("glue: table", table.shape, float(table[0]), float(table[-2]), float(table[-1]))
 
 
+def op_cases_mkl_compatible(nd):
+    """op_cases once more, on MKL's reproducible branch: `MKL_CBWR=COMPATIBLE python tests/golden/make_golden.py glue_mkl_compatible`.
+    The table's division and power and the embedding's exp / sin / cos go through MKL's vector math, whose last bits depend on the code
+    path MKL picks for the host CPU (the Intel authoring host and an AMD EPYC host differ in 169 of the 1001 table entries, by one ulp,
+    and by 3e-5 in the embedding at t = 999).  glue_vectors holds the authoring host's bits; this fixture holds the bits that every x86
+    host reproduces with MKL_CBWR=COMPATIBLE (tests/util.py: under_mkl_compatible)."""
+    import os
+
+    from neurosis.modules.diffusion.util import timestep_embedding
+
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE", "run with MKL_CBWR=COMPATIBLE"
+    t = torch.tensor([0, 1, 17, 500, 999])
+    table = nd.LegacyDDPMDiscretization()(1000, do_append_zero=False, flip=False).detach()
+    save_fixture(dict(t=t, emb320=timestep_embedding(t, 320), ddpm_table=table), "glue_vectors_mkl_compatible")
+    print("glue (MKL_CBWR=COMPATIBLE): table", table.shape)
+
+
 def adafactor_case():
     """Three steps of the reference's Adafactor (optimizers/adafactor.py) on a small mixed parameter set:
     matrices, 3x3 and 1x1 conv weights (OIHW), vectors.  Inputs: initial values and per-step gradients; outputs: the
@@ -1105,6 +1122,8 @@ if __name__ == "__main__":
         vae_case(nmodel)
     if "glue" in which:
         op_cases(nd)
+    if "glue_mkl_compatible" in which:       # only on request: needs MKL_CBWR=COMPATIBLE in the environment
+        op_cases_mkl_compatible(nd)
     if "adafactor" in which:
         adafactor_case()
     if "conditioner" in which:

@@ -22,7 +22,20 @@ class _Done:
         self.returncode = rc
 
 
-def test_launcher_starts_fresh_ranks_before_any_gpu_call(monkeypatch):
+def _in_fresh_process(body):
+    """Runs `body(monkeypatch)` of this module in a new interpreter.  What it checks -- nothing touched the GPU before the launcher --
+    is a property of the whole process, and in a run of the whole suite on a GPU box earlier tests have initialised HIP in this one."""
+    code = (f"import sys; sys.path.insert(0, {str(ROOT)!r}); import pytest; import tests.test_bench_launcher as t; "
+            f"mp = pytest.MonkeyPatch(); t.{body}(mp); mp.undo()")
+    p = subprocess.run([sys.executable, "-s", "-c", code], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+
+
+def test_launcher_starts_fresh_ranks_before_any_gpu_call():
+    _in_fresh_process("_launcher_starts_fresh_ranks_before_any_gpu_call")
+
+
+def _launcher_starts_fresh_ranks_before_any_gpu_call(monkeypatch):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     seen = {}
 
@@ -55,8 +68,12 @@ def test_a_rank_never_launches(monkeypatch):
     assert bench.launch_ranks(bench.parse_args([]), [], runner=runner) is None      # N = 1 runs in this process
 
 
-def test_main_takes_the_launcher_path_first(monkeypatch):
+def test_main_takes_the_launcher_path_first():
     """main() must reach the launcher before set_device / lib.load: the first GPU call of the parent would make it unsafe to spawn."""
+    _in_fresh_process("_main_takes_the_launcher_path_first")
+
+
+def _main_takes_the_launcher_path_first(monkeypatch):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     calls = []
     monkeypatch.setattr(bench, "launch_ranks", lambda args, argv: calls.append((args.gpus, torch.cuda.is_initialized())) or 0)

@@ -9,6 +9,7 @@ import torch
 import neurosis_amd.modules.diffusion as D
 from tests.golden.make_golden import UNET_SD15_TINY, UNET_TINY, VAE_TINY, synth_state_dict
 from tests.golden.fixture_io import load_fixture
+from tests.util import under_mkl_compatible
 
 G = Path(__file__).resolve().parent / "golden"
 
@@ -39,7 +40,10 @@ def test_full_size_sdxl_topology_on_meta():
 def test_sigma_table_and_denoiser_coefficients():
     fx = load_fixture("unet_sdxl_tiny")
     den = D.DiscreteDenoiser(preconditioning=D.EpsPreconditioning(), num_idx=1000, discretization=D.LegacyDDPMDiscretization())
-    assert torch.equal(den.sigmas, fx["sigma_table"])  # 1001 entries, trailing 0.0 (quirk Q1)
+    # 1001 entries, trailing 0.0 (quirk Q1): the reference's table bit for bit, on the MKL branch every host reproduces (tests/util.py)
+    got = under_mkl_compatible("import neurosis_amd.modules.diffusion as D\nout['sigmas'] = D.DiscreteDenoiser(preconditioning=D.EpsPreconditioning(), "
+                               "num_idx=1000, discretization=D.LegacyDDPMDiscretization()).sigmas")
+    assert torch.equal(got["sigmas"], load_fixture("glue_vectors_mkl_compatible")["ddpm_table"])
     assert not den.sigmas.requires_grad  # detached (quirk Q5)
     c_skip, c_out, c_in, c_noise = den.coefficients(fx["sigma"])
     assert torch.equal(c_noise, fx["c_noise_idx"])

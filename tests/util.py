@@ -1,4 +1,10 @@
 """Shared helpers for the parity tests."""
+import os
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
 import torch
 
 
@@ -54,3 +60,22 @@ def check_grad_cosines(label, named_grads, refs, floor_matrix=0.999, floor_vecto
     print(f"[gradient cosines] {label}: worst >=2-D {worst[True][0]:.6f} ({worst[True][1]}), worst 1-D {worst[False][0]:.6f} ({worst[False][1]})")
     assert not failures, (label, failures[:8])
     return worst
+
+
+def under_mkl_compatible(code: str) -> dict:
+    """Runs `code` in a fresh interpreter with MKL on its reproducible branch (MKL_CBWR=COMPATIBLE: the same bits on every x86 host) and
+    returns the tensors it stores in the dict `out`.  For exact comparisons with the reference's elementwise math (exp, sin, cos, division,
+    powers go through MKL's vector functions, whose last bits depend on the code path MKL picks for the host CPU; see
+    tests/golden/make_golden.py::op_cases_mkl_compatible).  A child process because MKL reads the setting once, at its first call, and
+    because the branch also makes MKL's GEMMs ~5x slower: the rest of the suite keeps the default."""
+    from safetensors.torch import load_file
+
+    root = str(Path(__file__).resolve().parents[1])
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "out.safetensors")
+        script = (f"import sys, torch\nsys.path.insert(0, {root!r})\nout = {{}}\n{code}\n"
+                  f"from safetensors.torch import save_file\nsave_file({{k: v.contiguous() for k, v in out.items()}}, {path!r})\n")
+        p = subprocess.run([sys.executable, "-s", "-c", script], env={**os.environ, "MKL_CBWR": "COMPATIBLE"}, capture_output=True, text=True,
+                           timeout=300)
+        assert p.returncode == 0, p.stderr[-4000:]
+        return load_file(path)
