@@ -24,7 +24,8 @@ extern "C" {
 #endif
 
 const char* nk_last_error(void);
-int nk_abi_version(void);     /* 5 (round 6: + the four *_geglu*_s entry points; bumped whenever entry points are added or change) */
+int nk_abi_version(void);     /* 5 (round 6: + the four *_geglu*_s entry points; bumped whenever an entry point changes; purely additive
+                                 entry points -- the CAME block below -- leave it as it is) */
 
 /* ------------------------------------------------------------------------------------------------
  * nn.Linear  (modules/attention.py:53,65,70,204-209,283-290,618,639; modules/diffusion/openaimodel.py:273-279,
@@ -364,6 +365,30 @@ typedef struct NkAdafactorArgs {
 long nk_adafactor_tensor_bytes(void);
 int nk_adafactor_init(const NkAdafactorArgs* args, void* stream);
 int nk_adafactor_chunk(const NkAdafactorArgs* args, void* stream);
+
+/* Fused multi-tensor CAME on the flat buffers.  Replaces CAME.step, reference optimizers/came.py:115-224: per tensor, Adafactor's
+ * factored second moment of g^2+eps1 (R, C; vectors: v), the update u clipped by its RMS (u_hat), a first moment m, and for factored
+ * tensors a second factored statistic of (u_hat - m)^2 + eps2 (Rr, Cr) that preconditions m.  Up to four launches per chunk of
+ * consecutive tensors: statistics, update RMS of the matrices, momentum (+ residual statistics; conv weights and vectors finish
+ * here), apply of the matrices.  `tensors` / `items` are device tables built by the host (layout: neurosis_amd/csrc/came.hip
+ * NkCameTensor, items as NkAfItem; nk_came_tensor_bytes() guards the mirror).  `state` holds, per tensor, m (the parameter's physical
+ * layout) and R, C, Rr, Cr (matrices: [d0], [d1]; conv OIHW weights: [O][KH][I], [O][KW][I]) or v (vectors).  `decay` is the
+ * decoupled weight-decay factor 1 - wd * (fixed_decay ? 1 : lr); `lr` the group's current learning rate. */
+typedef struct NkCameArgs {
+  float* master; const float* grad; void* shadow; float* state; float* ws;
+  const void* tensors; const void* items;
+  float* u2_part;       /* [nitems] partial sums of u^2 */
+  float* mean_row;      /* per matrix: partial sums of R, then of Rr, one per 256-row strip */
+  float* denom;         /* [ntensors] clip denominator max(1, rms(u) / clip_threshold) */
+  unsigned* counters;   /* "blocks done" counters, one range per tensor; all zero before a step, all zero after it */
+  int item_lo, item_hi, tensor_lo, tensor_hi;
+  float beta1, beta2, beta3;
+  float one_minus_beta1, one_minus_beta2, one_minus_beta3;   /* 1 - beta computed in double on the host, as the reference's `alpha=1.0 - beta` */
+  float eps1, eps2, clip_threshold, lr, decay, grad_scale;
+  int has_matrix;       /* the chunk holds at least one 2-D tensor (the two matrix-only passes are launched) */
+} NkCameArgs;
+long nk_came_tensor_bytes(void);
+int nk_came_chunk(const NkCameArgs* args, void* stream);
 
 /* LitEma.forward (reference modules/ema.py:40-59) as one pass over the flat fp32 buffers (n % 4 == 0):
  * ema[i] -= one_minus_decay * (ema[i] - p[i]).  The decay schedule min(decay, (1+n)/(10+n)) is the host's. */

@@ -17,6 +17,7 @@
 // in a fixed order: no atomics, bitwise reproducible.
 #include "../../include/neurosis_hip.h"
 #include "nk_common.h"
+#include "optim_common.h"
 
 struct NkAfTensor {      // mirrored by neurosis_amd/optim.py (AF_TENSOR_DTYPE); 72 bytes
   long off;              // element offset of the tensor in master / grad / shadow
@@ -34,8 +35,6 @@ struct NkAfTensor {      // mirrored by neurosis_amd/optim.py (AF_TENSOR_DTYPE);
 };
 static_assert(sizeof(NkAfTensor) == 80, "mirrored by neurosis_amd/optim.py");
 
-struct NkAfItem { int tensor, tr, tc, pad; };
-
 struct NkAfArgs {
   float* master; const float* grad; bf16_t* shadow; float* state; float* ws;
   const NkAfTensor* tensors; const NkAfItem* items;
@@ -50,22 +49,6 @@ struct NkAfArgs {
   int scale_parameter;
   const unsigned* health;   // backward-health word (errors.hip): non-zero -> every kernel of the step returns at once
 };
-// (wave-uniform scalar load; `volatile` so it is not hoisted or cached across the check)
-#define AF_HEALTH_GATE(a) do { if (*(const volatile unsigned*)(a).health) return; } while (0)
-
-#define AF_TR 256   // matrix tile rows
-#define AF_TC 64    // matrix tile cols
-#define AF_CONV_PAIRS 1024
-#define AF_VEC 1024
-
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // u of one conv (o,i) pair from the updated EMAs; g[kh][kw] are that pair's gradients (KH, KW <= 3)
 template <int KH_, int KW_>
 __device__ __forceinline__ void conv_u(const float (&row)[3], const float (&col)[3], const float (&g)[3][3], int KH, int KW,
@@ -174,26 +157,6 @@ __device__ __forceinline__ float af_conv_apply(const NkAfArgs& a, const NkAfTens
     }
   }
   return acc;
-}
-
-// "last block done": count this block in; true (for every thread of the block) in the block that completes `total`.
-// No fences: an agent-scope release / acquire writes back and invalidates the XCD's WHOLE L2 -- with every block of a 1 000-block launch
-// doing that beside the next step's VAE encoder the step went from 165 to 238 ms (round 4, first version).  Instead every handed-off
-// value is STORED with an agent-scope atomic store (sc1: written through to the coherence point) and drained (vmcnt(0)) before the
-// block is counted, and the finishing block LOADS them with agent-scope atomic loads (sc1: past its own non-coherent L2 lines) --
-// the second valid form of MI355X_MICROARCH.md "Correctness boundaries".
-#define AF_PUBLISH(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define AF_FETCH(ptr) __hip_atomic_load((ptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-__device__ __forceinline__ bool af_last_block(unsigned* counter, unsigned total, int tid, unsigned* flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this thread's published values have been acknowledged
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned old = atomicAdd(counter, 1u);
-    *flag = old + 1u == total;
-    if (old + 1u == total) AF_PUBLISH(counter, 0u);   // back to zero for the next step (nobody else touches it any more)
-  }
-  __syncthreads();
-  return *flag != 0u;
 }
 
 // one tensor's step size from its items' partial sums (RMS(u) -> clip denominator, RMS(p) -> relative step size)

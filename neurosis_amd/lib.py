@@ -118,6 +118,7 @@ SIGNATURES: dict[str, list] = {
     "nk_health_import": [vp, vp],
     "nk_adafactor_init": [vp, vp],
     "nk_adafactor_chunk": [vp, vp],
+    "nk_came_chunk": [vp, vp],
 }
 
 # entry points that return a size (long) instead of a status
@@ -134,6 +135,7 @@ SIZE_QUERIES: dict[str, list] = {
     "nk_lpips_layer_ws_floats": [i32, i32],
     "nk_attention_bwd_ws_floats": [adp],
     "nk_adafactor_tensor_bytes": [],
+    "nk_came_tensor_bytes": [],
     "nk_gemm_sk_status": [],
     "nk_health_status": [],
 }

@@ -11,6 +11,7 @@ per-parameter dict; `state_dict()` / `load_state_dict()` speak the reference opt
 `step`, `exp_avg_sq_row`, `exp_avg_sq_col` / `exp_avg_sq`, `RMS`) so a run resumes with its second moments, step count
 (relative-step warm-up, beta2_t) and per-tensor RMS intact.  `FlatEma` is an `nn.Module` carrying `LitEma`'s buffer names
 (`decay`, `num_updates`, one shadow per parameter), so `model_ema.*` keys of a reference checkpoint load and save unchanged.
+`FlatCAME` mirrors `neurosis.optimizers.came.CAME` (`optimizers/came.py`) the same way, on `csrc/came.hip`.
 """
 from __future__ import annotations
 
@@ -350,6 +351,212 @@ class AdafactorScheduler:
 
     def step(self) -> None:
         pass
+
+
+CAME_TENSOR_DTYPE = np.dtype([("off", "<i8"), ("m_off", "<i8"), ("r_off", "<i8"), ("c_off", "<i8"), ("rr_off", "<i8"), ("cr_off", "<i8"),
+                              ("ws_row", "<i8"), ("ws_col", "<i8"), ("kind", "<i4"), ("d0", "<i4"), ("d1", "<i4"), ("kh", "<i4"), ("kw", "<i4"),
+                              ("item0", "<i4"), ("nitems", "<i4"), ("mr0", "<i4"), ("cnt0", "<i4"), ("pad", "<i4")])
+
+
+class _CameArgs(C.Structure):
+    _fields_ = [("master", C.c_void_p), ("grad", C.c_void_p), ("shadow", C.c_void_p), ("state", C.c_void_p), ("ws", C.c_void_p),
+                ("tensors", C.c_void_p), ("items", C.c_void_p), ("u2_part", C.c_void_p), ("mean_row", C.c_void_p), ("denom", C.c_void_p),
+                ("counters", C.c_void_p), ("item_lo", C.c_int), ("item_hi", C.c_int), ("tensor_lo", C.c_int), ("tensor_hi", C.c_int),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("beta3", C.c_float),
+                ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("one_minus_beta3", C.c_float), ("eps1", C.c_float), ("eps2", C.c_float),
+                ("clip_threshold", C.c_float), ("lr", C.c_float), ("decay", C.c_float), ("grad_scale", C.c_float), ("has_matrix", C.c_int)]
+
+
+class FlatCAME:
+    """CAME on a FlatParamStore: the reference's `neurosis.optimizers.came.CAME` (optimizers/came.py:115-224) as up to four
+    multi-tensor HIP launches per chunk of tensors (`csrc/came.hip`).  Same rule per tensor: factored (over the last two dims)
+    second moment of g^2+eps1, update clipped by its RMS, first moment m, and for tensors with >= 2 dims a factored statistic of
+    the residual (u_hat - m)^2 + eps2 that preconditions m; decoupled weight decay; no bias correction.
+
+    Differences, all deliberate: the masters are fp32 and the bf16 shadow the kernels read is written round-to-nearest (the
+    reference rounds bf16 parameters stochastically, `copy_stochastic_`), as the fused Adafactor and AdamW do; `ams_bound` is not
+    implemented, and neither is `weight_decouple=False` with a weight decay (in the reference that only edits `p.grad` after the
+    update has been computed, without effect on the step): both raise.  Conv weights (OIHW) have the shape limits of
+    FlatAdafactor (<= 3x3), matrix rows must be a multiple of 4 elements."""
+
+    def __init__(self, store, lr: float = 2e-4, betas: tuple[float, float, float] = (0.9, 0.999, 0.9999), weight_decay: float = 0.0,
+                 weight_decouple: bool = True, fixed_decay: bool = False, clip_threshold: float = 1.0, eps1: float = 1e-30,
+                 eps2: float = 1e-16, chunk_bytes: Optional[int] = None):
+        _came_validate(lr, betas, weight_decay, weight_decouple, eps1, eps2, "FlatCAME")
+        if query("nk_came_tensor_bytes") != CAME_TENSOR_DTYPE.itemsize:
+            raise RuntimeError("FlatCAME: tensor table layout differs from the HIP library's")
+        if chunk_bytes is None:
+            import os
+
+            # the same gradient bytes per chunk as FlatAdafactor's default (its measurements: DESIGN.md section 3.6)
+            chunk_bytes = int(os.environ.get("NK_AF_CHUNK_MB", "128")) << 20
+        self.store = store
+        self.lr, self.betas, self.weight_decay = float(lr), tuple(float(b) for b in betas), float(weight_decay)
+        self.weight_decouple, self.fixed_decay = bool(weight_decouple), bool(fixed_decay)
+        self.clip_threshold, self.eps1, self.eps2 = float(clip_threshold), float(eps1), float(eps2)
+        self.step_count = 0
+        dev = store.master.device
+
+        tens = np.zeros(len(store.params), dtype=CAME_TENSOR_DTYPE)
+        items = []
+        self.chunks = []   # (tensor_lo, tensor_hi, item_lo, item_hi)
+        state_off, ws_max, mr_slots, n_counters = 0, 0, 0, 0
+        c_t0, c_i0, c_bytes, c_ws = 0, 0, 0, 0
+        for ti, (p, off) in enumerate(zip(store.params, store.offsets)):
+            t = tens[ti]
+            t["off"] = off
+            t["cnt0"] = n_counters
+            if p.dim() >= 2 and p.dim() not in (2, 4):
+                raise NotImplementedError(f"FlatCAME: {p.dim()}-d parameters are not supported")
+            nbytes = p.numel() * 4
+            if c_bytes and c_bytes + nbytes > chunk_bytes:      # close the current chunk before this tensor
+                self.chunks.append((c_t0, ti, c_i0, len(items)))
+                ws_max = max(ws_max, c_ws)
+                c_t0, c_i0, c_bytes, c_ws = ti, len(items), 0, 0
+            t["item0"] = len(items)
+            t["m_off"] = state_off
+            state_off += _align(p.numel())
+            if p.dim() == 2:
+                d0, d1 = p.shape
+                if d1 % 4:
+                    raise NotImplementedError("FlatCAME: matrix rows must be a multiple of 4 elements")
+                ntr, ntc = -(-d0 // AF_TR), -(-d1 // AF_TC)
+                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 1, d0, d1, 1, 1
+                for k, n in (("r_off", d0), ("c_off", d1), ("rr_off", d0), ("cr_off", d1)):
+                    t[k] = state_off
+                    state_off += _align(n)
+                t["ws_row"], t["ws_col"] = c_ws, c_ws + ntc * d0
+                c_ws += _align(ntc * d0 + ntr * d1)
+                items += [(ti, r, c, 0) for r in range(ntr) for c in range(ntc)]
+                t["mr0"] = mr_slots
+                mr_slots += 2 * ntr
+                n_counters += ntr + ntc
+            elif p.dim() == 4:
+                O, I, KH, KW = p.shape
+                if KH > 3 or KW > 3:
+                    raise NotImplementedError("FlatCAME: conv kernels larger than 3x3 are not supported")
+                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 2, O, I, KH, KW
+                for k, n in (("r_off", O * KH * I), ("c_off", O * KW * I), ("rr_off", O * KH * I), ("cr_off", O * KW * I)):
+                    t[k] = state_off
+                    state_off += _align(n)
+                items += [(ti, r, 0, 0) for r in range(-(-(O * I) // AF_CONV_PAIRS))]
+            else:
+                n = p.numel()
+                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 0, n, 1, 1, 1
+                t["r_off"] = state_off
+                state_off += _align(n)
+                items += [(ti, r, 0, 0) for r in range(-(-n // AF_VEC))]
+            t["nitems"] = len(items) - int(t["item0"])
+            n_counters += 1
+            c_bytes += nbytes
+        self.chunks.append((c_t0, len(store.params), c_i0, len(items)))
+        ws_max = max(ws_max, c_ws)
+
+        items_np = np.array(items, dtype=np.int32).view(AF_ITEM_DTYPE).reshape(-1)
+        self._tens_np = tens
+        self.tensors = torch.from_numpy(tens.view(np.uint8).copy()).to(dev)
+        self.items = torch.from_numpy(items_np.view(np.uint8).copy()).to(dev)
+        # zeroed before every step although every pass leaves them at zero: a step abandoned by the health gate must not poison the next one
+        self.counters = torch.zeros(n_counters, dtype=torch.int32, device=dev)
+        self.nitems, self.ntensors = len(items), len(store.params)
+        self.state = torch.zeros(max(state_off, 1), dtype=torch.float32, device=dev)
+        self.ws = torch.empty(max(ws_max, 1), dtype=torch.float32, device=dev)
+        self.u2_part = torch.zeros(self.nitems, dtype=torch.float32, device=dev)
+        self.mean_row = torch.zeros(max(mr_slots, 1), dtype=torch.float32, device=dev)
+        self.denom = torch.zeros(self.ntensors, dtype=torch.float32, device=dev)
+        self._has_matrix = [int((tens["kind"][t0:t1] == 1).any()) for (t0, t1, _, _) in self.chunks]
+
+    def decay_factor(self, lr: float) -> float:
+        """The decoupled weight decay's multiplier of p (pytorch_optimizer BaseOptimizer.apply_weight_decay)."""
+        return 1.0 - self.weight_decay * (1.0 if self.fixed_decay else lr)
+
+    def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
+        """One CAME update of every parameter (came.py:136-224) with the gradients multiplied by `grad_scale` (the data-parallel
+        mean); `lr` overrides the constructor's (what a torch LR scheduler set on the group).  Also rewrites the bf16 shadows."""
+        if lr is not None:
+            self.lr = float(lr)
+        self.counters.zero_()
+        self.step_count += 1
+        s = self.store
+        b1, b2, b3 = self.betas
+        for (t0, t1, i0, i1), has_matrix in zip(self.chunks, self._has_matrix):
+            a = _CameArgs(s.master.data_ptr(), s.grad.data_ptr(), s.shadow.data_ptr(), self.state.data_ptr(), self.ws.data_ptr(),
+                          self.tensors.data_ptr(), self.items.data_ptr(), self.u2_part.data_ptr(), self.mean_row.data_ptr(),
+                          self.denom.data_ptr(), self.counters.data_ptr(), i0, i1, t0, t1, b1, b2, b3, 1.0 - b1, 1.0 - b2, 1.0 - b3, self.eps1, self.eps2,
+                          self.clip_threshold, self.lr, self.decay_factor(self.lr), grad_scale, has_matrix)
+            call("nk_came_chunk", C.byref(a), ops._stream())
+        s._mark_fresh()
+
+    # -- introspection mirroring the reference's per-parameter state (came.py:151-164) ---------------
+    def param_state(self, index: int) -> dict:
+        """Views of parameter `index`'s state under the reference's keys and logical shapes (conv statistics permuted from the
+        physical [O][KH][I] / [O][KW][I] to [O, I, KH] / [O, I, KW])."""
+        t = self._tens_np[index]
+        p = self.store.params[index]
+        st = {"exp_avg": self.store._view(self.state, int(t["m_off"]), p)}
+        if t["kind"] == 1:
+            d0, d1 = int(t["d0"]), int(t["d1"])
+            for k, off, n in (("exp_avg_sq_row", "r_off", d0), ("exp_avg_sq_col", "c_off", d1), ("exp_avg_res_row", "rr_off", d0),
+                              ("exp_avg_res_col", "cr_off", d1)):
+                st[k] = self.state[int(t[off]):int(t[off]) + n]
+        elif t["kind"] == 2:
+            O, I, KH, KW = p.shape
+            for k, off, K in (("exp_avg_sq_row", "r_off", KH), ("exp_avg_sq_col", "c_off", KW), ("exp_avg_res_row", "rr_off", KH),
+                              ("exp_avg_res_col", "cr_off", KW)):
+                st[k] = self.state[int(t[off]):int(t[off]) + O * K * I].view(O, K, I).permute(0, 2, 1)
+        else:
+            st["exp_avg_sq"] = self.state[int(t["r_off"]):int(t["r_off"]) + p.numel()].view(p.shape)
+        return st
+
+    # -- checkpointing (torch.optim.Optimizer.state_dict layout, the reference's keys; `step` is the group's) -------------
+    def state_dict(self) -> dict:
+        state = {}
+        if self.step_count > 0:
+            for i in range(self.ntensors):
+                state[i] = {k: v.detach().clone().contiguous() for k, v in self.param_state(i).items()}
+        group = dict(lr=self.lr, betas=self.betas, weight_decay=self.weight_decay, weight_decouple=self.weight_decouple,
+                     fixed_decay=self.fixed_decay, ams_bound=False, eps1=self.eps1, eps2=self.eps2, step=self.step_count,
+                     params=list(range(self.ntensors)))
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        state = sd.get("state", {})
+        groups = sd.get("param_groups", [])
+        if not state:
+            self.step_count = 0
+            self.state.zero_()
+            return
+        if self.step_count == 0 and len(state) != self.ntensors:
+            raise ValueError(f"FlatCAME.load_state_dict: state for {len(state)} of {self.ntensors} parameters")
+        for i, st in state.items():
+            i = int(i)
+            if not 0 <= i < self.ntensors:
+                raise ValueError(f"FlatCAME.load_state_dict: parameter index {i} out of range (0..{self.ntensors - 1})")
+            mine = self.param_state(i)
+            if set(mine) != set(k for k in st if k != "step"):
+                raise ValueError(f"FlatCAME.load_state_dict: parameter {i} has state {sorted(st)}, expected {sorted(mine)}")
+            with torch.no_grad():
+                for k, v in mine.items():
+                    if tuple(v.shape) != tuple(st[k].shape):
+                        raise ValueError(f"FlatCAME.load_state_dict: {k} of parameter {i} has shape {tuple(st[k].shape)}, expected {tuple(v.shape)}")
+                    v.copy_(st[k].to(v.device, torch.float32))
+        if groups and "step" in groups[0]:
+            self.step_count = int(groups[0]["step"])
+
+
+def _came_validate(lr, betas, weight_decay, weight_decouple, eps1, eps2, who: str) -> None:
+    """The reference constructor's checks (pytorch_optimizer's validate_learning_rate / validate_betas / validate_non_negative),
+    plus the refusal of `weight_decouple=False` with a weight decay."""
+    if lr < 0.0:
+        raise ValueError(f"[-] learning rate must be positive. got {lr}")
+    if len(betas) != 3 or not all(0.0 <= b < 1.0 for b in betas):
+        raise ValueError(f"[-] betas must be three values in the range [0, 1). got {tuple(betas)}")
+    for name, v in (("weight_decay", weight_decay), ("eps1", eps1), ("eps2", eps2)):
+        if v < 0.0:
+            raise ValueError(f"[-] {name} must be non-negative. got {v}")
+    if not weight_decouple and weight_decay > 0.0:
+        raise NotImplementedError(f"{who}: weight_decouple=False with weight_decay > 0 is not implemented (in the reference it adds wd * p "
+                                  "to p.grad after the update has been computed, which does not change that step)")
 
 
 class FlatEma(torch.nn.Module):

@@ -10,6 +10,11 @@ buffers: a handful of HIP launches for the whole UNet instead of a Python loop o
 fallback: parameters must live in a `FlatParamStore` (the engine's `setup_flat_params()` puts them there; parameters
 handed over on a GPU without one are re-homed into a new store on the first step).
 
+`CAME` (`neurosis.optimizers.came.CAME`, reference `optimizers/came.py`) is the fused `neurosis_amd.optim.FlatCAME` under the
+reference class's constructor: Adafactor's factored second moment plus a first moment and a factored confidence statistic, 4 B of
+state per parameter against AdamW's 8 -- the memory-frugal optimizer with momentum that fine-tuning configs move to.  It lives in
+`neurosis_amd.optimizers.came`, where the prefix swap of its class path lands, and is re-exported here.
+
 `AdamW` is the fused flat AdamW (`nk_adamw_flat`) under `torch.optim.AdamW`'s constructor: not named by the reference's
 configs, provided because "any subclass of torch.optim.Optimizer" is what its YAML comment invites.
 `HybridOptimizer` / `HybridScheduler` (one optimizer per parameter group) are outside the SD/SDXL example configs and are
@@ -24,8 +29,9 @@ from torch.optim import Optimizer
 from torch.optim.lr_scheduler import LambdaLR
 
 from ..optim import FlatAdafactor
+from .came import CAME
 
-__all__ = ["Adafactor", "AdafactorScheduler", "AdamW"]
+__all__ = ["Adafactor", "AdafactorScheduler", "AdamW", "CAME"]
 
 
 def _group_store(group: dict, who: str):
