@@ -25,7 +25,7 @@ extern "C" {
 
 const char* nk_last_error(void);
 int nk_abi_version(void);     /* 5 (round 6: + the four *_geglu*_s entry points; bumped whenever an entry point changes; purely additive
-                                 entry points -- the CAME block below -- leave it as it is) */
+                                 entry points -- the CAME and AdamW8bit blocks below -- leave it as it is) */
 
 /* ------------------------------------------------------------------------------------------------
  * nn.Linear  (modules/attention.py:53,65,70,204-209,283-290,618,639; modules/diffusion/openaimodel.py:273-279,
@@ -389,6 +389,27 @@ typedef struct NkCameArgs {
 } NkCameArgs;
 long nk_came_tensor_bytes(void);
 int nk_came_chunk(const NkCameArgs* args, void* stream);
+
+/* Fused 8-bit blockwise AdamW (bitsandbytes' AdamW8bit algorithm; no reference counterpart) on the flat buffers, ONE launch per step.
+ * Every parameter is cut into blocks of 256 consecutive elements (physical order; a parameter's last block may be short, blocks never
+ * straddle parameters).  Block b keeps m and v as one byte each -- codes into the 256-entry dynamic maps qmap1 (signed, m) and qmap2
+ * (unsigned, v) -- and one fp32 absmax each: m = qmap1[code1] * absmax1[b], v = qmap2[code2] * absmax2[b].  The step dequantizes, updates
+ * m, v and p with the unquantized new moments, and requantizes to the nearest map entry (lowest index on a tie) of m / max|m| over the block.
+ * Tensors with is8 == 0 (below min_8bit_size) keep fp32 m / v in m32 / v32 and take the plain AdamW step.  Layout of `tensors`:
+ * neurosis_amd/csrc/adamw8bit.hip NkA8Tensor (nk_adamw8bit_tensor_bytes() guards the mirror); `blk_start` [ntensors + 1] holds each
+ * tensor's first block (prefix sums of ceil(numel / 256)); codes of block b are bytes [256 b, 256 b + 256) of code1 / code2.
+ * decay = 1 - lr * wd, bc1 = 1 - beta1^t, bc2 = 1 - beta2^t and 1 - beta are computed in double on the host. */
+typedef struct NkAdamW8bitArgs {
+  float* master; const float* grad; void* shadow;
+  unsigned char* code1; unsigned char* code2; float* absmax1; float* absmax2;
+  float* m32; float* v32;
+  const float* qmap1; const float* qmap2;
+  const void* tensors; const int* blk_start;
+  int ntensors, nblocks;
+  float beta1, beta2, one_minus_beta1, one_minus_beta2, eps, lr, decay, bc1, bc2, grad_scale;
+} NkAdamW8bitArgs;
+long nk_adamw8bit_tensor_bytes(void);
+int nk_adamw8bit_step(const NkAdamW8bitArgs* args, void* stream);
 
 /* LitEma.forward (reference modules/ema.py:40-59) as one pass over the flat fp32 buffers (n % 4 == 0):
  * ema[i] -= one_minus_decay * (ema[i] - p[i]).  The decay schedule min(decay, (1+n)/(10+n)) is the host's. */

@@ -119,6 +119,7 @@ SIGNATURES: dict[str, list] = {
     "nk_adafactor_init": [vp, vp],
     "nk_adafactor_chunk": [vp, vp],
     "nk_came_chunk": [vp, vp],
+    "nk_adamw8bit_step": [vp, vp],
 }
 
 # entry points that return a size (long) instead of a status
@@ -136,6 +137,7 @@ SIZE_QUERIES: dict[str, list] = {
     "nk_attention_bwd_ws_floats": [adp],
     "nk_adafactor_tensor_bytes": [],
     "nk_came_tensor_bytes": [],
+    "nk_adamw8bit_tensor_bytes": [],
     "nk_gemm_sk_status": [],
     "nk_health_status": [],
 }

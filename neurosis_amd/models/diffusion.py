@@ -146,9 +146,9 @@ class DiffusionEngine(nn.Module):
     @stream_optimizer.setter
     def stream_optimizer(self, on: bool) -> None:
         if on and getattr(self, "_torch_optimizer", None) is not None:
-            from ..optimizers import CAME
+            from ..optimizers import CAME, AdamW8bit
 
-            if isinstance(self._torch_optimizer, CAME):
+            if isinstance(self._torch_optimizer, (CAME, AdamW8bit)):
                 raise NotImplementedError(f"DiffusionEngine: stream_optimizer (the update streamed block by block behind backward) needs the fused "
                                           f"Adafactor, not {type(self._torch_optimizer).__name__}")
         self._stream_optimizer = bool(on)
@@ -211,12 +211,13 @@ class DiffusionEngine(nn.Module):
         """models/diffusion.py:261-296: one parameter group for the UNet (plus `initial_lr` from `model.base_lr`), one per
         trainable embedder; `self.optimizer(param_groups)`, then `self.scheduler(optimizer)`; the same return value.  What
         comes back must be one of this package's fused optimizers (`neurosis_amd.optimizers.Adafactor` -- the class the example
-        configs name under the prefix swap --, `neurosis_amd.optimizers.came.CAME` or `.AdamW`): the step is a few HIP launches over
-        the flat buffers, and an eager torch optimizer walking 1 700 parameter views would silently replace it, so anything else is
-        refused.  The streamed per-block update and the sharded (rs_ag) exchange drive the chunked Adafactor only: with CAME they raise."""
+        configs name under the prefix swap --, `neurosis_amd.optimizers.came.CAME`, `.AdamW8bit` or `.AdamW`): the step is a few HIP
+        launches over the flat buffers, and an eager torch optimizer walking 1 700 parameter views would silently replace it, so anything
+        else is refused.  The streamed per-block update and the sharded (rs_ag) exchange drive the chunked Adafactor only: with CAME or
+        AdamW8bit they raise."""
         if self.optimizer is None:
             return None
-        from ..optimizers import CAME, Adafactor, AdamW
+        from ..optimizers import CAME, Adafactor, AdamW, AdamW8bit
 
         unet_params = {"name": "UNet", "params": [p for p in self.model.parameters() if p.requires_grad]}
         if getattr(self.model, "base_lr", None) is not None:
@@ -228,11 +229,11 @@ class DiffusionEngine(nn.Module):
             if getattr(embedder, "is_trainable", False):
                 raise NotImplementedError("trainable conditioner embedders are outside the fused training step (SURVEY.md section 8: frozen TE/VAE)")
         opt = self.optimizer(param_groups) if callable(self.optimizer) and not isinstance(self.optimizer, torch.optim.Optimizer) else self.optimizer
-        if not isinstance(opt, (Adafactor, CAME, AdamW)):
+        if not isinstance(opt, (Adafactor, CAME, AdamW8bit, AdamW)):
             raise TypeError(f"DiffusionEngine: optimizer {type(opt).__module__}.{type(opt).__name__} cannot be fused; use "
                             "neurosis_amd.optimizers.Adafactor (the example configs' optimizer under the class_path prefix swap), "
-                            "neurosis_amd.optimizers.came.CAME or neurosis_amd.optimizers.AdamW")
-        if self.stream_optimizer and isinstance(opt, CAME):
+                            "neurosis_amd.optimizers.came.CAME, neurosis_amd.optimizers.AdamW8bit or neurosis_amd.optimizers.AdamW")
+        if self.stream_optimizer and isinstance(opt, (CAME, AdamW8bit)):
             raise NotImplementedError(f"DiffusionEngine: stream_optimizer (the update streamed block by block behind backward) needs the fused "
                                       f"Adafactor, not {type(opt).__name__}")
         self._torch_optimizer = opt

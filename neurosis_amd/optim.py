@@ -11,7 +11,8 @@ per-parameter dict; `state_dict()` / `load_state_dict()` speak the reference opt
 `step`, `exp_avg_sq_row`, `exp_avg_sq_col` / `exp_avg_sq`, `RMS`) so a run resumes with its second moments, step count
 (relative-step warm-up, beta2_t) and per-tensor RMS intact.  `FlatEma` is an `nn.Module` carrying `LitEma`'s buffer names
 (`decay`, `num_updates`, one shadow per parameter), so `model_ema.*` keys of a reference checkpoint load and save unchanged.
-`FlatCAME` mirrors `neurosis.optimizers.came.CAME` (`optimizers/came.py`) the same way, on `csrc/came.hip`.
+`FlatCAME` mirrors `neurosis.optimizers.came.CAME` (`optimizers/came.py`) the same way, on `csrc/came.hip`.  `FlatAdamW8bit` is
+bitsandbytes' blockwise 8-bit AdamW (`AdamW8bit`, named by the reference's sdxl-te config) as one launch of `csrc/adamw8bit.hip`.
 """
 from __future__ import annotations
 
@@ -557,6 +558,213 @@ def _came_validate(lr, betas, weight_decay, weight_decouple, eps1, eps2, who: st
     if not weight_decouple and weight_decay > 0.0:
         raise NotImplementedError(f"{who}: weight_decouple=False with weight_decay > 0 is not implemented (in the reference it adds wd * p "
                                   "to p.grad after the update has been computed, which does not change that step)")
+
+
+A8_BLOCK = 256
+A8_TENSOR_DTYPE = np.dtype([("off", "<i8"), ("soff", "<i8"), ("numel", "<i4"), ("is8", "<i4")])
+
+
+def create_dynamic_map(signed: bool = True, max_exponent_bits: int = 7, total_bits: int = 8) -> Tensor:
+    """The 256-entry quantization map of bitsandbytes' `create_dynamic_map` for 8 bits and 7 exponent bits: for decade i = 0..6, the
+    midpoints of linspace(0.1, 1, n + 1) with n = 2**i (signed) or 2**(i + 1) (unsigned), scaled by 10**(i - 6), and for the signed map
+    their negations too; then 0 and 1.0; sorted, fp32.  The signed map runs from -0.99297 to 1.0 (asymmetric on purpose)."""
+    if (max_exponent_bits, total_bits) != (7, 8):
+        raise NotImplementedError("create_dynamic_map: only the 8-bit map with 7 exponent bits is built")
+    data = []
+    for i in range(max_exponent_bits):
+        n = 2 ** i if signed else 2 ** (i + 1)
+        bounds = torch.linspace(0.1, 1, n + 1)
+        means = ((bounds[:-1] + bounds[1:]) / 2.0).tolist()
+        scale = 10 ** (-(max_exponent_bits - 1) + i)
+        data += [scale * x for x in means]
+        if signed:
+            data += [-scale * x for x in means]
+    data += [0.0, 1.0]
+    assert len(data) == 2 ** total_bits
+    return torch.tensor(sorted(data), dtype=torch.float32)
+
+
+class _A8Args(C.Structure):
+    _fields_ = [("master", C.c_void_p), ("grad", C.c_void_p), ("shadow", C.c_void_p), ("code1", C.c_void_p), ("code2", C.c_void_p),
+                ("absmax1", C.c_void_p), ("absmax2", C.c_void_p), ("m32", C.c_void_p), ("v32", C.c_void_p), ("qmap1", C.c_void_p),
+                ("qmap2", C.c_void_p), ("tensors", C.c_void_p), ("blk_start", C.c_void_p), ("ntensors", C.c_int), ("nblocks", C.c_int),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float),
+                ("lr", C.c_float), ("decay", C.c_float), ("bc1", C.c_float), ("bc2", C.c_float), ("grad_scale", C.c_float)]
+
+
+class FlatAdamW8bit:
+    """8-bit blockwise AdamW on a FlatParamStore (`csrc/adamw8bit.hip`, one launch per step): bitsandbytes' `AdamW8bit` algorithm,
+    restated here as the definition (bit-for-bit interchange with bitsandbytes itself is not claimed).
+
+    * Maps: qmap1 = create_dynamic_map(signed=True) for m, qmap2 = create_dynamic_map(signed=False) for v.
+    * Blocks: 256 consecutive elements of ONE parameter, in its physical order (conv weights [O][KH][KW][I]); the last block of a
+      parameter may be short; blocks never straddle parameters, so nothing depends on where a parameter sits in the store.
+    * Parameters with fewer than `min_8bit_size` elements keep fp32 m / v and take the plain AdamW step.
+    * Per element of an 8-bit parameter: g = grad * grad_scale; m = qmap1[c1] * absmax1[blk], v = qmap2[c2] * absmax2[blk];
+      m = b1 m + (1-b1) g; v = b2 v + (1-b2) g g; p = p (1 - lr wd) - lr (m / bc1) / (sqrt(v / bc2) + eps) with the unquantized new m, v;
+      then per block absmax = max |m| and c1 = the index of the map entry nearest to m / absmax (lowest index on a tie; absmax 0 stores
+      the code of 0.0); the same for v with qmap2.  bc1 = 1 - b1^t, bc2 = 1 - b2^t, 1 - b and 1 - lr wd are computed in double.
+    * Initial state: absmax 0 and every code the code of 0.0 (m = v = 0).
+
+    State: one byte each for m and v plus two fp32 absmax per 256 elements (2.03 B/param against AdamW's 8).  `state_dict()` speaks
+    bitsandbytes' per-parameter keys (`state1`, `state2`, `absmax1`, `absmax2`, `qmap1`, `qmap2`, `step`; fp32 `state1` / `state2` only
+    for small parameters)."""
+
+    def __init__(self, store, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 min_8bit_size: int = 4096):
+        _adamw_validate(lr, betas, eps, weight_decay)
+        if query("nk_adamw8bit_tensor_bytes") != A8_TENSOR_DTYPE.itemsize:
+            raise RuntimeError("FlatAdamW8bit: tensor table layout differs from the HIP library's")
+        self.store = store
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(float(b) for b in betas), float(eps), float(weight_decay)
+        self.min_8bit_size = int(min_8bit_size)
+        self.step_count = 0
+        dev = store.master.device
+        layout = self.layout([tuple(p.shape) for p in store.params], self.min_8bit_size)
+        tens = np.zeros(len(store.params), dtype=A8_TENSOR_DTYPE)
+        tens["off"] = store.offsets
+        tens["soff"], tens["numel"], tens["is8"] = layout["soff"], layout["numel"], layout["is8"]
+        if int(layout["numel"].max()) >= 2 ** 31 or layout["nblocks"] >= 2 ** 31 - 16:     # the kernel indexes elements of a tensor and blocks in int
+            raise NotImplementedError("FlatAdamW8bit: 2^31 or more elements in one parameter, or 2^31 - 16 or more blocks in one store")
+        self._tens_np = tens
+        self._blk = layout["blk_start"]
+        self.ntensors, self.nblocks = len(store.params), int(layout["nblocks"])
+        self.tensors = torch.from_numpy(tens.view(np.uint8).copy()).to(dev)
+        self.blk_start = torch.from_numpy(self._blk.astype(np.int32)).to(dev)
+        self.qmap1 = create_dynamic_map(signed=True).to(dev)
+        self.qmap2 = create_dynamic_map(signed=False).to(dev)
+        self.code1 = torch.empty(self.nblocks * A8_BLOCK, dtype=torch.uint8, device=dev)
+        self.code2 = torch.empty(self.nblocks * A8_BLOCK, dtype=torch.uint8, device=dev)
+        self.absmax1 = torch.zeros(self.nblocks, dtype=torch.float32, device=dev)
+        self.absmax2 = torch.zeros(self.nblocks, dtype=torch.float32, device=dev)
+        self.m32 = torch.zeros(max(int(layout["small"]), 1), dtype=torch.float32, device=dev)
+        self.v32 = torch.zeros_like(self.m32)
+        self.zero_codes = (int(torch.nonzero(self.qmap1.cpu() == 0)[0]), int(torch.nonzero(self.qmap2.cpu() == 0)[0]))
+        self.reset_state()
+
+    @staticmethod
+    def layout(shapes, min_8bit_size: int = 4096) -> dict:
+        """Per parameter shape: numel, is8, first block (blk_start, with the total appended) and fp32-state offset (soff, 64-aligned);
+        plus nblocks and the fp32 state size `small`.  Every parameter has blocks (the fp32 ones leave their codes unused)."""
+        numel = np.array([int(np.prod(s)) for s in shapes], dtype=np.int64)
+        is8 = (numel >= min_8bit_size).astype(np.int32)
+        nblk = -(-numel // A8_BLOCK)
+        blk_start = np.concatenate([[0], np.cumsum(nblk)]).astype(np.int64)
+        small = np.where(is8 == 0, (numel + 63) // 64 * 64, 0)
+        soff = np.concatenate([[0], np.cumsum(small)[:-1]]).astype(np.int64)
+        return {"numel": numel, "is8": is8, "blk_start": blk_start, "soff": soff, "nblocks": int(blk_start[-1]), "small": int(small.sum())}
+
+    @classmethod
+    def state_bytes(cls, shapes, min_8bit_size: int = 4096) -> int:
+        """Bytes of optimizer state for these parameter shapes: the codes (one byte each for m and v, whole blocks) and the two fp32 absmax
+        of every 8-bit parameter's blocks, fp32 m and v of the small ones."""
+        lay = cls.layout(shapes, min_8bit_size)
+        nblk = np.diff(lay["blk_start"])
+        return int((nblk * (2 * A8_BLOCK + 8) * lay["is8"]).sum() + 8 * (lay["numel"] * (1 - lay["is8"])).sum())
+
+    def reset_state(self) -> None:
+        """Step 0: absmax 0, every code the code of 0.0, fp32 state 0."""
+        self.code1.fill_(self.zero_codes[0])
+        self.code2.fill_(self.zero_codes[1])
+        self.absmax1.zero_()
+        self.absmax2.zero_()
+        self.m32.zero_()
+        self.v32.zero_()
+        self.step_count = 0
+
+    def step(self, grad_scale: float = 1.0, lr: Optional[float] = None) -> None:
+        """One AdamW8bit update of every parameter with the gradients multiplied by `grad_scale` (the data-parallel mean); `lr` overrides
+        the constructor's (what a torch LR scheduler set on the group).  Also rewrites the bf16 shadows."""
+        if lr is not None:
+            self.lr = float(lr)
+        self.step_count += 1
+        s = self.store
+        b1, b2 = self.betas
+        t = self.step_count
+        a = _A8Args(s.master.data_ptr(), s.grad.data_ptr(), s.shadow.data_ptr(), self.code1.data_ptr(), self.code2.data_ptr(),
+                    self.absmax1.data_ptr(), self.absmax2.data_ptr(), self.m32.data_ptr(), self.v32.data_ptr(), self.qmap1.data_ptr(),
+                    self.qmap2.data_ptr(), self.tensors.data_ptr(), self.blk_start.data_ptr(), self.ntensors, self.nblocks,
+                    b1, b2, 1.0 - b1, 1.0 - b2, self.eps, self.lr, 1.0 - self.lr * self.weight_decay, 1.0 - b1 ** t, 1.0 - b2 ** t, grad_scale)
+        call("nk_adamw8bit_step", C.byref(a), ops._stream())
+        s._mark_fresh()
+
+    # -- introspection under bitsandbytes' per-parameter keys ------------------------------------------------------------------------------
+    def param_state(self, index: int) -> dict:
+        """Views of parameter `index`'s state: `state1` / `state2` in the parameter's shape (uint8 codes, or fp32 m / v for a small
+        parameter); for 8-bit parameters also `absmax1` / `absmax2` (one per block) and the maps."""
+        t = self._tens_np[index]
+        p = self.store.params[index]
+        if not t["is8"]:
+            return {"state1": self.store._view(self.m32, int(t["soff"]), p), "state2": self.store._view(self.v32, int(t["soff"]), p)}
+        b0, b1 = int(self._blk[index]), int(self._blk[index + 1])
+        return {"state1": self.store._view(self.code1, b0 * A8_BLOCK, p), "state2": self.store._view(self.code2, b0 * A8_BLOCK, p),
+                "absmax1": self.absmax1[b0:b1], "absmax2": self.absmax2[b0:b1], "qmap1": self.qmap1, "qmap2": self.qmap2}
+
+    # -- checkpointing (torch.optim.Optimizer.state_dict layout, bitsandbytes' keys) ---------------------------------------------------------
+    def state_dict(self) -> dict:
+        state = {}
+        if self.step_count > 0:
+            for i in range(self.ntensors):
+                state[i] = {k: v.detach().clone().contiguous() for k, v in self.param_state(i).items()}
+                state[i]["step"] = self.step_count
+        group = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, min_8bit_size=self.min_8bit_size,
+                     params=list(range(self.ntensors)))
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        state = sd.get("state", {})
+        if not state:
+            self.reset_state()
+            return
+        if len(state) != self.ntensors:
+            raise ValueError(f"FlatAdamW8bit.load_state_dict: state for {len(state)} of {self.ntensors} parameters")
+        steps = set()
+        for i, st in state.items():
+            i = int(i)
+            if not 0 <= i < self.ntensors:
+                raise ValueError(f"FlatAdamW8bit.load_state_dict: parameter index {i} out of range (0..{self.ntensors - 1})")
+            mine = self.param_state(i)
+            if set(mine) != set(k for k in st if k != "step"):
+                raise ValueError(f"FlatAdamW8bit.load_state_dict: parameter {i} has state {sorted(st)}, expected {sorted(mine)} "
+                                 f"(min_8bit_size {self.min_8bit_size})")
+            for k in ("qmap1", "qmap2"):
+                if k in mine and not torch.equal(st[k].detach().to("cpu", torch.float32), mine[k].cpu()):
+                    raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} differs from this optimizer's quantization map")
+            for k in ("absmax1", "absmax2"):
+                if k in mine and tuple(st[k].shape) != tuple(mine[k].shape):
+                    raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} has {tuple(st[k].shape)} blocks, expected "
+                                     f"{tuple(mine[k].shape)} (block size {A8_BLOCK})")
+            for k in ("state1", "state2"):
+                if tuple(st[k].shape) != tuple(mine[k].shape) or st[k].dtype != mine[k].dtype:
+                    raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} is {st[k].dtype} {tuple(st[k].shape)}, "
+                                     f"expected {mine[k].dtype} {tuple(mine[k].shape)}")
+            steps.add(int(st["step"]))
+        if len(steps) != 1:
+            raise ValueError(f"FlatAdamW8bit.load_state_dict: per-parameter step counts differ ({sorted(steps)}); the fused update keeps one")
+        self.reset_state()
+        with torch.no_grad():
+            for i, st in state.items():
+                mine = self.param_state(int(i))
+                for k in ("state1", "state2", "absmax1", "absmax2"):
+                    if k in mine:
+                        mine[k].copy_(st[k].to(mine[k].device))
+        self.step_count = steps.pop()
+
+
+def _adamw_validate(lr, betas, eps, weight_decay) -> None:
+    """torch.optim.AdamW's constructor checks."""
+    if not 0.0 <= lr:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if not 0.0 <= eps:
+        raise ValueError(f"Invalid epsilon value: {eps}")
+    if len(betas) != 2:
+        raise ValueError(f"Invalid betas: {tuple(betas)}")
+    if not 0.0 <= betas[0] < 1.0:
+        raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+    if not 0.0 <= betas[1] < 1.0:
+        raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+    if not 0.0 <= weight_decay:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
 
 
 class FlatEma(torch.nn.Module):

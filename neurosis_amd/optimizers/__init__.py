@@ -15,6 +15,12 @@ reference class's constructor: Adafactor's factored second moment plus a first m
 state per parameter against AdamW's 8 -- the memory-frugal optimizer with momentum that fine-tuning configs move to.  It lives in
 `neurosis_amd.optimizers.came`, where the prefix swap of its class path lands, and is re-exported here.
 
+`AdamW8bit` is bitsandbytes' blockwise 8-bit AdamW (`bitsandbytes.optim.AdamW8bit`, the optimizer of the reference's
+`configs/sdxl/sdxl-te.example.yaml`) fused as `neurosis_amd.optim.FlatAdamW8bit` under bitsandbytes' constructor: one byte each for m
+and v plus two fp32 absmax per 256 elements, 2.03 B of state per parameter against AdamW's 8.  No prefix swap reaches it: a config that
+names `bitsandbytes.optim.AdamW8bit` selects it by changing that `class_path` to `neurosis_amd.optimizers.AdamW8bit` (this package
+provides no `bitsandbytes` module).  It lives in `neurosis_amd.optimizers.adamw8bit` and is re-exported here.
+
 `AdamW` is the fused flat AdamW (`nk_adamw_flat`) under `torch.optim.AdamW`'s constructor: not named by the reference's
 configs, provided because "any subclass of torch.optim.Optimizer" is what its YAML comment invites.
 `HybridOptimizer` / `HybridScheduler` (one optimizer per parameter group) are outside the SD/SDXL example configs and are
@@ -29,9 +35,10 @@ from torch.optim import Optimizer
 from torch.optim.lr_scheduler import LambdaLR
 
 from ..optim import FlatAdafactor
+from .adamw8bit import AdamW8bit
 from .came import CAME
 
-__all__ = ["Adafactor", "AdafactorScheduler", "AdamW", "CAME"]
+__all__ = ["Adafactor", "AdafactorScheduler", "AdamW", "AdamW8bit", "CAME"]
 
 
 def _group_store(group: dict, who: str):
