@@ -127,7 +127,10 @@ __device__ __forceinline__ void bn_sum_partials(const float* __restrict__ part, 
 #pragma unroll
     for (int j = 0; j < 16; ++j) s += sh[0][j][tx], q += sh[1][j][tx];
 }
-// forward finalisation: mean, rstd (biased variance), running statistics (unbiased variance, momentum)
+// forward finalisation: mean, rstd (biased variance), running statistics (unbiased variance, momentum).
+// One-pass variance, q / M - m^2 in fp32: its error grows as (|mean| / sigma)^2.  Measured at M = 131 072 (tools/norm_one_pass_limit.py):
+// relative rstd error 2.0e-4 at |mean| / sigma = 32, 7.3e-4 at 64, 2.7e-3 at 128, against half a bf16 ulp of 1.95e-3: beyond ~64 the
+// statistics are no longer bf16-accurate.
 __global__ __launch_bounds__(1024) void bn_stats_finalize_kernel(const float* __restrict__ part, int slabs, int C, long M, float eps,
                                                                  float momentum, float* __restrict__ mean, float* __restrict__ rstd,
                                                                  float* __restrict__ running_mean, float* __restrict__ running_var) {
