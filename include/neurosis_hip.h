@@ -166,7 +166,7 @@ typedef struct NkAttnDesc {
   long sdq, sdk, sdv, sdo;      /* backward only: row strides of dq, dk, dv, do */
   long bdq, bdk, bdv, bdo;      /* backward only: batch strides */
   float scale;                  /* D^-0.5 */
-  int causal;                   /* forward only: key j contributes to query i iff j <= i (Lq == Lk) */
+  int causal;                   /* key j contributes to query i iff j <= i (Lq == Lk); backward: nk_attention_bwd_causal only */
 } NkAttnDesc;
 int nk_attention_fwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, void* o, float* lse,
                      void* stream);
@@ -174,6 +174,10 @@ int nk_attention_fwd(const NkAttnDesc* d, const void* q, const void* k, const vo
 long nk_attention_bwd_ws_floats(const NkAttnDesc* d);
 int nk_attention_bwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, const void* o,
                      const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* delta_ws, void* stream);
+/* Backward of the CAUSAL forward (d->causal, head dim 64, Lq == Lk <= 96: the trainable text towers' self-attention).  Same arguments as
+ * nk_attention_bwd without the workspace; dq / dk / dv 16-byte aligned.  (nk_attention_bwd refuses causal descriptors.) */
+int nk_attention_bwd_causal(const NkAttnDesc* d, const void* q, const void* k, const void* v, const void* o,
+                            const float* lse, const void* d_o, void* dq, void* dk, void* dv, void* stream);
 /* in-place row softmax on bf16 [M][L]: unfused single-head attention = nk_linear_fwd (q k^T) -> nk_softmax_rows -> nk_linear_dgrad (p v).
  * Serves head dims the flash kernels do not take, and the chunked recomputing backward of the VAE mid block (d = 512) beyond 2 048 tokens per
  * sample (ops.attention512_fwd; up to there nk_attention_bwd's flash kernels run); d = 512 forward and backward are nk_attention_fwd / _bwd. */
@@ -307,6 +311,20 @@ int nk_lpips_layer_bwd(const void* f0, const void* f1, const float* w, const flo
  * text tower, models/text_encoder/clip.py:333-343); mode 1: "quick_gelu" x * sigmoid(1.702 x) (HF CLIPTextModel of
  * openai/clip-vit-large-patch14, models/text_encoder/clip.py:49-56). */
 int nk_gelu_fwd(const void* x, void* y, long n, int mode, void* stream);
+/* dx = dy * gelu'(x), same modes as nk_gelu_fwd; bf16 in and out, fp32 arithmetic (trainable text towers) */
+int nk_gelu_bwd(const void* dy, const void* x, void* dx, long n, int mode, void* stream);
+/* Token + position embedding backward of the text towers (x[b * L + l] = table[ids[b][l]] + pos[l]): dx [B * L][C] bf16 (row stride ldx);
+ * dtable [V][C] and dpos [P][C] fp32 gradients.  accumulate 0: both are overwritten and rows no token (position) hit come out zero;
+ * 1: added to; 2: written, the caller guarantees both are zero already (no clearing pass).  Deterministic: every row is a sum in token
+ * order, no atomics.  ids int64 [B * L], 0 <= id < V; B * L <= NK_EMBEDDING_BWD_MAX_TOKENS (the duplicate-id scans are quadratic). */
+#define NK_EMBEDDING_BWD_MAX_TOKENS 8192
+int nk_embedding_bwd(const long long* ids, const void* dx, long ldx, float* dtable, float* dpos, int B, int L, int V, int P, int C,
+                     int accumulate, void* stream);
+/* backward of a row gather sel[b] = x[b * L + idx[b]]: dx [B * L][C] bf16 (dense) = 0 except those rows = dsel[b] (row stride ldsel) */
+int nk_gather_rows_bwd(const void* dsel, long ldsel, const long long* idx, void* dx, int B, int L, int C, void* stream);
+/* dw [K][N] fp32 (row stride lddw) (+)= x^T dy over M <= 256 rows (x [M][K], dy [M][N] bf16): weight gradients the tile engine does not take
+ * (bigG's text_projection sees only the B end-of-text rows); fixed-order sums */
+int nk_wgrad_few_rows(const void* x, long ldx, const void* dy, long lddy, float* dw, long lddw, int M, int K, int N, int accumulate, void* stream);
 
 /* timestep_embedding (modules/diffusion/util.py:152-177): out[B][dim] bf16 = [cos | sin](t * freq) */
 int nk_timestep_embedding(const float* t, void* out, int B, int dim, float max_period, void* stream);

@@ -1112,7 +1112,10 @@ __global__ __launch_bounds__(NW * 64, 3) void attn64_bwd_dkdv_kernel(const AttnP
 // workgroups) while the others are on the next tile.  Q' = bf16(Q scale log2 e), -lse2 and -delta = -rowsum(dO o O) are made on the fly
 // per 32-query tile, from rows fetched two tiles ahead by LDS-DMA.
 // dK / dV leave as fp32 partials per query split (summed by attn_dkv_reduce_kernel) or, with one split, directly.
+// CAUSAL (the trainable text towers' self-attention, Lq == Lk <= 96, nk_attention_bwd_causal): P recomputed from the causal forward's
+// log-sum-exp is zeroed where key j > query i, which zeroes dS there too (dS = P o (dP - delta)); every other step is the same.
 #define SMALL_DSROW 72                               // bytes per row of the dS^T image [96 keys][32 queries] (64 + 8: conflict-free 8-byte writes)
+template <bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void attn64_bwd_small_kernel(const AttnParams p) {
   constexpr int TILE = 32 * 128, STAGE = 3 * TILE + 256 + 1024;   // Q' image, dO image, [32] -lse2, [32] -delta | O rows | 4 x 256 B raw log-sum-exp
   constexpr int KIMG = 96 * 128, DSBUF = 96 * SMALL_DSROW;
@@ -1284,10 +1287,20 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_small_kernel(const AttnPara
         A64_RDTR(olo[0][0], o00, 0); A64_RDTR(olo[0][1], o01, 0); A64_RDTR(ohi[0][0], o10, 0); A64_RDTR(ohi[0][1], o11, 0);
         A64_RDTR(olo[1][0], o00, 2048); A64_RDTR(olo[1][1], o01, 2048); A64_RDTR(ohi[1][0], o10, 2048); A64_RDTR(ohi[1][1], o11, 2048);
       }
+      if constexpr (CAUSAL) {
+        // accumulator register r of this lane: key k0 + kl, query q0 + acc_row(r, h5)
+        const int qrel = (t_lo + t) * 32 - (k0 + kl);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        s[r] = EXP2(s[r]);
-        dp[r] *= s[r];
+        for (int r = 0; r < 16; ++r) {
+          s[r] = qrel + acc_row(r, h5) >= 0 ? EXP2(s[r]) : 0.f;
+          dp[r] *= s[r];
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          s[r] = EXP2(s[r]);
+          dp[r] *= s[r];
+        }
       }
       if (tail_keys) {
 #pragma unroll
@@ -1802,6 +1815,7 @@ static int attn_qsplit(const NkAttnDesc* d) {
   while (s < 16 && base * s < 512 && d->Lq / (s * 2) >= 128) s *= 2;
   return s;
 }
+#define ATTN64_SMALL_SMEM (96 * 128 + 3 * (3 * 32 * 128 + 256 + 1024) + 2 * 96 * SMALL_DSROW)
 extern "C" long nk_attention_bwd_ws_floats(const NkAttnDesc* d) {
   int s = attn_qsplit(d);
   if (d->D == 64 && d->Lk <= 96 && attn_small_qsplit(d) > s) s = attn_small_qsplit(d);
@@ -1855,10 +1869,10 @@ extern "C" int nk_attention_bwd(const NkAttnDesc* d, const void* q, const void* 
     const Attn64Ws w = Attn64Ws::make(d->B, d->H, d->Lq);
     p.qsplit = attn_small_qsplit(d);
     p.dkv_part = p.qsplit > 1 ? delta_ws + w.part : nullptr;
-    const int smem = 96 * 128 + 3 * (3 * 32 * 128 + 256 + 1024) + 2 * 96 * SMALL_DSROW;
-    set_smem(attn64_bwd_small_kernel, smem);
+    const int smem = ATTN64_SMALL_SMEM;
+    set_smem(attn64_bwd_small_kernel<false>, smem);
     const dim3 lgrid = attn_grid(p, dim3(p.qsplit, d->H, d->B));
-    hipLaunchKernelGGL(attn64_bwd_small_kernel, lgrid, dim3(256), smem, stream, p);
+    hipLaunchKernelGGL(attn64_bwd_small_kernel<false>, lgrid, dim3(256), smem, stream, p);
     if (int e = nk_check_launch("attn64_bwd_small_kernel")) return e;
     if (p.qsplit > 1) {
       long total = (long)d->B * d->Lk * ((long)d->H * d->D / 4);
@@ -1941,4 +1955,36 @@ extern "C" int nk_attention_bwd(const NkAttnDesc* d, const void* q, const void* 
     }
   }
   return NK_OK;
+}
+
+// Backward of the CAUSAL forward (nk_attention_fwd with d->causal): the text towers when they are trained (configs/sdxl/sdxl-te.example.yaml).
+// Head dim 64, Lq == Lk <= 96 (77 tokens): the one-kernel backward above in its causal instantiation, one query split, so dK / dV leave
+// directly and no workspace is needed.  nk_attention_bwd keeps refusing causal descriptors.
+extern "C" int nk_attention_bwd_causal(const NkAttnDesc* d, const void* q, const void* k, const void* v, const void* o,
+                                       const float* lse, const void* d_o, void* dq, void* dk, void* dv, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (int e = attn_check(d)) return e;
+  NK_CHECK_ARG(q && k && v && o && lse && d_o && dq && dk && dv);
+  NK_CHECK_ARG(d->causal && d->D == 64 && d->Lq == d->Lk && d->Lk <= 96);
+  NK_CHECK_ARG((d->sdq & 7) == 0 && (d->sdk & 7) == 0 && (d->sdv & 7) == 0 && (d->sdo & 7) == 0);
+  NK_CHECK_ARG((d->bdq & 7) == 0 && (d->bdk & 7) == 0 && (d->bdv & 7) == 0 && (d->bdo & 7) == 0);
+  NK_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 15) == 0 &&
+               ((uintptr_t)d_o & 15) == 0);
+  NK_CHECK_ARG(((uintptr_t)dq & 15) == 0 && ((uintptr_t)dk & 15) == 0 && ((uintptr_t)dv & 15) == 0);
+  AttnParams p = {};
+  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.Oc = (const bf16_t*)o;
+  p.dO = (const bf16_t*)d_o; p.dQ = (bf16_t*)dq; p.dK = (bf16_t*)dk; p.dV = (bf16_t*)dv;
+  p.LSE = (float*)lse;
+  p.B = d->B; p.H = d->H; p.Lq = d->Lq; p.Lk = d->Lk; p.D = d->D;
+  p.sq = d->sq; p.sk = d->sk; p.sv = d->sv; p.so = d->so;
+  p.bq = d->bq; p.bk = d->bk; p.bv = d->bv; p.bo = d->bo;
+  p.sdq = d->sdq; p.sdk = d->sdk; p.sdv = d->sdv; p.sdo = d->sdo;
+  p.bdq = d->bdq; p.bdk = d->bdk; p.bdv = d->bdv; p.bdo = d->bdo;
+  p.scale = d->scale;
+  p.causal = 1;
+  p.qsplit = 1;
+  set_smem(attn64_bwd_small_kernel<true>, ATTN64_SMALL_SMEM);
+  const dim3 lgrid = attn_grid(p, dim3(1, d->H, d->B));
+  hipLaunchKernelGGL(attn64_bwd_small_kernel<true>, lgrid, dim3(256), ATTN64_SMALL_SMEM, stream, p);
+  return nk_check_launch("attn64_bwd_small_kernel<causal>");
 }

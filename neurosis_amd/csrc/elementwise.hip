@@ -147,7 +147,7 @@ extern "C" int nk_silu_bwd(const void* dy, const void* x, void* dx, long n, void
   return nk_check_launch("silu_bwd");
 }
 
-// ---- GELU of the CLIP text transformers (forward only: the encoders are frozen) -------------------
+// ---- GELU of the CLIP text transformers ---------------------------------------------------------
 // mode 0: exact erf form (open_clip's nn.GELU); mode 1: quick_gelu x * sigmoid(1.702 x) (openai/clip-vit-large-patch14)
 template <int MODE>
 __global__ void gelu_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long n8) {
@@ -167,6 +167,146 @@ extern "C" int nk_gelu_fwd(const void* x, void* y, long n, int mode, void* strea
   else
     hipLaunchKernelGGL(gelu_fwd_kernel<1>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
   return nk_check_launch("gelu_fwd");
+}
+
+// GELU backward (trainable text towers): dx = dy * gelu'(x), fp32 arithmetic on bf16 data, the same modes as the forward
+//   mode 0: gelu'(x) = Phi(x) + x phi(x);  mode 1: s + 1.702 x s (1 - s), s = sigmoid(1.702 x)
+template <int MODE>
+__global__ void gelu_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, bf16_t* __restrict__ dx, long n8) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    float g[8], f[8];
+    unpack8(*(const uint4_t*)(dy + i * 8), g);
+    unpack8(*(const uint4_t*)(x + i * 8), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float d;
+      if (MODE == 0) {
+        d = 0.5f * (1.0f + erff(f[e] * 0.70710678118654752f)) + f[e] * 0.39894228040143268f * __expf(-0.5f * f[e] * f[e]);
+      } else {
+        const float sg = 1.0f / (1.0f + __expf(-1.702f * f[e]));
+        d = sg + 1.702f * f[e] * sg * (1.0f - sg);
+      }
+      g[e] *= d;
+    }
+    *(uint4_t*)(dx + i * 8) = pack8(g);
+  }
+}
+extern "C" int nk_gelu_bwd(const void* dy, const void* x, void* dx, long n, int mode, void* stream) {
+  NK_CHECK_ARG(dy && x && dx && n > 0 && (n & 7) == 0 && (mode == 0 || mode == 1));
+  NK_CHECK_ARG(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0);     // 16-byte accesses
+  if (mode == 0)
+    hipLaunchKernelGGL(gelu_bwd_kernel<0>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x,
+                       (bf16_t*)dx, n >> 3);
+  else
+    hipLaunchKernelGGL(gelu_bwd_kernel<1>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x,
+                       (bf16_t*)dx, n >> 3);
+  return nk_check_launch("gelu_bwd");
+}
+
+// ---- token + position embedding backward (trainable text towers) --------------------------------
+// Workgroup w < N = B * L owns token w: if w is the FIRST token with its id v, it sums the gradient rows of every token with id v in token
+// order and writes (or adds) table row v; later tokens with the same id do nothing.  Workgroup N + l sums position l over the batch, b = 0 .. B-1.
+// Fixed-order sums, no atomics: the result does not depend on scheduling (a padded prompt repeats one id some 60 times).  Each lane owns
+// 8 columns.  The ids are wave-uniform loads; the O(N^2) id scan is nothing at N = 308.
+__global__ void embedding_bwd_kernel(const long long* __restrict__ ids, const bf16_t* __restrict__ dx, long ldx, float* __restrict__ dtab,
+                                     float* __restrict__ dpos, int N, int L, int V, int C, int accumulate) {
+  const int w = blockIdx.x;
+  const int c8 = C >> 3;
+  if (w < N) {
+    const long long v = ids[w];
+    if (v < 0 || v >= V) return;      // (the forward's lookup rejects such ids; never write outside the table)
+    int seen = 0;
+    for (int j = threadIdx.x; j < w; j += blockDim.x) seen |= ids[j] == v;
+    if (__syncthreads_or(seen)) return;
+    for (int ch = threadIdx.x; ch < c8; ch += blockDim.x) {
+      float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (int t = w; t < N; ++t) {
+        if (ids[t] != v) continue;
+        float f[8];
+        unpack8(*(const uint4_t*)(dx + (long)t * ldx + ch * 8), f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += f[e];
+      }
+      float4_t* out = (float4_t*)(dtab + v * (long)C + ch * 8);
+      float4_t lo = {acc[0], acc[1], acc[2], acc[3]}, hi = {acc[4], acc[5], acc[6], acc[7]};
+      if (accumulate) { lo += out[0]; hi += out[1]; }
+      out[0] = lo;
+      out[1] = hi;
+    }
+  } else {
+    const int l = w - N, B = N / L;
+    for (int ch = threadIdx.x; ch < c8; ch += blockDim.x) {
+      float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (int b = 0; b < B; ++b) {
+        float f[8];
+        unpack8(*(const uint4_t*)(dx + ((long)b * L + l) * ldx + ch * 8), f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += f[e];
+      }
+      float4_t* out = (float4_t*)(dpos + (long)l * C + ch * 8);
+      float4_t lo = {acc[0], acc[1], acc[2], acc[3]}, hi = {acc[4], acc[5], acc[6], acc[7]};
+      if (accumulate) { lo += out[0]; hi += out[1]; }
+      out[0] = lo;
+      out[1] = hi;
+    }
+  }
+}
+extern "C" int nk_embedding_bwd(const long long* ids, const void* dx, long ldx, float* dtable, float* dpos, int B, int L, int V, int P, int C,
+                                int accumulate, void* stream_) {
+  NK_CHECK_ARG(ids && dx && dtable && dpos && B > 0 && L > 0 && L <= P && V > 0 && C > 0 && (C & 7) == 0 && (ldx & 7) == 0 && ldx >= C);
+  NK_CHECK_ARG(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dtable & 15) == 0 && ((uintptr_t)dpos & 15) == 0);
+  NK_CHECK_ARG((long)B * L <= NK_EMBEDDING_BWD_MAX_TOKENS && accumulate >= 0 && accumulate <= 2);     // (the id scans are quadratic in B * L)
+  hipStream_t stream = (hipStream_t)stream_;
+  if (accumulate == 0) {     // overwrite: rows no token (no position) hit are zero; (2: the caller's buffers are zero already)
+    if (hipMemsetAsync(dtable, 0, (size_t)V * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
+    if (hipMemsetAsync(dpos, 0, (size_t)P * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
+  }
+  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(B * L + L), dim3(128), 0, stream, ids, (const bf16_t*)dx, ldx, dtable, dpos, B * L, L, V, C,
+                     accumulate == 1);
+  return nk_check_launch("embedding_bwd");
+}
+
+// ---- backward of a row gather: dx[B * L][C] = 0 except row b * L + idx[b] = dsel[b] (idx read on the device; 0 <= idx[b] < L) ----
+__global__ void gather_rows_bwd_kernel(const bf16_t* __restrict__ dsel, long ldsel, const long long* __restrict__ idx, bf16_t* __restrict__ dx,
+                                       int L, int c8, long n8) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+    const long r = i / c8;
+    const int ch = (int)(i - r * c8);
+    const int b = (int)(r / L), l = (int)(r - (long)b * L);
+    uint4_t z = {0u, 0u, 0u, 0u};
+    if (idx[b] == l) z = *(const uint4_t*)(dsel + (long)b * ldsel + ch * 8);
+    *(uint4_t*)(dx + i * 8) = z;
+  }
+}
+extern "C" int nk_gather_rows_bwd(const void* dsel, long ldsel, const long long* idx, void* dx, int B, int L, int C, void* stream) {
+  NK_CHECK_ARG(dsel && idx && dx && B > 0 && L > 0 && C > 0 && (C & 7) == 0 && (ldsel & 7) == 0 && ldsel >= C);
+  NK_CHECK_ARG(((uintptr_t)dsel & 15) == 0 && ((uintptr_t)dx & 15) == 0);                                 // 16-byte accesses
+  const long n8 = (long)B * L * (C >> 3);
+  hipLaunchKernelGGL(gather_rows_bwd_kernel, dim3(ew_blocks(n8)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)dsel, ldsel, idx,
+                     (bf16_t*)dx, L, C >> 3, n8);
+  return nk_check_launch("gather_rows_bwd");
+}
+
+// ---- weight gradient contracted over a few rows: dw[K][N] (+)= sum_m x[m][k] dy[m][n], m = 0 .. M-1 in order (M <= 256) ----------
+// bigG's text_projection [width, embed_dim] (read transposed by the forward) sees only the B end-of-text rows.  One lane per output.
+__global__ void wgrad_few_rows_kernel(const bf16_t* __restrict__ x, long ldx, const bf16_t* __restrict__ dy, long lddy, float* __restrict__ dw,
+                                      long lddw, int M, int K, int N, int accumulate) {
+  const long total = (long)K * N;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int k = (int)(i / N), n = (int)(i - (long)k * N);
+    float acc = 0.f;
+    for (int m = 0; m < M; ++m) acc += bf2f(x[(long)m * ldx + k]) * bf2f(dy[(long)m * lddy + n]);
+    float* o = dw + (long)k * lddw + n;
+    *o = accumulate ? *o + acc : acc;
+  }
+}
+extern "C" int nk_wgrad_few_rows(const void* x, long ldx, const void* dy, long lddy, float* dw, long lddw, int M, int K, int N, int accumulate,
+                                 void* stream) {
+  NK_CHECK_ARG(x && dy && dw && M > 0 && M <= 256 && K > 0 && N > 0 && ldx >= K && lddy >= N && lddw >= N);
+  const long total = (long)K * N;
+  hipLaunchKernelGGL(wgrad_few_rows_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
+                     (const bf16_t*)dy, lddy, dw, lddw, M, K, N, accumulate);
+  return nk_check_launch("wgrad_few_rows");
 }
 
 // ---- out = a + b (gradient join where a tensor feeds two consumers) ----------------------------

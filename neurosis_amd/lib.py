@@ -62,6 +62,7 @@ SIGNATURES: dict[str, list] = {
     "nk_conv2d_wgrad": [cdp, vp, vp, vp, i32, vp],
     "nk_attention_fwd": [adp, vp, vp, vp, vp, vp, vp],
     "nk_attention_bwd": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "nk_attention_bwd_causal": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "nk_softmax_rows": [vp, i64, i32, vp],
     "nk_softmax_rows_bwd": [vp, vp, i64, i32, f32, vp],
     "nk_groupnorm_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
@@ -81,6 +82,10 @@ SIGNATURES: dict[str, list] = {
     "nk_geglu_bwd_s": [vp, vp, vp, i64, i32, vp],
     "nk_silu_fwd": [vp, vp, i64, vp],
     "nk_gelu_fwd": [vp, vp, i64, i32, vp],
+    "nk_gelu_bwd": [vp, vp, vp, i64, i32, vp],
+    "nk_embedding_bwd": [vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "nk_gather_rows_bwd": [vp, i64, vp, vp, i32, i32, i32, vp],
+    "nk_wgrad_few_rows": [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
     "nk_leaky_relu_fwd": [vp, vp, i64, f32, vp],
     "nk_leaky_relu_bwd": [vp, vp, vp, i64, f32, vp],
     "nk_maxpool2x2_fwd": [vp, vp, i32, i32, i32, i32, vp],

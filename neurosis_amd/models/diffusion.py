@@ -104,6 +104,8 @@ class DiffusionEngine(nn.Module):
         missing = [k for k in missing if not k.startswith("vae_") and "._orig_mod." not in k]
         if self.store is not None:
             self.store.refresh()
+        for st in getattr(self, "embedder_stores", ()):
+            st.refresh()
         return missing, unexpected
 
     def _init_first_stage(self, model: AutoencoderKL) -> None:
@@ -121,9 +123,35 @@ class DiffusionEngine(nn.Module):
             dec.standalone = True
             self.vae_decoder = dec
 
+    def trainable_embedders(self) -> list:
+        """The conditioner's embedders with is_trainable (configs/sdxl/sdxl-te.example.yaml trains both text towers)."""
+        return [e for e in getattr(self.conditioner, "embedders", ()) if getattr(e, "is_trainable", False)]
+
+    def _check_trainable_embedders(self) -> None:
+        """What the trained-conditioner step does not (yet) take, refused by name."""
+        tr = self.trainable_embedders()
+        if not tr:
+            return
+        for e in tr:
+            if not hasattr(e, "trained_parameters"):
+                raise NotImplementedError(f"trainable embedder {type(e).__name__}: only the CLIP text towers have a training chain")
+        if self.stream_optimizer:
+            raise NotImplementedError("stream_optimizer (the update streamed block by block behind backward) does not drive the text towers' groups")
+        import torch.distributed as dist
+
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("trainable text towers at world size > 1: their gradient exchange is not built (one GPU only)")
+
     def setup_flat_params(self) -> FlatParamStore:
-        """Re-home the trainable UNet parameters into the flat fp32/bf16/grad buffers (call after .cuda())."""
+        """Re-home the trainable UNet parameters into the flat fp32/bf16/grad buffers (call after .cuda()).  Each trainable text tower gets
+        a store of its own over embedder.trained_parameters() (`self.embedder_stores`): one optimizer group each."""
+        self._check_trainable_embedders()
         self.store = FlatParamStore([p for p in self.model.diffusion_model.parameters() if p.requires_grad])
+        self.embedder_stores = []
+        for e in self.trainable_embedders():
+            st = FlatParamStore(e.trained_parameters())
+            st.state.assume_zeroed = False        # (overwritten by their producers on the first micro-batch, as the UNet's)
+            self.embedder_stores.append(st)
         # contract: every parameter gradient is OVERWRITTEN by its producer on the first micro-batch of a step
         # (store.state.grad_accumulate False) and added to on later ones, so the 10 GB buffer is never zero-filled between steps
         self.store.state.assume_zeroed = False
@@ -145,6 +173,8 @@ class DiffusionEngine(nn.Module):
 
     @stream_optimizer.setter
     def stream_optimizer(self, on: bool) -> None:
+        if on and self.trainable_embedders():
+            raise NotImplementedError("stream_optimizer (the update streamed block by block behind backward) does not drive the text towers' groups")
         if on and getattr(self, "_torch_optimizer", None) is not None:
             from ..optimizers import CAME, AdamW8bit
 
@@ -209,7 +239,8 @@ class DiffusionEngine(nn.Module):
 
     def configure_optimizers(self):
         """models/diffusion.py:261-296: one parameter group for the UNet (plus `initial_lr` from `model.base_lr`), one per
-        trainable embedder; `self.optimizer(param_groups)`, then `self.scheduler(optimizer)`; the same return value.  What
+        trainable embedder (its name, `initial_lr` = its base_lr, the parameters of its flat store: embedder.trained_parameters());
+        `self.optimizer(param_groups)`, then `self.scheduler(optimizer)`; the same return value.  What
         comes back must be one of this package's fused optimizers (`neurosis_amd.optimizers.Adafactor` -- the class the example
         configs name under the prefix swap --, `neurosis_amd.optimizers.came.CAME`, `.AdamW8bit` or `.AdamW`): the step is a few HIP
         launches over the flat buffers, and an eager torch optimizer walking 1 700 parameter views would silently replace it, so anything
@@ -225,9 +256,15 @@ class DiffusionEngine(nn.Module):
         if self.store is not None and self.stream_optimizer:
             unet_params["chunk_boundaries"] = self._block_boundaries()     # lets the fused update be streamed block by block
         param_groups = [unet_params]
-        for embedder in getattr(self.conditioner, "embedders", ()):
-            if getattr(embedder, "is_trainable", False):
-                raise NotImplementedError("trainable conditioner embedders are outside the fused training step (SURVEY.md section 8: frozen TE/VAE)")
+        self._check_trainable_embedders()
+        for embedder in self.trainable_embedders():
+            # one group per trainable embedder (models/diffusion.py:270-289): its name, initial_lr = base_lr.  The group holds what the
+            # selected outputs depend on -- the tower's flat store exactly; a parameter with no gradient (bigG's logit_scale) stays as it is,
+            # as torch skips a parameter whose .grad is None
+            group = {"name": getattr(embedder, "name", type(embedder).__name__), "params": embedder.trained_parameters()}
+            if getattr(embedder, "base_lr", None) is not None:
+                group["initial_lr"] = embedder.base_lr
+            param_groups.append(group)
         opt = self.optimizer(param_groups) if callable(self.optimizer) and not isinstance(self.optimizer, torch.optim.Optimizer) else self.optimizer
         if not isinstance(opt, (Adafactor, CAME, AdamW8bit, AdamW)):
             raise TypeError(f"DiffusionEngine: optimizer {type(opt).__module__}.{type(opt).__name__} cannot be fused; use "
@@ -284,7 +321,8 @@ class DiffusionEngine(nn.Module):
         cond = None
         from ..graphs import graphs_enabled
 
-        if os.environ.get("NK_COND_OVERLAP", "1") != "0" and inputs.is_cuda and not (graphs_enabled("te") or graphs_enabled("vae")):
+        if (os.environ.get("NK_COND_OVERLAP", "1") != "0" and inputs.is_cuda and not (graphs_enabled("te") or graphs_enabled("vae"))
+                and not self.trainable_embedders()):     # (a trained conditioner runs in line: its backward follows the main stream)
             main = torch.cuda.current_stream()
             if getattr(self, "_cond_stream", None) is None:
                 self._cond_stream = torch.cuda.Stream(device=inputs.device)
@@ -310,6 +348,8 @@ class DiffusionEngine(nn.Module):
         changing it between a forward and its backward raises).  The first micro-batch overwrites the gradients,
         later ones add; with a FlatDataParallel `dp`, only the last micro-batch exchanges them (DDP's no_sync)."""
         self.store.state.grad_accumulate = micro_batch_index > 0
+        for st in getattr(self, "embedder_stores", ()):
+            st.state.grad_accumulate = micro_batch_index > 0
         self._last_micro_batch = bool(last)
         if dp is not None:
             dp.no_sync(not last)
@@ -352,6 +392,9 @@ class DiffusionEngine(nn.Module):
         (dp.attach_optimizer) and the ranks' new bf16 shadows are gathered right behind the update, on the same stream."""
         if self.store is None:
             raise RuntimeError("call setup_flat_params() first")
+        if dp is not None and getattr(self, "embedder_stores", None):
+            raise NotImplementedError("trainable text towers with a data-parallel exchange (FlatDataParallel, rs_ag or all-reduce): the towers' "
+                                      "gradient exchange is not built")
         sharded = dp is not None and getattr(dp, "sharded", False)
         if sharded and (getattr(self, "model_ema", None) is not None or getattr(self, "adafactor", None) is None or self._streaming_step):
             raise NotImplementedError("the sharded exchange (NK_DP_MODE=rs_ag) needs the fused Adafactor and supports neither EMA (its update reads "
@@ -363,6 +406,9 @@ class DiffusionEngine(nn.Module):
             if self._optimizer_stream is None:
                 self._optimizer_stream = torch.cuda.Stream(device=self.store.master.device)
             self._optimizer_stream.wait_stream(torch.cuda.current_stream())      # gradients (and their exchange) are complete
+            for st in [self.store, *getattr(self, "embedder_stores", ())]:       # every group's weight gradients
+                if st.state.wgrad_stream is not None:
+                    self._optimizer_stream.wait_stream(st.state.wgrad_stream)
             scope = torch.cuda.stream(self._optimizer_stream)
         with scope:
             opt = self._torch_optimizer
@@ -387,6 +433,8 @@ class DiffusionEngine(nn.Module):
                 dp.after_optimizer_step()      # every rank's shard of the new shadows, gathered behind the update
         self._optimizer_in_flight = overlap
         self.store.state.grad_accumulate = False
+        for st in getattr(self, "embedder_stores", ()):
+            st.state.grad_accumulate = False
         self.global_step += 1
 
     def join_optimizer(self) -> None:

@@ -13,7 +13,12 @@ names and activation, so that either checkpoint layout loads unchanged:
     open_clip token_embedding.weight, positional_embedding, transformer.resblocks.N.{ln_1, attn.in_proj_{weight,bias},
               attn.out_proj, ln_2, mlp.c_fc, mlp.c_proj}, ln_final, text_projection, logit_scale
 
-Forward only (the encoders are frozen in the SDXL configs; training them is configs/sdxl/sdxl-te.example.yaml, not built).
+Frozen towers (the SDXL configs) run their forward under no_grad, replayed from hipGraphs.  An embedder built with is_trainable=True
+(configs/sdxl/sdxl-te.example.yaml) returns outputs that autograd connects, through nn.apply_module, to ONE closure chain per tower: the
+embedding, every layer's LayerNorms, GEMMs, causal attention (ops.attention_causal_fwd) and GELU (ops.gelu_fwd), and for bigG's pooled
+output ln_final, the end-of-text gather and text_projection -- all HIP kernels forward and backward.  Only the layers the selected
+outputs depend on run; parameters they do not depend on get no gradient (trained_parameters(): what DiffusionEngine puts in the tower's
+flat store and optimizer group).
 Tokenisation needs the CLIP vocabulary files: they are looked up locally through transformers' CLIPTokenizer when text is
 passed; token ids (LongTensor [B, 77]) are accepted directly.
 """
@@ -28,6 +33,7 @@ from torch import Tensor, nn
 
 from ... import ops
 from ...graphs import ForwardGraphs, frozen_stamp, graphs_enabled
+from ...nn import apply_module, as_tokens
 from ...modules.encoders.embedding import AbstractEmbModel
 
 logger = logging.getLogger(__name__)
@@ -56,12 +62,105 @@ def _residual_block(x: Tensor, batch: int, heads: int, ln_1, qkv, out_proj, ln_2
     return _linear(hidden, fc_out, residual=x)
 
 
+def _residual_block_train(x: Tensor, batch: int, heads: int, ln_1, qkv, out_proj, ln_2, fc_in, fc_out, quick_gelu: bool):
+    """_residual_block with its backward: (x', bwd(dx') -> dx).  `qkv(h)` returns (fused [M, 3 width] = [q | k | v], bwd(dfused) -> dh).
+    Parameter gradients go to .grad in their engine's mode (ops.linear_fwd / layernorm_fwd closures, the packed projection's own)."""
+    width = x.shape[1]
+    h1, b_ln1 = ops.layernorm_fwd(x, ln_1.weight, ln_1.bias, ln_1.eps)
+    fused, b_qkv = qkv(h1)
+    q, k, v = fused[:, :width], fused[:, width:2 * width], fused[:, 2 * width:]
+    attended, b_att = ops.attention_causal_fwd(q, k, v, batch, heads, width // heads)
+    x1, b_out = ops.linear_fwd(attended, out_proj.weight, out_proj.bias, residual=x)
+    h2, b_ln2 = ops.layernorm_fwd(x1, ln_2.weight, ln_2.bias, ln_2.eps)
+    u, b_fc1 = ops.linear_fwd(h2, fc_in.weight, fc_in.bias)
+    g, b_gelu = ops.gelu_fwd(u, quick_gelu)
+    x2, b_fc2 = ops.linear_fwd(g, fc_out.weight, fc_out.bias, residual=x1)
+
+    def bwd(dx2: Tensor) -> Tensor:
+        dx1 = b_ln2(b_fc1(b_gelu(b_fc2(dx2))), dx_add=dx2)
+        dfused = torch.empty_like(fused)
+        b_att(b_out(dx1), dq=dfused[:, :width], dk=dfused[:, width:2 * width], dv=dfused[:, 2 * width:])
+        return b_ln1(b_qkv(dfused), dx_add=dx1)
+
+    return x2, bwd
+
+
 def _embed(ids: Tensor, table: Tensor, positions: Tensor) -> Tensor:
     """token + position embeddings as bf16 tokens [B * L, width]"""
     if ids.dim() != 2 or ids.shape[1] > positions.shape[0]:
         raise ValueError(f"token ids must be [batch, <= {positions.shape[0]}], got {tuple(ids.shape)}")
     summed = table[ids] + positions[: ids.shape[1]]
     return ops.cast_bf16(summed.reshape(-1, summed.shape[-1]).float())
+
+
+def _embed_train(ids: Tensor, table: Tensor, positions: Tensor):
+    """_embed with its backward: (x, bwd(dx)), bwd writing table.grad / positions.grad (ops.embedding_bwd)"""
+    x = _embed(ids, table, positions)
+
+    def bwd(dx: Tensor) -> None:
+        ops.embedding_bwd(ids.contiguous(), dx, table, positions)
+
+    return x, bwd
+
+
+def _final_train(x: Tensor, B: int, L: int, ln, eot: Tensor, want_tokens: bool, want_pooled: bool, projection: Optional[Tensor] = None,
+                 projection_t: Optional[Tensor] = None):
+    """ln(x), then its rows b * L + eot[b] (@ projection when given): (outputs, bwd(dtokens, dpooled) -> dx).  ONE LayerNorm serves both
+    outputs, so its gamma / beta gradients have one producer.  projection_t is the bf16 [E, width] matrix the forward reads; the
+    projection's own gradient [width, E] contracts over only B rows (ops.wgrad_few_rows)."""
+    normed, b_ln = ops.layernorm_fwd(x, ln.weight, ln.bias, ln.eps)
+    outs = [normed] if want_tokens else []
+    sel = None
+    if want_pooled:
+        sel = normed[torch.arange(B, device=x.device) * L + eot].contiguous()
+        outs.append(sel if projection is None else ops.gemm_nt(sel, projection_t))
+
+    def bwd(dtokens: Optional[Tensor], dpooled: Optional[Tensor]) -> Tensor:
+        d = None
+        if dpooled is not None:
+            if projection is not None:
+                ops.wgrad_few_rows(sel, dpooled, ops.grad_flat(projection).view(projection.shape), ops.wgrad_mode(projection) == 1)
+                dpooled = ops.gemm_nn(dpooled, projection_t)
+            d = ops.gather_rows_bwd(dpooled, eot, L)
+        if dtokens is not None:
+            d = dtokens if d is None else ops.add(d, dtokens)
+        return b_ln(d)
+
+    return outs, bwd
+
+
+def _chain_train(x: Tensor, blocks, taps):
+    """Run `blocks` (callables x -> (x', bwd)) from the embedding output x; returns ({i: state i for i in taps}, last state, bwd(grads, dtop)),
+    state i being the input of block i (state len(blocks) the last output).  bwd adds each tap's gradient where its state enters, walks the
+    blocks backwards and returns the gradient of x."""
+    states, closures = {0: x} if 0 in taps else {}, []
+    for i, block in enumerate(blocks):
+        x, b = block(x)
+        closures.append(b)
+        if i + 1 in taps:
+            states[i + 1] = x
+
+    def bwd(grads: dict, dtop: Optional[Tensor]) -> Tensor:
+        d = dtop
+        for i in range(len(closures), -1, -1):
+            g = grads.get(i)
+            if g is not None:
+                d = g if d is None else ops.add(d, g)
+            if i > 0:
+                d = closures[i - 1](d)
+        return d
+
+    return states, x, bwd
+
+
+def _trainable(embedder, tower: nn.Module) -> bool:
+    """the embedder's forward runs the autograd-connected training chain"""
+    return embedder.is_trainable and torch.is_grad_enabled() and any(p.requires_grad for p in tower.parameters())
+
+
+def _out_grads(gouts, n: int):
+    """the first n incoming gradients as dense bf16 token matrices (None where autograd passed none)"""
+    return [None if g is None else as_tokens(g.contiguous()) for g in gouts[:n]]
 
 
 def _graphable(tower: nn.Module, ids: Tensor) -> bool:
@@ -95,15 +194,38 @@ class _HFAttention(nn.Module):
     def qkv(self, h: Tensor):
         """q, k, v of the normed tokens from ONE GEMM: the three projections packed [q; k; v] (bf16 weight, fp32 bias), rebuilt
         only when one of the six tensors changes -- 24 launches fewer per CLIP-L forward than three GEMMs per layer"""
+        width = self.q_proj.weight.shape[0]
+        fused = self._fused(h)
+        return fused[:, :width], fused[:, width:2 * width], fused[:, 2 * width:]
+
+    def _fused(self, h: Tensor) -> Tensor:
         parts = (self.q_proj, self.k_proj, self.v_proj)
         stamp = tuple(ops._param_stamp(t) for lin in parts for t in (lin.weight, lin.bias))
         if self._packed is None or self._packed[0] != stamp:
             weight = torch.cat([ops.w2d(lin.weight) for lin in parts], dim=0).contiguous()
             bias = torch.cat([lin.bias.detach().float() for lin in parts]).contiguous()
             self._packed = (stamp, weight, bias)
-        width = self.q_proj.weight.shape[0]
-        fused = ops.gemm_nt(h, self._packed[1], self._packed[2])
-        return fused[:, :width], fused[:, width:2 * width], fused[:, 2 * width:]
+        return ops.gemm_nt(h, self._packed[1], self._packed[2])
+
+
+    def qkv_train(self, h: Tensor):
+        """(fused [q | k | v], bwd(dfused) -> dh): the input gradient through the packed weight, the weight gradients split back to the three
+        projections (column slices of dfused)"""
+        fused = self._fused(h)
+        packed = self._packed[1]
+        parts = (self.q_proj, self.k_proj, self.v_proj)
+
+        def bwd(dfused: Tensor) -> Tensor:
+            width = parts[0].weight.shape[0]
+
+            def wgrads():
+                for i, lin in enumerate(parts):
+                    ops.gemm_tn_f32(dfused[:, i * width:(i + 1) * width], h, ops.g2d(lin.weight), ops.wgrad_mode(lin.weight), dbias=ops.grad_flat(lin.bias))
+
+            ops.on_wgrad_stream(wgrads, dfused, h, owner=parts[0].weight)
+            return ops.gemm_nn(dfused, packed)
+
+        return fused, bwd
 
 
 class _HFMLP(nn.Module):
@@ -172,6 +294,46 @@ class CLIPTextTower(nn.Module):
         eos = ids.argmax(-1) if self.eos_token_id == 2 else (ids == self.eos_token_id).int().argmax(-1)
         return {"last_hidden_state": last, "pooler_output": last[torch.arange(B, device=last.device), eos],
                 "hidden_states": None if states is None else tuple(s.float().reshape(B, L, -1) for s in states)}
+
+
+    def _eos(self, ids: Tensor) -> Tensor:
+        return ids.argmax(-1) if self.eos_token_id == 2 else (ids == self.eos_token_id).int().argmax(-1)
+
+    def train_depth(self, state: Optional[int], want_last: bool, want_pooled: bool) -> int:
+        """layers the training forward runs: all of them when the final-normed outputs are wanted, else up to hidden_states[state]"""
+        return len(self.text_model.encoder.layers) if (want_last or want_pooled) else state
+
+    def train_outputs(self, ids: Tensor, state: Optional[int], want_last: bool, want_pooled: bool) -> tuple:
+        """The training forward, autograd-connected through nn.apply_module: fp32 (hidden_states[state] [B, L, C] if state is not None,
+        last_hidden_state [B, L, C] if want_last, pooler_output [B, C] if want_pooled), with forward()'s values."""
+        tm = self.text_model
+        layers = list(tm.encoder.layers)[: self.train_depth(state, want_last, want_pooled)]
+        final = want_last or want_pooled
+
+        def run(ids):
+            B, L = ids.shape
+            emb = tm.embeddings
+            x, b_emb = _embed_train(ids, emb.token_embedding.weight, emb.position_embedding.weight)
+            blocks = [lambda h, l=l: _residual_block_train(h, B, self.heads, l.layer_norm1, l.self_attn.qkv_train, l.self_attn.out_proj, l.layer_norm2,
+                                                          l.mlp.fc1, l.mlp.fc2, self.quick_gelu) for l in layers]
+            states, top, b_chain = _chain_train(x, blocks, set() if state is None else {state})
+            outs = [] if state is None else [states[state].float().reshape(B, L, -1)]
+            b_final = None
+            if final:
+                fo, b_final = _final_train(top, B, L, tm.final_layer_norm, self._eos(ids), want_last, want_pooled)
+                outs += [fo[0].float().reshape(B, L, -1)] if want_last else []
+                outs += [fo[-1].float()] if want_pooled else []
+
+            def bwd(*gouts):
+                g = _out_grads(gouts, len(outs))
+                grads = {} if state is None else {state: g.pop(0)}
+                dtop = b_final(g[0] if want_last else None, g[-1] if want_pooled else None) if final else None
+                b_emb(b_chain(grads, dtop))
+                return None
+
+            return tuple(outs), bwd
+
+        return apply_module(run, [ids], self)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -259,6 +421,51 @@ class OpenCLIPTextTower(nn.Module):
         eot = normed[torch.arange(B, device=ids.device), ids.argmax(dim=-1)].contiguous()       # highest id = end of text
         pooled = ops.gemm_nt(eot, self._projection_t())
         return {"last": x.float().reshape(B, L, width), "penultimate": penultimate.float().reshape(B, L, width), "pooled": pooled.float()}
+
+
+    def train_depth(self, want_last: bool, want_pooled: bool) -> int:
+        """blocks the training forward runs: all of them for "last" / "pooled", all but the last for "penultimate" alone"""
+        n = len(self.transformer.resblocks)
+        return n if (want_last or want_pooled) else n - 1
+
+    def train_outputs(self, ids: Tensor, want_penultimate: bool, want_last: bool, want_pooled: bool) -> tuple:
+        """The training forward, autograd-connected through nn.apply_module: fp32 (penultimate, last [B, L, width], pooled [B, embed_dim]),
+        each only when asked for, with forward()'s values."""
+        n = len(self.transformer.resblocks)
+        depth = self.train_depth(want_last, want_pooled)
+        blocks_ = list(self.transformer.resblocks)[:depth]
+        taps = ({n - 1} if want_penultimate else set()) | ({n} if want_last else set())
+
+        def run(ids):
+            B, L = ids.shape
+            x, b_emb = _embed_train(ids, self.token_embedding.weight, self.positional_embedding)
+            width = x.shape[1]
+
+            def block_fn(h, blk):
+                a = blk.attn
+
+                def packed_qkv(hn):
+                    return ops.linear_fwd(hn, a.in_proj_weight, a.in_proj_bias)
+
+                return _residual_block_train(h, B, self.heads, blk.ln_1, packed_qkv, a.out_proj, blk.ln_2, blk.mlp.c_fc, blk.mlp.c_proj, self.quick_gelu)
+
+            states, top, b_chain = _chain_train(x, [lambda h, blk=blk: block_fn(h, blk) for blk in blocks_], taps)
+            outs = [states[i].float().reshape(B, L, width) for i in sorted(taps)]
+            b_final = None
+            if want_pooled:
+                fo, b_final = _final_train(top, B, L, self.ln_final, ids.argmax(dim=-1), False, True, self.text_projection, self._projection_t())
+                outs.append(fo[0].float())
+
+            def bwd(*gouts):
+                g = _out_grads(gouts, len(outs))
+                grads = {i: g[j] for j, i in enumerate(sorted(taps))}
+                dtop = b_final(None, g[-1]) if want_pooled else None
+                b_emb(b_chain(grads, dtop))
+                return None
+
+            return tuple(outs), bwd
+
+        return apply_module(run, [ids], self)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -350,8 +557,39 @@ class FrozenCLIPEmbedder(_TokenizingEmbedder):
             # the reference raises here for "last" and "pooled" (its match statement has no such arms) although its forward
             # handles both; they are accepted
             self.layer_idx = None
+        if self.is_trainable and extended_chunks > 1:
+            raise NotImplementedError("a trainable FrozenCLIPEmbedder does not support extended_chunks > 1 (its training chain takes [B, 77] token ids)")
         if not self.is_trainable:
             self.freeze()
+
+    def _train_spec(self):
+        """(hidden state index or None, want last_hidden_state, want pooler_output) of the training forward"""
+        state = None if self.layer in ("last", "pooled") else self.layer_idx + 1
+        return state, self.layer == "last", self.layer == "pooled" or self.return_pooled
+
+    def trained_parameters(self) -> list:
+        """The parameters the selected outputs depend on, in registration order: what one step gives a gradient (and what the optimizer
+        group holds).  Layers past the selected one and final_layer_norm under layer = "hidden" are not among them."""
+        state, want_last, want_pooled = self._train_spec()
+        tm = self.transformer.text_model
+        used = [tm.embeddings, *list(tm.encoder.layers)[: self.transformer.train_depth(state, want_last, want_pooled)]]
+        if want_last or want_pooled:
+            used.append(tm.final_layer_norm)
+        ids = {id(p) for m in used for p in m.parameters()}
+        return [p for p in self.parameters() if id(p) in ids]
+
+    def _forward_trainable(self, text):
+        if self.extended_chunks > 1:
+            raise NotImplementedError("a trainable FrozenCLIPEmbedder does not support extended_chunks > 1")
+        ids = _check_ids(self._ids_for(text), self.transformer.text_model.embeddings.token_embedding.weight.device)
+        state, want_last, want_pooled = self._train_spec()
+        outs = list(self.transformer.train_outputs(ids, state, want_last, want_pooled))
+        pooled = outs[-1] if want_pooled else None
+        if self.layer == "pooled":
+            z = pooled[:, None, :]
+        else:
+            z = outs[0]
+        return (z, pooled) if self.return_pooled else z
 
     def _select(self, out: dict) -> Tensor:
         if self.layer == "last":
@@ -360,8 +598,13 @@ class FrozenCLIPEmbedder(_TokenizingEmbedder):
             return out["pooler_output"][:, None, :]
         return out["hidden_states"][self.layer_idx + 1]
 
-    @torch.no_grad()
     def forward(self, text: Union[str, list, Tensor]):
+        if _trainable(self, self.transformer):
+            return self._forward_trainable(text)
+        return self._forward_frozen(text)
+
+    @torch.no_grad()
+    def _forward_frozen(self, text: Union[str, list, Tensor]):
         ids = self._ids_for(text)
         if ids.dim() == 2:
             out = self.transformer(ids, output_hidden_states=self.output_hidden_states)
@@ -406,8 +649,37 @@ class FrozenOpenCLIPEmbedder2(_TokenizingEmbedder):
         self.device, self.max_length = torch.device(device), max_length
         self.layer, self.return_pooled, self.legacy, self.extended_chunks = layer, always_return_pooled, legacy, extended_chunks
         self.embed_dim = self.model.text_projection.shape[-1]
+        if self.is_trainable and (legacy or extended_chunks > 1):
+            raise NotImplementedError("a trainable FrozenOpenCLIPEmbedder2 supports neither legacy=True nor extended_chunks > 1")
         if not self.is_trainable:
             self.freeze()
+
+    def _train_spec(self):
+        """(want penultimate, want last, want pooled) of the training forward"""
+        return self.layer == "penultimate", self.layer == "last", self.layer == "pooled" or self.return_pooled
+
+    def trained_parameters(self) -> list:
+        """The parameters the selected outputs depend on, in registration order (logit_scale never is; ln_final and text_projection only
+        with the pooled output; the last block not for "penultimate" alone)."""
+        _, want_last, want_pooled = self._train_spec()
+        m = self.model
+        used = [m.token_embedding, *list(m.transformer.resblocks)[: m.train_depth(want_last, want_pooled)]]
+        ids = {id(p) for mod in used for p in mod.parameters()} | {id(m.positional_embedding)}
+        if want_pooled:
+            ids |= {id(p) for p in m.ln_final.parameters()} | {id(m.text_projection)}
+        return [p for p in self.parameters() if id(p) in ids]
+
+    def _forward_trainable(self, text):
+        if self.legacy or self.extended_chunks > 1:
+            raise NotImplementedError("a trainable FrozenOpenCLIPEmbedder2 supports neither legacy=True nor extended_chunks > 1")
+        ids = _check_ids(self._ids_for(text), self.model.token_embedding.weight.device)
+        want = self._train_spec()
+        outs = dict(zip([k for k, w in zip(("penultimate", "last", "pooled"), want) if w], self.model.train_outputs(ids, *want)))
+        if self.layer == "pooled":
+            z = outs["pooled"]
+        else:
+            z = outs[self.layer]
+        return (z, outs["pooled"]) if self.return_pooled else z
 
     def encode_with_transformer(self, text: Tensor):
         out = self.model(text)
@@ -418,8 +690,13 @@ class FrozenOpenCLIPEmbedder2(_TokenizingEmbedder):
         B, L, width = chosen.shape
         return _norm(ops.cast_bf16(chosen.reshape(B * L, width)), self.model.ln_final).float().reshape(B, L, width)
 
-    @torch.no_grad()
     def forward(self, text: Union[str, list, Tensor]):
+        if _trainable(self, self.model):
+            return self._forward_trainable(text)
+        return self._forward_frozen(text)
+
+    @torch.no_grad()
+    def _forward_frozen(self, text: Union[str, list, Tensor]):
         ids = self._ids_for(text)
         if ids.dim() == 2:
             out = self.encode_with_transformer(ids)

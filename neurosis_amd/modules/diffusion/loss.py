@@ -88,12 +88,16 @@ class StandardDiffusionLoss(DiffusionLoss):
         context, y = cond.get("crossattn", None), cond.get("vector", None)
         cpad = (Cc + 7) // 8 * 8
         params = [p for p in unet.parameters() if p.requires_grad]
+        # a trained conditioner (configs/sdxl/sdxl-te.example.yaml): the UNet's backward also returns the gradients of its conditioning
+        need_dctx = context is not None and context.requires_grad and torch.is_grad_enabled()
+        need_dy = y is not None and y.requires_grad and torch.is_grad_enabled()
 
-        def run():
+        def run(context=None, y=None):
             zt = torch.empty_like(x)
             net_in = torch.empty(B * H * W, cpad, dtype=BF16, device=dev)
             call("nk_edm_prepare", x.data_ptr(), eps.data_ptr(), sig.data_ptr(), c_in.data_ptr(), zt.data_ptr(), net_in.data_ptr(), B, Cc, H * W, cpad, ops._stream())
-            out, unet_bwd = unet.fwd_graphed(Img(net_in, B, H, W), c_noise, None if context is None else as_tokens(context), None if y is None else as_tokens(y))
+            out, unet_bwd = unet.fwd_graphed(Img(net_in, B, H, W), c_noise, None if context is None else as_tokens(context), None if y is None else as_tokens(y),
+                                             need_dctx, need_dy)
             loss = torch.empty(B, dtype=torch.float32, device=dev)
             call("nk_edm_loss", out.t.data_ptr(), zt.data_ptr(), target.data_ptr(), c_out.data_ptr(), c_skip.data_ptr(), w.data_ptr(), loss.data_ptr(), None,
                  B, Cc, H * W, out.C, 1.0, ops._stream())
@@ -105,14 +109,19 @@ class StandardDiffusionLoss(DiffusionLoss):
                 scratch = torch.empty(B, dtype=torch.float32, device=dev)
                 call("nk_edm_loss", out.t.data_ptr(), zt.data_ptr(), target.data_ptr(), c_out.data_ptr(), c_skip.data_ptr(), wg.data_ptr(), scratch.data_ptr(),
                      dnet.data_ptr(), B, Cc, H * W, out.C, 1.0, ops._stream())
-                unet_bwd(dnet)
-                return ()
+                res = unet_bwd(dnet)
+                if not (need_dctx or need_dy):
+                    return ()
+                _, dctx, dy = res
+                return (None if dctx is None else dctx.view(context.shape), None if dy is None else dy.view(y.shape))
 
             return loss, bwd
 
-        if not torch.is_grad_enabled() or not params:
-            return run()[0]
-        return NkFunction.apply(run, 0, *params)
+        if not torch.is_grad_enabled() or not (params or need_dctx or need_dy):
+            return run(context, y)[0]
+        if need_dctx or need_dy:
+            return NkFunction.apply(run, 2, context, y, *params)
+        return NkFunction.apply(lambda: run(context, y), 0, *params)
 
     def _forward(self, network: nn.Module, denoiser: Denoiser, cond: dict, inputs: Tensor, batch: dict, return_dict: bool = False,
                  sigmas: Optional[Tensor] = None, noise: Optional[Tensor] = None):

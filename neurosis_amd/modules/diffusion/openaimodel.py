@@ -38,8 +38,9 @@ class TimestepBlock(nn.Module):
 class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
     """openaimodel.py:65-93: passes emb to TimestepBlocks, context to SpatialTransformers."""
 
-    def fwd(self, x: Img, emb: Tensor, context: Optional[Tensor]):
-        """bwd(dy tokens) -> (dx tokens | None, demb | None)."""
+    def fwd(self, x: Img, emb: Tensor, context: Optional[Tensor], dctx_sink: Optional[Callable[[Tensor], None]] = None):
+        """bwd(dy tokens) -> (dx tokens | None, demb | None).  dctx_sink: the gradient of `context` from each SpatialTransformer is handed
+        to it during the backward (None: not computed)."""
         bwds = []
         first = True
         for layer in self:
@@ -47,7 +48,7 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
                 x, b = layer.fwd(x, emb)
                 bwds.append(("emb", b))
             elif isinstance(layer, SpatialTransformer):
-                x, b = layer.fwd(x, context)
+                x, b = layer.fwd(x, context, need_dctx=dctx_sink is not None)
                 bwds.append(("ctx", b))
             elif isinstance(layer, (Conv2d, Upsample, Downsample)):
                 x, b = layer.fwd(x, need_dx=not (first and getattr(self, "_nk_input_block", False)))
@@ -67,7 +68,9 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
                     dy, de = b(dy)
                     demb = de if demb is None else ops.add(demb, de)
                 elif kind == "ctx":
-                    dy, _ = b(dy)
+                    dy, dc = b(dy)
+                    if dctx_sink is not None and dc is not None:
+                        dctx_sink(dc)
                 else:
                     dyi, _ = b(dy)
                     dy = None if dyi is None else dyi.t
@@ -431,46 +434,55 @@ class UNetModel(nn.Module):
             for a, kv in zip(atts, outs):
                 a._nk_kv = (kv, context)
 
-    def fwd_graphed(self, x: Img, timesteps: Tensor, context: Optional[Tensor], y: Optional[Tensor]):
+    def fwd_graphed(self, x: Img, timesteps: Tensor, context: Optional[Tensor], y: Optional[Tensor], need_dctx: bool = False, need_dy: bool = False):
         """`fwd`, replayed from a hipGraph once this input signature has been seen twice (neurosis_amd/graphs.py): the training
         step's ~2 700 launches cost the host nothing.  NK_GRAPH=0 keeps the eager chain.  A gradient-ready hook (the
         data-parallel exchange) is called between the backward's per-block graph segments, as the eager chain calls it."""
         from ...graphs import ChainGraphs, frozen_stamp, graphs_enabled
 
         if not x.t.is_cuda or not graphs_enabled():
-            return self.fwd(x, timesteps, context, y)
+            return self.fwd(x, timesteps, context, y, need_dctx, need_dy)
         if self._nk_graphs is None:
             self._nk_graphs = ChainGraphs(self.out[2].weight, hook=lambda: self.grad_ready_hook)
         N, H, W = x.N, x.H, x.W
         # (frozen_stamp: the captured kernels read the weights' bf16 shadows by address -- a flat store keeps them in place, free
         # parameters get new ones whenever they change; ~0.4 ms of host time per call for the SDXL UNet's 1 700 tensors)
-        return self._nk_graphs.run(lambda t, ts, c, yy: self.fwd(Img(t, N, H, W), ts, c, yy), [x.t, timesteps, context, y],
-                                   extra_key=(N, H, W, frozen_stamp(self), self.training))
+        return self._nk_graphs.run(lambda t, ts, c, yy: self.fwd(Img(t, N, H, W), ts, c, yy, need_dctx, need_dy), [x.t, timesteps, context, y],
+                                   extra_key=(N, H, W, frozen_stamp(self), self.training, need_dctx, need_dy))
 
-    def fwd(self, x: Img, timesteps: Tensor, context: Optional[Tensor], y: Optional[Tensor]):
+    def fwd(self, x: Img, timesteps: Tensor, context: Optional[Tensor], y: Optional[Tensor], need_dctx: bool = False, need_dy: bool = False):
         """x: Img with channels padded to a multiple of 8.  Returns (out Img (padded channels), bwd);
-        bwd(dout tokens) -> dx tokens or None."""
+        bwd(dout tokens) -> dx tokens or None; with need_dctx or need_dy (a trained conditioner) -> (dx, dcontext | None, dy | None):
+        dcontext [B*Lc, Cc] the sum over every cross-attention of its K / V projections' input gradients, dy [B, adm] through label_emb."""
         hook_raw = self.grad_ready_hook
+        need_dctx = bool(need_dctx) and context is not None
+        need_dy = bool(need_dy) and y is not None and self.num_classes is not None
         t_emb = ops.timestep_embedding(timesteps, self.model_channels)
         emb, b_time = self._mlp_fwd(self.time_embed, t_emb, need_dx=False)
         b_label = None
         if self.num_classes is not None:
-            lab, b_label = self._mlp_fwd(self.label_emb[0], y, need_dx=False)
+            lab, b_label = self._mlp_fwd(self.label_emb[0], y, need_dx=need_dy)
             emb = ops.add(emb, lab)
         if context is not None:
             self._project_context(context)
+        dctx = [None]
+
+        def sink(dc: Tensor) -> None:        # (fixed order: the backward's block order)
+            dctx[0] = dc if dctx[0] is None else ops.add(dctx[0], dc)
+
+        sink_ = sink if need_dctx else None
         hs: List[Img] = []
         tape = []
         h = x
         for module in self.input_blocks:
-            h, b = module.fwd(h, emb, context)
+            h, b = module.fwd(h, emb, context, sink_)
             hs.append(h)
             tape.append((module, b))
-        h, b_mid = self.middle_block.fwd(h, emb, context)
+        h, b_mid = self.middle_block.fwd(h, emb, context, sink_)
         out_tape = []
         for module in self.output_blocks:
             h, b_cat = ops.cat_fwd(h, hs.pop())
-            h, b = module.fwd(h, emb, context)
+            h, b = module.fwd(h, emb, context, sink_)
             out_tape.append((module, b, b_cat))
         gn = self.out[0]
         hn, b_gn = ops.groupnorm_fwd(h, gn.weight, gn.bias, 32, gn.eps, silu=True)
@@ -519,14 +531,17 @@ class UNetModel(nn.Module):
                 if hook:
                     hook(module)
             tape.clear()
+            dy = None
             if b_label is not None:
-                b_label(demb)
+                dy = b_label(demb)
                 if hook:
                     hook(self.label_emb)
             b_time(demb)
             if hook:
                 hook(self.time_embed)
             ops.join_wgrad_stream(self.out[2].weight)
+            if need_dctx or need_dy:
+                return dh, dctx[0], dy
             return dh
 
         return out, bwd
@@ -546,16 +561,19 @@ class UNetModel(nn.Module):
                 img = Img.from_nchw(x)
             else:
                 img = Img(ops.nchw_to_tokens(x, cpad), N, H, W)
-            out, bwd = self.fwd(img, timesteps, None if context is None else as_tokens(context), None if y is None else as_tokens(y))
+            need_dctx = context is not None and context.requires_grad
+            need_dy = y is not None and y.requires_grad
+            out, bwd = self.fwd(img, timesteps, None if context is None else as_tokens(context), None if y is None else as_tokens(y), need_dctx, need_dy)
             o = ops.tokens_to_nchw(out.t, N, self.out_channels, out.H, out.W, dtype=x.dtype if x.dtype in (torch.float32, BF16) else torch.float32)
 
             def bwd2(g):
                 gt = ops.nchw_to_tokens(g, out.C)
-                dx = bwd(gt)
+                res = bwd(gt)
+                dx, dctx, dy = res if (need_dctx or need_dy) else (res, None, None)
                 gx = None
                 if dx is not None and x.requires_grad:
                     gx = ops.tokens_to_nchw(dx, N, Cin, H, W, dtype=x.dtype)
-                return gx, None, None, None
+                return gx, None, None if dctx is None else dctx.view(context.shape), None if dy is None else dy.view(y.shape)
 
             return o, bwd2
 

@@ -791,10 +791,62 @@ def geglu_fwd(u: Tensor):
 
 
 def gelu(x: Tensor, quick: bool = False) -> Tensor:
-    """exact GELU, or x * sigmoid(1.702 x) with quick=True; forward only (frozen text encoders)"""
+    """exact GELU, or x * sigmoid(1.702 x) with quick=True; forward only (frozen text encoders; gelu_fwd has the backward)"""
     y = torch.empty_like(x)
     call("nk_gelu_fwd", x.data_ptr(), y.data_ptr(), x.numel(), int(quick), _stream())
     return y
+
+
+def gelu_fwd(x: Tensor, quick: bool = False):
+    """(gelu(x), bwd) for the trainable text towers; bwd(dy) -> dx = dy * gelu'(x) (nk_gelu_bwd, same mode)"""
+    if not x.is_contiguous():
+        raise ValueError("gelu_fwd: x must be dense")
+    y = gelu(x, quick)
+
+    def bwd(dy: Tensor) -> Tensor:
+        if dy.shape != x.shape or dy.dtype != BF16 or not dy.is_contiguous():
+            raise ValueError("gelu bwd: dy must be a dense bf16 tensor of x's shape")
+        dx = torch.empty_like(x)
+        call("nk_gelu_bwd", dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), int(quick), _stream())
+        return dx
+
+    return y, bwd
+
+
+def embedding_bwd(ids: Tensor, dx: Tensor, table: Tensor, positions: Tensor) -> None:
+    """Gradients of x[b * L + l] = table[ids[b, l]] + positions[l] (the text towers' embedding) written into table.grad / positions.grad
+    (fp32), in the parameters' engine mode: the first micro-batch overwrites (rows nothing hit come out zero), later ones add.  Deterministic
+    (nk_embedding_bwd: fixed-order sums, no atomics).  ids [B, L] int64; dx [B * L, C] bf16."""
+    _check2d(dx, "dx")
+    B, L = ids.shape
+    V, Cc = table.shape
+    P = positions.shape[0]
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or dx.shape != (B * L, Cc) or positions.shape[1] != Cc:
+        raise ValueError(f"embedding_bwd: ids [B, L] int64 and dx [B * L, {Cc}] expected, got {tuple(ids.shape)} {ids.dtype}, {tuple(dx.shape)}")
+    call("nk_embedding_bwd", ids.data_ptr(), dx.data_ptr(), dx.stride(0), grad_flat(table).data_ptr(), grad_flat(positions).data_ptr(), B, L, V, P,
+         Cc, wgrad_mode(table), _stream())
+
+
+def gather_rows_bwd(dsel: Tensor, idx: Tensor, L: int) -> Tensor:
+    """backward of sel[b] = x[b * L + idx[b]]: the dense [B * L, C] gradient of x, zero except the gathered rows (nk_gather_rows_bwd)"""
+    _check2d(dsel, "dsel")
+    B, Cc = dsel.shape
+    if idx.shape != (B,) or idx.dtype != torch.int64 or not idx.is_contiguous():
+        raise ValueError("gather_rows_bwd: idx must be a dense int64 [B] tensor")
+    dx = torch.empty(B * L, Cc, dtype=BF16, device=dsel.device)
+    call("nk_gather_rows_bwd", dsel.data_ptr(), dsel.stride(0), idx.data_ptr(), dx.data_ptr(), B, L, Cc, _stream())
+    return dx
+
+
+def wgrad_few_rows(x: Tensor, dy: Tensor, dw: Tensor, accumulate: bool) -> None:
+    """dw [K, N] fp32 (+)= x^T dy over the M <= 256 rows of x [M, K] and dy [M, N] (nk_wgrad_few_rows)"""
+    _check2d(x, "x")
+    _check2d(dy, "dy")
+    M, K = x.shape
+    N = dy.shape[1]
+    if dy.shape[0] != M or dw.shape != (K, N) or dw.dtype != torch.float32 or dw.stride(1) != 1:
+        raise ValueError(f"wgrad_few_rows: bad shapes {tuple(x.shape)} {tuple(dy.shape)} {tuple(dw.shape)}")
+    call("nk_wgrad_few_rows", x.data_ptr(), x.stride(0), dy.data_ptr(), dy.stride(0), dw.data_ptr(), dw.stride(0), M, K, N, int(accumulate), _stream())
 
 
 def leaky_relu_fwd(x: Tensor, slope: float = 0.2):
@@ -926,7 +978,7 @@ def cat_fwd(a: Img, b: Img):
 def attention_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head: int, causal: bool = False, need_lse: bool = True,
                   return_lse: bool = False):
     """softmax(q k^T / sqrt(d)) v.  q [B*Lq, H*D], k/v [B*Lk, H*D] token matrices (column slices allowed).
-    bwd(do) -> (dq, dk, dv) dense token matrices.  causal=True (frozen text transformers) is forward only.
+    bwd(do) -> (dq, dk, dv) dense token matrices.  causal=True has no backward here (attention_causal_fwd has one).
     dim_head = 512 (the VAE mid block): csrc/attn512.h forward (need_lse=False skips the log-sum-exp output: inference), csrc/attn512_bwd.h backward."""
     for n, t in (("q", q), ("k", k), ("v", v)):
         _check2d(t, n)
@@ -961,6 +1013,40 @@ def attention_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head:
 
     if return_lse:              # [B, heads, Lq] fp32, natural log of the row sums of exp(scale q k^T) (the chunked recompute backward rebuilds P from it)
         return o, bwd, lse
+    return o, bwd
+
+
+def attention_causal_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head: int = 64):
+    """Causal self-attention WITH a backward (the trained text towers): the forward is attention_fwd(causal=True), launch for launch;
+    bwd(do, dq=None, dk=None, dv=None) -> (dq, dk, dv) through nk_attention_bwd_causal (head dim 64, at most 96 tokens).  dq / dk / dv may be
+    given as column slices of one buffer (the packed QKV projection's gradient)."""
+    L = q.shape[0] // B
+    if dim_head != 64 or L > 96 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
+        raise NotImplementedError(f"attention_causal_fwd: the backward takes head dim 64 and at most 96 tokens (self-attention), got D = {dim_head}, L = {L}")
+    o, _, lse = attention_fwd(q, k, v, B, heads, dim_head, causal=True, return_lse=True)
+    HD = heads * dim_head
+
+    def bwd(do: Tensor, dq: Optional[Tensor] = None, dk: Optional[Tensor] = None, dv: Optional[Tensor] = None):
+        _check2d(do, "do")
+        dq = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dq is None else dq
+        dk = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dk is None else dk
+        dv = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dv is None else dv
+        for n, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+            _check2d(t, n)
+            if t.shape != (B * L, HD):
+                raise ValueError(f"attention_causal_fwd bwd: {n} must be [{B * L}, {HD}], got {tuple(t.shape)}")
+        d = NkAttnDesc()
+        d.B, d.H, d.Lq, d.Lk, d.D = B, heads, L, L, dim_head
+        d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
+        d.bq, d.bk, d.bv, d.bo = L * q.stride(0), L * k.stride(0), L * v.stride(0), L * o.stride(0)
+        d.sdq, d.sdk, d.sdv, d.sdo = dq.stride(0), dk.stride(0), dv.stride(0), do.stride(0)
+        d.bdq, d.bdk, d.bdv, d.bdo = L * dq.stride(0), L * dk.stride(0), L * dv.stride(0), L * do.stride(0)
+        d.scale = float(dim_head) ** -0.5
+        d.causal = 1
+        call("nk_attention_bwd_causal", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(),
+             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _stream())
+        return dq, dk, dv
+
     return o, bwd
 
 
