@@ -57,7 +57,7 @@ __device__ __forceinline__ void cm_tensor_denom(const NkCmArgs& a, const NkCameT
   for (int i = tid; i < t.nitems; i += 256) su += AF_FETCH(a.u2_part + t.item0 + i);
   su = block_sum_256(su, red);
   if (tid == 0) {
-    const float numel = t.kind == 0 ? (float)t.d0 : (float)t.d0 * (float)t.d1 * (float)(t.kind == 2 ? t.kh * t.kw : 1);
+    const float numel = af_tensor_numel(t.kind, t.d0, t.d1, t.kh, t.kw);
     const float rms = sqrtf(su) / sqrtf(numel);
     a.denom[ti] = fmaxf(1.0f, rms / a.clip);
   }

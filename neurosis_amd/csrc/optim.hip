@@ -169,7 +169,7 @@ __device__ __forceinline__ void af_tensor_scale(const NkAfArgs& a, const NkAfTen
   su = block_sum_256(su, red);
   sp = block_sum_256(sp, red);
   if (tid == 0) {
-    const float numel = t.kind == 0 ? (float)t.d0 : (float)t.d0 * (float)t.d1 * (float)(t.kind == 2 ? t.kh * t.kw : 1);
+    const float numel = af_tensor_numel(t.kind, t.d0, t.d1, t.kh, t.kw);
     const float rms_u = sqrtf(su / numel);
     const float denom = fmaxf(1.0f, rms_u / a.clip);
     const float rms_p = sqrtf(sp) / sqrtf(numel);

@@ -1,5 +1,5 @@
 // Device helpers shared by the fused multi-tensor optimizers (optim.hip: Adafactor, came.hip: CAME): the work item of a chunk, the tile
-// geometry, the backward-health gate, the fixed-order block reduction and the "last block done" hand-off.
+// geometry, the backward-health gate, the element count of a table entry, the fixed-order block reduction and the "last block done" hand-off.
 #pragma once
 #include "nk_common.h"
 
@@ -12,6 +12,11 @@ struct NkAfItem { int tensor, tr, tc, pad; };   // one block's work: tensor inde
 #define AF_TC 64    // matrix tile cols
 #define AF_CONV_PAIRS 1024
 #define AF_VEC 1024
+
+// number of elements of a tensor-table entry, as the float the RMS divisions use (vector: d0; matrix: d0 x d1; conv: O x I x KH x KW)
+__device__ __forceinline__ float af_tensor_numel(int kind, int d0, int d1, int kh, int kw) {
+  return kind == 0 ? (float)d0 : (float)d0 * (float)d1 * (float)(kind == 2 ? kh * kw : 1);
+}
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
   v = wave_sum(v);

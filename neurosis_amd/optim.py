@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from typing import Optional
 
 import numpy as np
@@ -48,7 +49,178 @@ def _align(n: int, a: int = 64) -> int:
     return (n + a - 1) // a * a
 
 
-class FlatAdafactor:
+def _default_chunk_bytes() -> int:
+    """Gradient bytes per chunk of tensors (NK_AF_CHUNK_MB, default 128), for FlatAdafactor (three launches per chunk) and FlatCAME alike."""
+    # A chunk's gradients are re-read (second-moment pass, update-RMS pass, apply pass) out of the 256 MB Infinity Cache instead of HBM
+    # while the chunk fits it -- 14 instead of 22 HBM bytes per parameter.  The update runs on its own stream beside the next step's VAE
+    # encoder, so what counts is the HBM bandwidth it takes from that encoder: round 3 (five launches per chunk) measured a steady-state
+    # step of 172.2 / 172.8 / 173.8 / 174.8 ms at 64 / 128 / 256 / 2048 MB; round 4 (three launches per chunk): step-time p50 164.3 /
+    # 165.2 / 165.5 ms at 64 / 128 / 256 MB (one box, back to back; DESIGN.md section 3.6) -- the cache-sized chunk still wins although it
+    # costs twice the launches.
+    # 128 MB (round 5; 64 before): alone on the chip the update takes 20.5 / 17.8 / 13.8 / 12.7 / 12.2 / 11.7 ms at 32 / 64 / 128 / 256 /
+    # 512 / 1024 MB chunks (tools/bench_optimizer.py) -- three dependent launches per chunk, each with its ramp and tail -- while the
+    # second and third read of a chunk's gradients only stay in the 256 MB Infinity Cache for small chunks; in the step 128 MB measured
+    # -0.5 ms against 64, 256 the same as 64, 512 +0.6 ms (profiles/r05_ab_notes.txt)
+    return int(os.environ.get("NK_AF_CHUNK_MB", "128")) << 20
+
+
+# The state vectors a tensor of each kind (0 vector, 1 matrix, 2 conv) owns, in the order they lie in `state`: (table field, length) with
+# length one of "numel", "d0", "d1", "row" (conv: O*KH*I) and "col" (conv: O*KW*I).  _plan_tables() lays them out; the kernels find them
+# through the C structs that AF_TENSOR_DTYPE / CAME_TENSOR_DTYPE mirror.
+_AF_STATE = {0: (("row_off", "numel"),), 1: (("row_off", "d0"), ("col_off", "d1")), 2: (("row_off", "row"), ("col_off", "col"))}
+_CAME_STATE = {0: (("m_off", "numel"), ("r_off", "numel")),
+              1: (("m_off", "numel"), ("r_off", "d0"), ("c_off", "d1"), ("rr_off", "d0"), ("cr_off", "d1")),
+              2: (("m_off", "numel"), ("r_off", "row"), ("c_off", "col"), ("rr_off", "row"), ("cr_off", "col"))}
+
+
+def _plan_tables(who: str, shapes, offsets, chunk_bytes: int, boundaries, dtype: np.dtype, state_fields: dict, mr_per_strip: int) -> dict:
+    """The tensor table, work items and chunks of a factored optimizer over parameters of `shapes` at element `offsets` of the flat
+    buffers; pure (no store, no library, no device).  A matrix is tiled AF_TR x AF_TC (one item per tile, partial row / column sums in
+    the chunk's workspace, `mr_per_strip` mean_row slots per 256-row strip, one counter per strip and per tile column), a conv weight
+    takes one item per AF_CONV_PAIRS (o, i) pairs, anything else one per AF_VEC elements; every tensor has one more counter.  A chunk is
+    closed before the tensor that would take its gradients past `chunk_bytes`, and before every tensor index in `boundaries`.
+    Returns tensors (`dtype`), items (AF_ITEM_DTYPE), chunks [(tensor_lo, tensor_hi, item_lo, item_hi)] and the sizes state / ws /
+    mean_row / counters."""
+    bounds = set(int(b) for b in (boundaries or ()))
+    tens = np.zeros(len(shapes), dtype=dtype)
+    items, chunks = [], []
+    state_off = ws_max = mr_slots = n_counters = 0
+    c_t0 = c_i0 = c_bytes = c_ws = 0
+    for ti, (shape, off) in enumerate(zip(shapes, offsets)):
+        t = tens[ti]
+        t["off"] = off
+        t["cnt0"] = n_counters
+        if len(shape) >= 2 and len(shape) not in (2, 4):
+            raise NotImplementedError(f"{who}: {len(shape)}-d parameters are not supported")
+        numel = math.prod(shape)
+        if c_bytes and (c_bytes + numel * 4 > chunk_bytes or ti in bounds):   # close the current chunk before this tensor
+            chunks.append((c_t0, ti, c_i0, len(items)))
+            ws_max = max(ws_max, c_ws)
+            c_t0, c_i0, c_bytes, c_ws = ti, len(items), 0, 0
+        t["item0"] = len(items)
+        if len(shape) == 2:
+            kind, (d0, d1), kh, kw = 1, shape, 1, 1
+            if d1 % 4:
+                raise NotImplementedError(f"{who}: matrix rows must be a multiple of 4 elements")
+            ntr, ntc = -(-d0 // AF_TR), -(-d1 // AF_TC)
+            t["ws_row"], t["ws_col"] = c_ws, c_ws + ntc * d0
+            c_ws += _align(ntc * d0 + ntr * d1)
+            items += [(ti, r, c, 0) for r in range(ntr) for c in range(ntc)]
+            t["mr0"] = mr_slots
+            mr_slots += mr_per_strip * ntr
+            n_counters += ntr + ntc
+        elif len(shape) == 4:
+            kind, (d0, d1, kh, kw) = 2, shape
+            if kh > 3 or kw > 3:
+                raise NotImplementedError(f"{who}: conv kernels larger than 3x3 are not supported")
+            items += [(ti, r, 0, 0) for r in range(-(-(d0 * d1) // AF_CONV_PAIRS))]
+        else:
+            kind, d0, d1, kh, kw = 0, numel, 1, 1, 1
+            items += [(ti, r, 0, 0) for r in range(-(-numel // AF_VEC))]
+        t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = kind, d0, d1, kh, kw
+        length = {"numel": numel, "d0": d0, "d1": d1, "row": d0 * kh * d1, "col": d0 * kw * d1}
+        for field, n in state_fields[kind]:
+            t[field] = state_off
+            state_off += _align(length[n])
+        t["nitems"] = len(items) - int(t["item0"])
+        n_counters += 1
+        c_bytes += numel * 4
+    chunks.append((c_t0, len(shapes), c_i0, len(items)))
+    ws_max = max(ws_max, c_ws)
+    return {"tensors": tens, "items": np.array(items, dtype=np.int32).view(AF_ITEM_DTYPE).reshape(-1), "chunks": chunks,
+            "state": state_off, "ws": ws_max, "mean_row": mr_slots, "counters": n_counters}
+
+
+class _FlatOptimizer:
+    """Checkpoints of the fused optimizers, in `torch.optim.Optimizer.state_dict()` layout: {"state": {i: {...}}, "param_groups": [one]},
+    parameter i being `store.params[i]` (registration order, as torch numbers them).  A class supplies `param_state(i)` (views of its
+    buffers under its upstream class's keys and logical shapes), `_group_dict()`, `reset_state()`, and overrides the hooks below where it
+    differs."""
+
+    _matched = ()   # keys of param_state() that a checkpoint has to equal instead of setting them
+
+    def _saved_state(self, i: int) -> dict:
+        """parameter i's checkpoint entry: param_state(i) with the tensors copied"""
+        return {k: (v.detach().clone().contiguous() if torch.is_tensor(v) else v) for k, v in self.param_state(i).items()}
+
+    def state_dict(self) -> dict:
+        state = {i: self._saved_state(i) for i in range(self.ntensors)} if self.step_count > 0 else {}
+        return {"state": state, "param_groups": [{**self._group_dict(), "params": list(range(self.ntensors))}]}
+
+    def _accepts_partial_state(self) -> bool:
+        return False
+
+    def _check_entry(self, i: int, st: dict, mine: dict) -> None:
+        """refuse a checkpoint entry `st` that does not fit parameter i's own state `mine` (shapes are checked by the caller)"""
+        if set(mine) != set(k for k in st if k != "step"):
+            raise ValueError(f"{type(self).__name__}.load_state_dict: parameter {i} has state {sorted(st)}, expected {sorted(mine)}")
+
+    def _saved_step(self, sd: dict, state: dict) -> Optional[int]:
+        """the step count a checkpoint carries: one per parameter, all equal"""
+        steps = set(int(st["step"]) for st in state.values())
+        if len(steps) != 1:
+            raise ValueError(f"{type(self).__name__}.load_state_dict: per-parameter step counts differ ({sorted(steps)}); the fused update keeps one")
+        return steps.pop()
+
+    def _copy_state(self, state: dict) -> None:
+        with torch.no_grad():
+            for i, st in state.items():
+                for k, v in self.param_state(i).items():
+                    if torch.is_tensor(v) and k not in self._matched:
+                        v.copy_(st[k].to(v.device, v.dtype))
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Every entry is checked before anything is copied.  A checkpoint without state resets the optimizer."""
+        who = f"{type(self).__name__}.load_state_dict"
+        state = {int(i): st for i, st in sd.get("state", {}).items()}
+        if not state:
+            self.reset_state()
+            return
+        if len(state) != self.ntensors and not self._accepts_partial_state():
+            raise ValueError(f"{who}: state for {len(state)} of {self.ntensors} parameters")
+        for i, st in state.items():
+            if not 0 <= i < self.ntensors:
+                raise ValueError(f"{who}: parameter index {i} out of range (0..{self.ntensors - 1})")
+            mine = {k: v for k, v in self.param_state(i).items() if torch.is_tensor(v)}
+            self._check_entry(i, st, mine)
+            for k, v in mine.items():
+                if tuple(v.shape) != tuple(st[k].shape):
+                    raise ValueError(f"{who}: {k} of parameter {i} has shape {tuple(st[k].shape)}, expected {tuple(v.shape)}")
+        step = self._saved_step(sd, state)
+        self._copy_state(state)
+        if step is not None:
+            self.step_count = step
+
+
+class _FlatFactored(_FlatOptimizer):
+    """What FlatAdafactor and FlatCAME share: the tables of _plan_tables() on the device and one flat fp32 `state`."""
+
+    def _plan(self, store, dtype: np.dtype, state_fields: dict, mr_per_strip: int, chunk_bytes: Optional[int], boundaries=None) -> int:
+        """Lay out and upload the tables, allocate what both optimizers keep per tensor / item; returns the workspace size (floats)."""
+        plan = _plan_tables(type(self).__name__, [tuple(p.shape) for p in store.params], store.offsets,
+                           _default_chunk_bytes() if chunk_bytes is None else chunk_bytes, boundaries, dtype, state_fields, mr_per_strip)
+        dev = store.master.device
+        self.store = store
+        self.step_count = 0
+        self.chunks = plan["chunks"]   # (tensor_lo, tensor_hi, item_lo, item_hi)
+        self._tens_np = plan["tensors"]
+        self.tensors = torch.from_numpy(plan["tensors"].view(np.uint8).copy()).to(dev)
+        self.items = torch.from_numpy(plan["items"].view(np.uint8).copy()).to(dev)
+        # "blocks done" counters of the last-block-done finalisations (optim_common.h): zeroed before every step although every pass
+        # leaves them at zero -- a step abandoned half way by the health gate must not poison the next one
+        self.counters = torch.zeros(plan["counters"], dtype=torch.int32, device=dev)
+        self.nitems, self.ntensors = len(plan["items"]), len(store.params)
+        self.state = torch.zeros(max(plan["state"], 1), dtype=torch.float32, device=dev)
+        self.u2_part = torch.zeros(self.nitems, dtype=torch.float32, device=dev)
+        self.mean_row = torch.zeros(max(plan["mean_row"], 1), dtype=torch.float32, device=dev)
+        return max(plan["ws"], 1)
+
+    def reset_state(self) -> None:
+        self.step_count = 0
+        self.state.zero_()
+
+
+class FlatAdafactor(_FlatFactored):
     """Adafactor on a FlatParamStore.  Constructor arguments as the reference's (adafactor.py:104-131)."""
 
     def __init__(self, store, lr: Optional[float] = None, eps: tuple[float, float] = (1e-30, 1e-3), clip_threshold: float = 1.0,
@@ -62,104 +234,19 @@ class FlatAdafactor:
             raise NotImplementedError("FlatAdafactor: beta1 (first moment) is not implemented; the reference configs use beta1=None")
         if query("nk_adafactor_tensor_bytes") != AF_TENSOR_DTYPE.itemsize:
             raise RuntimeError("FlatAdafactor: tensor table layout differs from the HIP library's")
-        if chunk_bytes is None:
-            # gradient bytes per chunk of tensors (three launches each).  A chunk's gradients are re-read (second-moment pass, update-RMS
-            # pass, apply pass) out of the 256 MB Infinity Cache instead of HBM while the chunk fits it -- 14 instead of 22 HBM bytes per
-            # parameter.  The update runs on its own stream beside the next step's VAE encoder, so what counts is the HBM bandwidth it takes
-            # from that encoder: round 3 (five launches per chunk) measured a steady-state step of 172.2 / 172.8 / 173.8 / 174.8 ms at
-            # 64 / 128 / 256 / 2048 MB; round 4 (three launches per chunk): step-time p50 164.3 / 165.2 / 165.5 ms at 64 / 128 / 256 MB
-            # (one box, back to back) -- the cache-sized chunk still wins although it costs twice the launches.
-            import os
-
-            # 128 MB (round 5; 64 before): alone on the chip the update takes 20.5 / 17.8 / 13.8 / 12.7 / 12.2 / 11.7 ms at 32 / 64 / 128 / 256 /
-            # 512 / 1024 MB chunks (tools/bench_optimizer.py) -- three dependent launches per chunk, each with its ramp and tail -- while the
-            # second and third read of a chunk's gradients only stay in the 256 MB Infinity Cache for small chunks; in the step 128 MB measured
-            # -0.5 ms against 64, 256 the same as 64, 512 +0.6 ms (profiles/r05_ab_notes.txt)
-            chunk_bytes = int(os.environ.get("NK_AF_CHUNK_MB", "128")) << 20
-        # `boundaries`: tensor indices at which a new chunk must begin (the first parameter of every top-level UNet block), so
-        # that a block's update can be issued as soon as that block's gradients are final, while backward is still running
-        bounds = set(int(b) for b in (boundaries or ()))
-        self.store = store
         self.lr, self.eps, self.clip_threshold, self.decay_rate = lr, eps, clip_threshold, decay_rate
         self.weight_decay, self.scale_parameter, self.relative_step, self.warmup_init = weight_decay, scale_parameter, relative_step, warmup_init
-        self.step_count = 0
+        # `boundaries`: tensor indices at which a new chunk must begin (the first parameter of every top-level UNet block), so
+        # that a block's update can be issued as soon as that block's gradients are final, while backward is still running
+        self._ws_stride = self._plan(store, AF_TENSOR_DTYPE, _AF_STATE, 1, chunk_bytes, boundaries)
         dev = store.master.device
-
-        tens = np.zeros(len(store.params), dtype=AF_TENSOR_DTYPE)
-        items = []
-        self.chunks = []   # (tensor_lo, tensor_hi, item_lo, item_hi)
-        state_off = 0
-        ws_max = 0
-        mr_slots = 0
-        n_counters = 0
-        c_t0, c_i0, c_bytes, c_ws = 0, 0, 0, 0
-        for ti, (p, off) in enumerate(zip(store.params, store.offsets)):
-            t = tens[ti]
-            t["off"] = off
-            t["cnt0"] = n_counters
-            if p.dim() >= 2 and p.dim() not in (2, 4):
-                raise NotImplementedError(f"FlatAdafactor: {p.dim()}-d parameters are not supported")
-            nbytes = p.numel() * 4
-            if c_bytes and (c_bytes + nbytes > chunk_bytes or ti in bounds):   # close the current chunk before this tensor
-                self.chunks.append((c_t0, ti, c_i0, len(items)))
-                ws_max = max(ws_max, c_ws)
-                c_t0, c_i0, c_bytes, c_ws = ti, len(items), 0, 0
-            t["item0"] = len(items)
-            if p.dim() == 2:
-                d0, d1 = p.shape
-                if d1 % 4:
-                    raise NotImplementedError("FlatAdafactor: matrix rows must be a multiple of 4 elements")
-                ntr, ntc = -(-d0 // AF_TR), -(-d1 // AF_TC)
-                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 1, d0, d1, 1, 1
-                t["row_off"], t["col_off"] = state_off, state_off + _align(d0)
-                state_off += _align(d0) + _align(d1)
-                t["ws_row"], t["ws_col"] = c_ws, c_ws + ntc * d0
-                c_ws += _align(ntc * d0 + ntr * d1)
-                items += [(ti, r, c, 0) for r in range(ntr) for c in range(ntc)]
-                t["mr0"] = mr_slots
-                mr_slots += ntr
-                n_counters += ntr + ntc
-            elif p.dim() == 4:
-                O, I, KH, KW = p.shape
-                if KH > 3 or KW > 3:
-                    raise NotImplementedError("FlatAdafactor: conv kernels larger than 3x3 are not supported")
-                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 2, O, I, KH, KW
-                t["row_off"], t["col_off"] = state_off, state_off + _align(O * KH * I)
-                state_off += _align(O * KH * I) + _align(O * KW * I)
-                items += [(ti, r, 0, 0) for r in range(-(-(O * I) // AF_CONV_PAIRS))]
-            else:
-                n = p.numel()
-                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 0, n, 1, 1, 1
-                t["row_off"] = state_off
-                state_off += _align(n)
-                items += [(ti, r, 0, 0) for r in range(-(-n // AF_VEC))]
-            t["nitems"] = len(items) - int(t["item0"])
-            n_counters += 1
-            c_bytes += nbytes
-        self.chunks.append((c_t0, len(store.params), c_i0, len(items)))
-        ws_max = max(ws_max, c_ws)
-
-        items_np = np.array(items, dtype=np.int32).view(AF_ITEM_DTYPE).reshape(-1)
-        self._tens_np = tens
-        self.tensors = torch.from_numpy(tens.view(np.uint8).copy()).to(dev)
-        self.items = torch.from_numpy(items_np.view(np.uint8).copy()).to(dev)
-        # "blocks done" counters of the last-block-done finalisations (optim.hip): zeroed before every step (begin_step) although every pass
-        # leaves them at zero -- a step abandoned half way by the health gate must not poison the next one
-        self.counters = torch.zeros(n_counters, dtype=torch.int32, device=dev)
-        self.nitems, self.ntensors = len(items), len(store.params)
-        self.state = torch.zeros(max(state_off, 1), dtype=torch.float32, device=dev)
         # NK_AF_STREAMS (default 1; 2 = A/B): consecutive chunks alternate between two streams forked from the caller's, so that one chunk's
         # tail (counter round trips, finishing blocks) runs beside the next chunk's loads.  Chunks share nothing but the
         # partial-sum workspace, which then exists once per stream.
-        import os as _os
-
-        self.nstreams = 2 if _os.environ.get("NK_AF_STREAMS", "1") == "2" else 1
+        self.nstreams = 2 if os.environ.get("NK_AF_STREAMS", "1") == "2" else 1
         self._side = None
-        self.ws = torch.empty(max(ws_max, 1) * self.nstreams, dtype=torch.float32, device=dev)
-        self._ws_stride = max(ws_max, 1)
-        self.u2_part = torch.zeros(self.nitems, dtype=torch.float32, device=dev)
+        self.ws = torch.empty(self._ws_stride * self.nstreams, dtype=torch.float32, device=dev)
         self.p2_part = torch.zeros(self.nitems, dtype=torch.float32, device=dev)
-        self.mean_row = torch.zeros(max(mr_slots, 1), dtype=torch.float32, device=dev)
         self.scale = torch.zeros(self.ntensors, dtype=torch.float32, device=dev)
         self.lr_t = torch.zeros(self.ntensors, dtype=torch.float32, device=dev)
         self._p2_valid = False
@@ -298,43 +385,27 @@ class FlatAdafactor:
         p = self.store.params[index]
         return (ops._phys_flat(p).float().norm(2) / (p.numel() ** 0.5)).reshape(())
 
-    def state_dict(self) -> dict:
-        """{"state": {i: {...}}, "param_groups": [...]}: parameter i is `store.params[i]` (registration order, as
-        torch numbers them).  Tensors are copies in the reference's logical shapes."""
-        state = {}
-        if self.step_count > 0:
-            for i in range(self.ntensors):
-                st = {k: (v.detach().clone().contiguous() if torch.is_tensor(v) else v) for k, v in self.param_state(i).items()}
-                st["RMS"] = self._rms(i) if self.scale_parameter else 0
-                state[i] = st
-        group = dict(lr=self.lr, eps=self.eps, clip_threshold=self.clip_threshold, decay_rate=self.decay_rate, beta1=None,
-                     weight_decay=self.weight_decay, scale_parameter=self.scale_parameter, relative_step=self.relative_step,
-                     warmup_init=self.warmup_init, params=list(range(self.ntensors)))
-        return {"state": state, "param_groups": [group]}
+    def _saved_state(self, i: int) -> dict:
+        """Tensors are copies in the reference's logical shapes."""
+        st = super()._saved_state(i)
+        st["RMS"] = self._rms(i) if self.scale_parameter else 0
+        return st
 
-    def load_state_dict(self, sd: dict) -> None:
-        state = sd.get("state", {})
-        if not state:
-            self.step_count = 0
-            self.state.zero_()
-            return
-        steps = set()
-        for i, st in state.items():
-            i = int(i)
-            if not 0 <= i < self.ntensors:
-                raise ValueError(f"FlatAdafactor.load_state_dict: parameter index {i} out of range (0..{self.ntensors - 1})")
-            mine = self.param_state(i)
-            for k in ("exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_sq"):
-                if (k in mine) != (k in st):
-                    raise ValueError(f"FlatAdafactor.load_state_dict: parameter {i} is {'not ' if k not in mine else ''}factored here but the checkpoint disagrees ({k})")
-                if k in mine:
-                    if tuple(mine[k].shape) != tuple(st[k].shape):
-                        raise ValueError(f"FlatAdafactor.load_state_dict: {k} of parameter {i} has shape {tuple(st[k].shape)}, expected {tuple(mine[k].shape)}")
-                    mine[k].copy_(st[k].to(mine[k].device, torch.float32))
-            steps.add(int(st["step"]))
-        if len(steps) != 1:
-            raise ValueError(f"FlatAdafactor.load_state_dict: per-parameter step counts differ ({sorted(steps)}); the fused update keeps one")
-        self.step_count = steps.pop()
+    def _group_dict(self) -> dict:
+        return dict(lr=self.lr, eps=self.eps, clip_threshold=self.clip_threshold, decay_rate=self.decay_rate, beta1=None,
+                    weight_decay=self.weight_decay, scale_parameter=self.scale_parameter, relative_step=self.relative_step,
+                    warmup_init=self.warmup_init)
+
+    def _accepts_partial_state(self) -> bool:
+        return True
+
+    def _check_entry(self, i: int, st: dict, mine: dict) -> None:
+        for k in ("exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_sq"):
+            if (k in mine) != (k in st):
+                raise ValueError(f"FlatAdafactor.load_state_dict: parameter {i} is {'not ' if k not in mine else ''}factored here but the checkpoint disagrees ({k})")
+
+    def _copy_state(self, state: dict) -> None:
+        super()._copy_state(state)
         self._p2_valid = False       # RMS(p) is recomputed from the (separately restored) parameters
 
 
@@ -368,7 +439,7 @@ class _CameArgs(C.Structure):
                 ("clip_threshold", C.c_float), ("lr", C.c_float), ("decay", C.c_float), ("grad_scale", C.c_float), ("has_matrix", C.c_int)]
 
 
-class FlatCAME:
+class FlatCAME(_FlatFactored):
     """CAME on a FlatParamStore: the reference's `neurosis.optimizers.came.CAME` (optimizers/came.py:115-224) as up to four
     multi-tensor HIP launches per chunk of tensors (`csrc/came.hip`).  Same rule per tensor: factored (over the last two dims)
     second moment of g^2+eps1, update clipped by its RMS, first moment m, and for tensors with >= 2 dims a factored statistic of
@@ -386,86 +457,15 @@ class FlatCAME:
         _came_validate(lr, betas, weight_decay, weight_decouple, eps1, eps2, "FlatCAME")
         if query("nk_came_tensor_bytes") != CAME_TENSOR_DTYPE.itemsize:
             raise RuntimeError("FlatCAME: tensor table layout differs from the HIP library's")
-        if chunk_bytes is None:
-            import os
-
-            # the same gradient bytes per chunk as FlatAdafactor's default (its measurements: DESIGN.md section 3.6)
-            chunk_bytes = int(os.environ.get("NK_AF_CHUNK_MB", "128")) << 20
-        self.store = store
         self.lr, self.betas, self.weight_decay = float(lr), tuple(float(b) for b in betas), float(weight_decay)
         self.weight_decouple, self.fixed_decay = bool(weight_decouple), bool(fixed_decay)
         self.clip_threshold, self.eps1, self.eps2 = float(clip_threshold), float(eps1), float(eps2)
-        self.step_count = 0
+        # mean_row: partial sums of R, then of Rr, per 256-row strip.  No `boundaries`: this update is not streamed behind backward
+        ws = self._plan(store, CAME_TENSOR_DTYPE, _CAME_STATE, 2, chunk_bytes)
         dev = store.master.device
-
-        tens = np.zeros(len(store.params), dtype=CAME_TENSOR_DTYPE)
-        items = []
-        self.chunks = []   # (tensor_lo, tensor_hi, item_lo, item_hi)
-        state_off, ws_max, mr_slots, n_counters = 0, 0, 0, 0
-        c_t0, c_i0, c_bytes, c_ws = 0, 0, 0, 0
-        for ti, (p, off) in enumerate(zip(store.params, store.offsets)):
-            t = tens[ti]
-            t["off"] = off
-            t["cnt0"] = n_counters
-            if p.dim() >= 2 and p.dim() not in (2, 4):
-                raise NotImplementedError(f"FlatCAME: {p.dim()}-d parameters are not supported")
-            nbytes = p.numel() * 4
-            if c_bytes and c_bytes + nbytes > chunk_bytes:      # close the current chunk before this tensor
-                self.chunks.append((c_t0, ti, c_i0, len(items)))
-                ws_max = max(ws_max, c_ws)
-                c_t0, c_i0, c_bytes, c_ws = ti, len(items), 0, 0
-            t["item0"] = len(items)
-            t["m_off"] = state_off
-            state_off += _align(p.numel())
-            if p.dim() == 2:
-                d0, d1 = p.shape
-                if d1 % 4:
-                    raise NotImplementedError("FlatCAME: matrix rows must be a multiple of 4 elements")
-                ntr, ntc = -(-d0 // AF_TR), -(-d1 // AF_TC)
-                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 1, d0, d1, 1, 1
-                for k, n in (("r_off", d0), ("c_off", d1), ("rr_off", d0), ("cr_off", d1)):
-                    t[k] = state_off
-                    state_off += _align(n)
-                t["ws_row"], t["ws_col"] = c_ws, c_ws + ntc * d0
-                c_ws += _align(ntc * d0 + ntr * d1)
-                items += [(ti, r, c, 0) for r in range(ntr) for c in range(ntc)]
-                t["mr0"] = mr_slots
-                mr_slots += 2 * ntr
-                n_counters += ntr + ntc
-            elif p.dim() == 4:
-                O, I, KH, KW = p.shape
-                if KH > 3 or KW > 3:
-                    raise NotImplementedError("FlatCAME: conv kernels larger than 3x3 are not supported")
-                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 2, O, I, KH, KW
-                for k, n in (("r_off", O * KH * I), ("c_off", O * KW * I), ("rr_off", O * KH * I), ("cr_off", O * KW * I)):
-                    t[k] = state_off
-                    state_off += _align(n)
-                items += [(ti, r, 0, 0) for r in range(-(-(O * I) // AF_CONV_PAIRS))]
-            else:
-                n = p.numel()
-                t["kind"], t["d0"], t["d1"], t["kh"], t["kw"] = 0, n, 1, 1, 1
-                t["r_off"] = state_off
-                state_off += _align(n)
-                items += [(ti, r, 0, 0) for r in range(-(-n // AF_VEC))]
-            t["nitems"] = len(items) - int(t["item0"])
-            n_counters += 1
-            c_bytes += nbytes
-        self.chunks.append((c_t0, len(store.params), c_i0, len(items)))
-        ws_max = max(ws_max, c_ws)
-
-        items_np = np.array(items, dtype=np.int32).view(AF_ITEM_DTYPE).reshape(-1)
-        self._tens_np = tens
-        self.tensors = torch.from_numpy(tens.view(np.uint8).copy()).to(dev)
-        self.items = torch.from_numpy(items_np.view(np.uint8).copy()).to(dev)
-        # zeroed before every step although every pass leaves them at zero: a step abandoned by the health gate must not poison the next one
-        self.counters = torch.zeros(n_counters, dtype=torch.int32, device=dev)
-        self.nitems, self.ntensors = len(items), len(store.params)
-        self.state = torch.zeros(max(state_off, 1), dtype=torch.float32, device=dev)
-        self.ws = torch.empty(max(ws_max, 1), dtype=torch.float32, device=dev)
-        self.u2_part = torch.zeros(self.nitems, dtype=torch.float32, device=dev)
-        self.mean_row = torch.zeros(max(mr_slots, 1), dtype=torch.float32, device=dev)
+        self.ws = torch.empty(ws, dtype=torch.float32, device=dev)
         self.denom = torch.zeros(self.ntensors, dtype=torch.float32, device=dev)
-        self._has_matrix = [int((tens["kind"][t0:t1] == 1).any()) for (t0, t1, _, _) in self.chunks]
+        self._has_matrix = [int((self._tens_np["kind"][t0:t1] == 1).any()) for (t0, t1, _, _) in self.chunks]
 
     def decay_factor(self, lr: float) -> float:
         """The decoupled weight decay's multiplier of p (pytorch_optimizer BaseOptimizer.apply_weight_decay)."""
@@ -510,39 +510,16 @@ class FlatCAME:
         return st
 
     # -- checkpointing (torch.optim.Optimizer.state_dict layout, the reference's keys; `step` is the group's) -------------
-    def state_dict(self) -> dict:
-        state = {}
-        if self.step_count > 0:
-            for i in range(self.ntensors):
-                state[i] = {k: v.detach().clone().contiguous() for k, v in self.param_state(i).items()}
-        group = dict(lr=self.lr, betas=self.betas, weight_decay=self.weight_decay, weight_decouple=self.weight_decouple,
-                     fixed_decay=self.fixed_decay, ams_bound=False, eps1=self.eps1, eps2=self.eps2, step=self.step_count,
-                     params=list(range(self.ntensors)))
-        return {"state": state, "param_groups": [group]}
+    def _group_dict(self) -> dict:
+        return dict(lr=self.lr, betas=self.betas, weight_decay=self.weight_decay, weight_decouple=self.weight_decouple,
+                    fixed_decay=self.fixed_decay, ams_bound=False, eps1=self.eps1, eps2=self.eps2, step=self.step_count)
 
-    def load_state_dict(self, sd: dict) -> None:
-        state = sd.get("state", {})
+    def _accepts_partial_state(self) -> bool:
+        return self.step_count > 0
+
+    def _saved_step(self, sd: dict, state: dict) -> Optional[int]:
         groups = sd.get("param_groups", [])
-        if not state:
-            self.step_count = 0
-            self.state.zero_()
-            return
-        if self.step_count == 0 and len(state) != self.ntensors:
-            raise ValueError(f"FlatCAME.load_state_dict: state for {len(state)} of {self.ntensors} parameters")
-        for i, st in state.items():
-            i = int(i)
-            if not 0 <= i < self.ntensors:
-                raise ValueError(f"FlatCAME.load_state_dict: parameter index {i} out of range (0..{self.ntensors - 1})")
-            mine = self.param_state(i)
-            if set(mine) != set(k for k in st if k != "step"):
-                raise ValueError(f"FlatCAME.load_state_dict: parameter {i} has state {sorted(st)}, expected {sorted(mine)}")
-            with torch.no_grad():
-                for k, v in mine.items():
-                    if tuple(v.shape) != tuple(st[k].shape):
-                        raise ValueError(f"FlatCAME.load_state_dict: {k} of parameter {i} has shape {tuple(st[k].shape)}, expected {tuple(v.shape)}")
-                    v.copy_(st[k].to(v.device, torch.float32))
-        if groups and "step" in groups[0]:
-            self.step_count = int(groups[0]["step"])
+        return int(groups[0]["step"]) if groups and "step" in groups[0] else None
 
 
 def _came_validate(lr, betas, weight_decay, weight_decouple, eps1, eps2, who: str) -> None:
@@ -592,7 +569,7 @@ class _A8Args(C.Structure):
                 ("lr", C.c_float), ("decay", C.c_float), ("bc1", C.c_float), ("bc2", C.c_float), ("grad_scale", C.c_float)]
 
 
-class FlatAdamW8bit:
+class FlatAdamW8bit(_FlatOptimizer):
     """8-bit blockwise AdamW on a FlatParamStore (`csrc/adamw8bit.hip`, one launch per step): bitsandbytes' `AdamW8bit` algorithm,
     restated here as the definition (bit-for-bit interchange with bitsandbytes itself is not claimed).
 
@@ -701,54 +678,33 @@ class FlatAdamW8bit:
                 "absmax1": self.absmax1[b0:b1], "absmax2": self.absmax2[b0:b1], "qmap1": self.qmap1, "qmap2": self.qmap2}
 
     # -- checkpointing (torch.optim.Optimizer.state_dict layout, bitsandbytes' keys) ---------------------------------------------------------
-    def state_dict(self) -> dict:
-        state = {}
-        if self.step_count > 0:
-            for i in range(self.ntensors):
-                state[i] = {k: v.detach().clone().contiguous() for k, v in self.param_state(i).items()}
-                state[i]["step"] = self.step_count
-        group = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, min_8bit_size=self.min_8bit_size,
-                     params=list(range(self.ntensors)))
-        return {"state": state, "param_groups": [group]}
+    _matched = ("qmap1", "qmap2")
 
-    def load_state_dict(self, sd: dict) -> None:
-        state = sd.get("state", {})
-        if not state:
-            self.reset_state()
-            return
-        if len(state) != self.ntensors:
-            raise ValueError(f"FlatAdamW8bit.load_state_dict: state for {len(state)} of {self.ntensors} parameters")
-        steps = set()
-        for i, st in state.items():
-            i = int(i)
-            if not 0 <= i < self.ntensors:
-                raise ValueError(f"FlatAdamW8bit.load_state_dict: parameter index {i} out of range (0..{self.ntensors - 1})")
-            mine = self.param_state(i)
-            if set(mine) != set(k for k in st if k != "step"):
-                raise ValueError(f"FlatAdamW8bit.load_state_dict: parameter {i} has state {sorted(st)}, expected {sorted(mine)} "
-                                 f"(min_8bit_size {self.min_8bit_size})")
-            for k in ("qmap1", "qmap2"):
-                if k in mine and not torch.equal(st[k].detach().to("cpu", torch.float32), mine[k].cpu()):
-                    raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} differs from this optimizer's quantization map")
-            for k in ("absmax1", "absmax2"):
-                if k in mine and tuple(st[k].shape) != tuple(mine[k].shape):
-                    raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} has {tuple(st[k].shape)} blocks, expected "
-                                     f"{tuple(mine[k].shape)} (block size {A8_BLOCK})")
-            for k in ("state1", "state2"):
-                if tuple(st[k].shape) != tuple(mine[k].shape) or st[k].dtype != mine[k].dtype:
-                    raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} is {st[k].dtype} {tuple(st[k].shape)}, "
-                                     f"expected {mine[k].dtype} {tuple(mine[k].shape)}")
-            steps.add(int(st["step"]))
-        if len(steps) != 1:
-            raise ValueError(f"FlatAdamW8bit.load_state_dict: per-parameter step counts differ ({sorted(steps)}); the fused update keeps one")
-        self.reset_state()
-        with torch.no_grad():
-            for i, st in state.items():
-                mine = self.param_state(int(i))
-                for k in ("state1", "state2", "absmax1", "absmax2"):
-                    if k in mine:
-                        mine[k].copy_(st[k].to(mine[k].device))
-        self.step_count = steps.pop()
+    def _saved_state(self, i: int) -> dict:
+        return {**super()._saved_state(i), "step": self.step_count}
+
+    def _group_dict(self) -> dict:
+        return dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, min_8bit_size=self.min_8bit_size)
+
+    def _check_entry(self, i: int, st: dict, mine: dict) -> None:
+        if set(mine) != set(k for k in st if k != "step"):
+            raise ValueError(f"FlatAdamW8bit.load_state_dict: parameter {i} has state {sorted(st)}, expected {sorted(mine)} "
+                             f"(min_8bit_size {self.min_8bit_size})")
+        for k in self._matched:
+            if k in mine and not torch.equal(st[k].detach().to("cpu", torch.float32), mine[k].cpu()):
+                raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} differs from this optimizer's quantization map")
+        for k in ("absmax1", "absmax2"):
+            if k in mine and tuple(st[k].shape) != tuple(mine[k].shape):
+                raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} has {tuple(st[k].shape)} blocks, expected "
+                                 f"{tuple(mine[k].shape)} (block size {A8_BLOCK})")
+        for k in ("state1", "state2"):
+            if tuple(st[k].shape) != tuple(mine[k].shape) or st[k].dtype != mine[k].dtype:
+                raise ValueError(f"FlatAdamW8bit.load_state_dict: {k} of parameter {i} is {st[k].dtype} {tuple(st[k].shape)}, "
+                                 f"expected {mine[k].dtype} {tuple(mine[k].shape)}")
+
+    def _copy_state(self, state: dict) -> None:
+        self.reset_state()          # the codes and absmax that no parameter's views cover (block tails) are those of step 0
+        super()._copy_state(state)
 
 
 def _adamw_validate(lr, betas, eps, weight_decay) -> None:

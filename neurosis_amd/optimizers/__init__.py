@@ -1,14 +1,14 @@
-"""MI355X mirror of `neurosis.optimizers` (/root/reference/src/neurosis/optimizers/__init__.py): the optimizer block of the
+"""MI355X mirror of `neurosis.optimizers` (reference `src/neurosis/optimizers/__init__.py`): the optimizer block of the
 example configs (`configs/sdxl/sdxl.example.yaml:158-169`, `configs/sd15/sd15.example.yml`) names
 `neurosis.optimizers.Adafactor` and `neurosis.optimizers.AdafactorScheduler`; under the `neurosis.` -> `neurosis_amd.` prefix
 swap these resolve here.
 
-`Adafactor` keeps the reference class's constructor (`optimizers/adafactor.py:100-131`) and is a real
-`torch.optim.Optimizer` (so LightningCLI's `OptimizerCallable`, `configure_optimizers` and checkpointing accept it), but its
-`step()` is the fused multi-tensor update of `neurosis_amd.optim.FlatAdafactor` on the flat fp32 master / gradient
-buffers: a handful of HIP launches for the whole UNet instead of a Python loop over ~1 700 tensors.  There is no eager
-fallback: parameters must live in a `FlatParamStore` (the engine's `setup_flat_params()` puts them there; parameters
-handed over on a GPU without one are re-homed into a new store on the first step).
+Every class here is a real `torch.optim.Optimizer` (so LightningCLI's `OptimizerCallable`, `configure_optimizers`, LR schedulers and
+checkpointing accept it) under its upstream constructor, whose `step()` is a fused update on the flat fp32 master / gradient buffers of
+a `FlatParamStore`; `_base._FusedOptimizer` holds what they share, and says what happens to parameters that have no store yet.
+
+`Adafactor` keeps the reference class's constructor (`optimizers/adafactor.py:100-131`) over `neurosis_amd.optim.FlatAdafactor`.  Its
+hyper-parameters are read when the flat optimizer is built, not at every step, and `step` is kept per parameter.
 
 `CAME` (`neurosis.optimizers.came.CAME`, reference `optimizers/came.py`) is the fused `neurosis_amd.optim.FlatCAME` under the
 reference class's constructor: Adafactor's factored second moment plus a first moment and a factored confidence statistic, 4 B of
@@ -28,45 +28,24 @@ not built.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
-import torch
 from torch.optim import Optimizer
 from torch.optim.lr_scheduler import LambdaLR
 
 from ..optim import FlatAdafactor
+from ._base import _FusedOptimizer, _group_store
 from .adamw8bit import AdamW8bit
 from .came import CAME
 
 __all__ = ["Adafactor", "AdafactorScheduler", "AdamW", "AdamW8bit", "CAME"]
 
 
-def _group_store(group: dict, who: str):
-    """The FlatParamStore that holds exactly this group's parameters (created on a GPU if they have none yet)."""
-    from ..nn import FlatParamStore
-
-    params = [p for p in group["params"] if p.requires_grad]
-    if not params:
-        raise ValueError(f"{who}: a parameter group without trainable parameters")
-    stores = {id(getattr(p, "_nk_store", None)): getattr(p, "_nk_store", None) for p in params}
-    if None in stores.values():
-        if len(stores) > 1:
-            raise ValueError(f"{who}: a parameter group mixes store-managed and free parameters")
-        if not params[0].is_cuda:
-            raise RuntimeError(f"{who}: the fused update runs on HIP buffers; move the model to the GPU (and call "
-                               "setup_flat_params()) before the first step -- there is no CPU path")
-        return FlatParamStore(params)
-    if len(stores) != 1:
-        raise ValueError(f"{who}: the parameters of one group live in {len(stores)} different flat stores")
-    store = next(iter(stores.values()))
-    if len(store.params) != len(params) or any(a is not b for a, b in zip(store.params, params)):
-        raise ValueError(f"{who}: a parameter group must cover its flat store exactly ({len(params)} parameters given, "
-                         f"{len(store.params)} in the store): the fused kernels update the whole buffer")
-    return store
-
-
-class Adafactor(Optimizer):
+class Adafactor(_FusedOptimizer):
     """`neurosis.optimizers.Adafactor` (reference optimizers/adafactor.py:100-255), fused."""
+
+    _strict_groups = False
 
     def __init__(self, params, lr: Optional[float] = None, eps: tuple[float, float] = (1e-30, 1e-3), clip_threshold: float = 1.0,
                  decay_rate: float = -0.8, beta1: Optional[float] = None, weight_decay: float = 0.0, scale_parameter: bool = True,
@@ -80,51 +59,18 @@ class Adafactor(Optimizer):
         defaults = dict(lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1, weight_decay=weight_decay,
                         scale_parameter=scale_parameter, relative_step=relative_step, warmup_init=warmup_init, differentiable=False)
         super().__init__(params, defaults)
-        self._flat: list[FlatAdafactor] = []
-        self._pending_state: Optional[dict] = None
 
-    # -- binding to the flat buffers --------------------------------------------------------------------
-    def bind(self) -> list[FlatAdafactor]:
-        """One FlatAdafactor per parameter group (each group = one flat store).  Idempotent."""
-        if not self._flat:
-            for g in self.param_groups:
-                store = _group_store(g, "Adafactor")
-                self._flat.append(FlatAdafactor(store, lr=g["lr"] if not g["relative_step"] else None, eps=tuple(g["eps"]),
-                                                clip_threshold=g["clip_threshold"], decay_rate=g["decay_rate"], beta1=g["beta1"],
-                                                weight_decay=g["weight_decay"], scale_parameter=g["scale_parameter"],
-                                                relative_step=g["relative_step"], warmup_init=g["warmup_init"],
-                                                boundaries=g.get("chunk_boundaries")))
-            if self._pending_state is not None:
-                sd, self._pending_state = self._pending_state, None
-                self._load_flat(sd)
-        return self._flat
-
-    @property
-    def flat(self) -> FlatAdafactor:
-        """The fused optimizer of the first (UNet) group."""
-        return self.bind()[0]
-
-    @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for f in self.bind():
-            f.step(grad_scale)
-        return loss
-
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        """Nothing to do, on purpose: `.grad` tensors are views of the store's flat gradient buffer and every gradient is
-        OVERWRITTEN by the kernel that produces it on the first micro-batch of a step (FlatParamStore docstring); setting
-        them to None -- torch's default -- would detach the parameters from that buffer."""
+    def _make_flat(self, g: dict) -> FlatAdafactor:
+        """Built once from the group's hyper-parameters: step() does not read them again (only `grad_scale` reaches the update)."""
+        return FlatAdafactor(_group_store(g, "Adafactor"), lr=g["lr"] if not g["relative_step"] else None, eps=tuple(g["eps"]),
+                             clip_threshold=g["clip_threshold"], decay_rate=g["decay_rate"], beta1=g["beta1"],
+                             weight_decay=g["weight_decay"], scale_parameter=g["scale_parameter"],
+                             relative_step=g["relative_step"], warmup_init=g["warmup_init"], boundaries=g.get("chunk_boundaries"))
 
     @staticmethod
     def _get_lr(param_group: dict, param_state: dict) -> float:
         """adafactor.py:133-147 (what AdafactorScheduler reports), from the group's hyper-parameters and a state holding
         `step` and `RMS`."""
-        import math
-
         rel_step_sz = param_group["lr"]
         if param_group["relative_step"]:
             min_step = 1e-6 * param_state["step"] if param_group["warmup_init"] else 1e-2
@@ -133,40 +79,6 @@ class Adafactor(Optimizer):
         if param_group["scale_parameter"]:
             param_scale = max(param_group["eps"][1], float(param_state["RMS"]))
         return param_scale * rel_step_sz
-
-    # -- checkpointing: torch's layout, the reference's per-parameter keys ------------------------------
-    def state_dict(self) -> dict:
-        groups, state, base = [], {}, 0
-        flats = self._flat
-        for gi, g in enumerate(self.param_groups):
-            n = len(g["params"])
-            packed = {k: v for k, v in g.items() if k != "params"}
-            packed["params"] = list(range(base, base + n))
-            groups.append(packed)
-            if gi < len(flats):
-                for i, st in flats[gi].state_dict()["state"].items():
-                    state[base + i] = st
-            base += n
-        if not flats and self._pending_state is not None:
-            state = self._pending_state["state"]
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, state_dict: dict) -> None:
-        for g, saved in zip(self.param_groups, state_dict.get("param_groups", [])):
-            for k, v in saved.items():
-                if k != "params":
-                    g[k] = v
-        if self._flat:
-            self._load_flat(state_dict)
-        else:
-            self._pending_state = state_dict      # applied when the flat buffers exist (first step / bind())
-
-    def _load_flat(self, sd: dict) -> None:
-        base = 0
-        for g, f in zip(self.param_groups, self._flat):
-            n = len(g["params"])
-            f.load_state_dict({"state": {int(i) - base: st for i, st in sd.get("state", {}).items() if base <= int(i) < base + n}})
-            base += n
 
 
 class AdafactorScheduler(LambdaLR):
@@ -188,55 +100,42 @@ class AdafactorScheduler(LambdaLR):
     def get_lr(self):
         opt = self.optimizer
         flats = getattr(opt, "_flat", [])
-        lrs = [float(f.lr_t[0]) for f in flats if f.step_count > 0]
+        lrs = [float(f.lr_t[0]) for f in flats if getattr(f, "step_count", 0) > 0]      # (AdamW's groups count no steps of their own)
         if len(lrs) == 0:
             lrs = self.base_lrs  # if called before stepping
         return lrs
 
 
-class AdamW(Optimizer):
+class _StoreAdamW:
+    """`FlatParamStore.adamw_step` (the moments live in the store itself) behind the interface of the flat optimizers."""
+
+    def __init__(self, store):
+        self.store = store
+
+    def step(self, grad_scale: float = 1.0) -> None:
+        self.store.adamw_step(self.lr, self.betas, self.eps, self.weight_decay, grad_scale)
+
+    def state_dict(self) -> dict:
+        return self.store.optimizer_state_dict()
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.store.load_optimizer_state_dict(sd)
+
+
+class AdamW(_FusedOptimizer):
     """Fused flat AdamW (`FlatParamStore.adamw_step`, one launch over all parameters) under `torch.optim.AdamW`'s arguments."""
+
+    _strict_groups = False
 
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self._stores = []
 
-    def bind(self):
-        if not self._stores:
-            self._stores = [_group_store(g, "AdamW") for g in self.param_groups]
-        return self._stores
+    def _make_flat(self, g: dict) -> _StoreAdamW:
+        return _StoreAdamW(_group_store(g, "AdamW"))
 
-    @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for g, store in zip(self.param_groups, self.bind()):
-            store.adamw_step(g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"], grad_scale)
-        return loss
-
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        """See Adafactor.zero_grad: gradients are overwritten by their producers; the views must stay attached."""
-
-    def state_dict(self) -> dict:
-        groups, state, base = [], {}, 0
-        for gi, g in enumerate(self.param_groups):
-            n = len(g["params"])
-            groups.append({**{k: v for k, v in g.items() if k != "params"}, "params": list(range(base, base + n))})
-            if gi < len(self._stores):
-                for i, st in self._stores[gi].optimizer_state_dict()["state"].items():
-                    state[base + i] = st
-            base += n
-        return {"state": state, "param_groups": groups}
+    def _push(self, g: dict, f: _StoreAdamW) -> None:
+        f.lr, f.betas, f.eps, f.weight_decay = g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]
 
     def load_state_dict(self, state_dict: dict) -> None:
-        for g, saved in zip(self.param_groups, state_dict.get("param_groups", [])):
-            for k, v in saved.items():
-                if k != "params":
-                    g[k] = v
-        base = 0
-        for g, store in zip(self.param_groups, self.bind()):
-            n = len(g["params"])
-            store.load_optimizer_state_dict({"state": {int(i) - base: st for i, st in state_dict.get("state", {}).items() if base <= int(i) < base + n}})
-            base += n
+        self.bind()         # the state lives in the stores: nothing is held back for a later bind()
+        super().load_state_dict(state_dict)

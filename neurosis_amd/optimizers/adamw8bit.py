@@ -1,10 +1,7 @@
 """`AdamW8bit`: bitsandbytes' blockwise 8-bit AdamW (`bitsandbytes.optim.AdamW8bit`, the optimizer of the reference's
-`configs/sdxl/sdxl-te.example.yaml`), fused on the flat buffers.
-
-Same constructor and defaults as `bitsandbytes.optim.AdamW8bit`, and a real `torch.optim.Optimizer` (so LightningCLI's
-`OptimizerCallable`, `configure_optimizers`, LR schedulers and checkpointing accept it), but its `step()` is one HIP launch of
-`neurosis_amd.optim.FlatAdamW8bit` (`csrc/adamw8bit.hip`) over the whole flat fp32 master / gradient buffer.  The algorithm is
-defined in `FlatAdamW8bit`'s docstring; bit-for-bit interchange with bitsandbytes itself is not claimed.  There is no eager fallback.
+`configs/sdxl/sdxl-te.example.yaml`): its constructor and defaults over one HIP launch of `neurosis_amd.optim.FlatAdamW8bit`
+(`csrc/adamw8bit.hip`) per parameter group.  The algorithm is defined in `FlatAdamW8bit`'s docstring; bit-for-bit interchange with
+bitsandbytes itself is not claimed.  Binding, stepping and checkpoints are `_FusedOptimizer`'s.
 
 Not built, and refused loudly: `amsgrad=True`, `block_wise=False` (one absmax per tensor), `percentile_clipping < 100`, `args`
 (bitsandbytes' per-module override object) and `is_paged=True` (paged state).  `optim_bits` is accepted and ignored, as in
@@ -12,19 +9,15 @@ bitsandbytes' own AdamW8bit, which always keeps 8-bit state.
 """
 from __future__ import annotations
 
-from typing import Optional
-
-import torch
-from torch.optim import Optimizer
-
 from ..optim import FlatAdamW8bit, _adamw_validate
+from ._base import _FusedOptimizer, _group_store
 
 __all__ = ["AdamW8bit"]
 
 _WHO = "neurosis_amd.optimizers.AdamW8bit"
 
 
-class AdamW8bit(Optimizer):
+class AdamW8bit(_FusedOptimizer):
     """8-bit blockwise AdamW, fused (bitsandbytes.optim.AdamW8bit's constructor)."""
 
     def __init__(self, params, lr: float = 1e-3, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
@@ -48,81 +41,14 @@ class AdamW8bit(Optimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
         super().__init__(params, defaults)
         self.min_8bit_size = int(min_8bit_size)
-        self._flat: list[FlatAdamW8bit] = []
-        self._pending_state: Optional[dict] = None
 
-    # -- binding to the flat buffers --------------------------------------------------------------------
-    def bind(self) -> list[FlatAdamW8bit]:
-        """One FlatAdamW8bit per parameter group (each group = one flat store).  Idempotent."""
-        from . import _group_store
+    def _make_flat(self, g: dict) -> FlatAdamW8bit:
+        return FlatAdamW8bit(_group_store(g, "AdamW8bit"), lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"],
+                             min_8bit_size=self.min_8bit_size)
 
-        if not self._flat:
-            for g in self.param_groups:
-                self._flat.append(FlatAdamW8bit(_group_store(g, "AdamW8bit"), lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"],
-                                                weight_decay=g["weight_decay"], min_8bit_size=self.min_8bit_size))
-            if self._pending_state is not None:
-                sd, self._pending_state = self._pending_state, None
-                self._load_flat(sd)
-        return self._flat
+    def _push(self, g: dict, f: FlatAdamW8bit) -> None:
+        _adamw_validate(g["lr"], g["betas"], g["eps"], g["weight_decay"])
+        f.lr, f.betas, f.eps, f.weight_decay = float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"])
 
-    @property
-    def flat(self) -> FlatAdamW8bit:
-        """The fused optimizer of the first (UNet) group."""
-        return self.bind()[0]
-
-    @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for g, f in zip(self.param_groups, self.bind()):
-            # the group's hyper-parameters as they are NOW (an LR scheduler or a loaded checkpoint may have changed them)
-            _adamw_validate(g["lr"], g["betas"], g["eps"], g["weight_decay"])
-            f.betas, f.eps, f.weight_decay = tuple(float(b) for b in g["betas"]), float(g["eps"]), float(g["weight_decay"])
-            f.step(grad_scale, lr=g["lr"])
-            g["step"] = f.step_count
-        return loss
-
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        """Nothing to do, on purpose (see neurosis_amd.optimizers.Adafactor.zero_grad): `.grad` tensors are views of the store's
-        flat gradient buffer, overwritten by their producers on the first micro-batch of a step."""
-
-    # -- checkpointing: torch's layout, bitsandbytes' per-parameter keys ------------------------------------------------
-    def state_dict(self) -> dict:
-        groups, state, base = [], {}, 0
-        for gi, g in enumerate(self.param_groups):
-            n = len(g["params"])
-            packed = {k: v for k, v in g.items() if k != "params"}
-            packed["params"] = list(range(base, base + n))
-            groups.append(packed)
-            if gi < len(self._flat):
-                packed["step"] = self._flat[gi].step_count
-                for i, st in self._flat[gi].state_dict()["state"].items():
-                    state[base + i] = st
-            base += n
-        if not self._flat and self._pending_state is not None:
-            state = self._pending_state["state"]
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, state_dict: dict) -> None:
-        saved_groups = state_dict.get("param_groups", [])
-        if len(saved_groups) != len(self.param_groups):
-            raise ValueError(f"AdamW8bit.load_state_dict: {len(saved_groups)} parameter groups in the checkpoint, {len(self.param_groups)} here")
-        for g, saved in zip(self.param_groups, saved_groups):
-            if len(saved.get("params", g["params"])) != len(g["params"]):
-                raise ValueError("AdamW8bit.load_state_dict: a parameter group's size differs from the checkpoint's")
-            for k, v in saved.items():
-                if k != "params":
-                    g[k] = v
-        if self._flat:
-            self._load_flat(state_dict)
-        else:
-            self._pending_state = state_dict      # applied when the flat buffers exist (first step / bind())
-
-    def _load_flat(self, sd: dict) -> None:
-        base = 0
-        for g, f in zip(self.param_groups, self._flat):
-            n = len(g["params"])
-            f.load_state_dict({"state": {int(i) - base: st for i, st in sd.get("state", {}).items() if base <= int(i) < base + n}})
-            base += n
+    def _group_extras(self, f: FlatAdamW8bit) -> dict:
+        return {"step": f.step_count}       # the group carries the step count beside the per-parameter ones (which are what a load reads)
