@@ -89,6 +89,13 @@ int nk_debug_raise_health(void* stream);
 /* Diagnostic: writes the device's 100 MHz constant clock (s_memrealtime) to *dst, stream-ordered and capturable into a hipGraph
  * (tools/step_timeline.py: where the replayed backward segments of the two streams lie in time, untraced). */
 int nk_debug_stamp(unsigned long long* dst, void* stream);
+/* Test hooks: which kernels did a call launch?  Every launch site reports its kernel's name -- with the template arguments where several
+ * instantiations share one (nk_gemm_g2p_kernel<160>, nk_conv3x3_halo_kernel<128,2,1>) -- into a per-thread log while the log is on.
+ * nk_debug_launch_log(mode): 1 = on and cleared, 2 = cleared, 0 = off.  nk_debug_launch_names(buf, cap) copies the names logged by the calling
+ * thread since the last clear into the HOST buffer, one per line, and returns their number (the log keeps the first 64).  Host-only: nothing
+ * is launched, so both may be called while a stream is capturing. */
+int nk_debug_launch_log(int mode);
+long nk_debug_launch_names(char* buf, long cap);
 
 /* `count` (<= 8) weight gradients of identical shape in ONE launch: the three 1280x1280 projections of a transformer
  * block are 100 tiles each, far below one workgroup per CU on their own.  dy / x / dw are HOST arrays of device pointers. */

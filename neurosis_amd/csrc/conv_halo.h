@@ -629,7 +629,11 @@ static int launch_halo_as(const NkGemmParams& p_in, hipStream_t stream) {
   const NkGather& g = p.ga;
   const long tiles = (long)p.halo_nb * ((g.W + CH_TW - 1) / CH_TW) * ((g.H + HaloGeom<MI>::TH - 1) / HaloGeom<MI>::TH) * (p.N / BN_);
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(HaloRing<BN_>::THREADS), HaloGeom<MI>::template smem<BN_>(), stream, p);
-  return nk_check_launch("nk_conv3x3_halo_kernel");
+  // <column-tile width, tile rows (MI = 4: 8 rows, MI = 2: 4 rows), statistics epilogue>
+  if (BN_ == 160 && MI == 4) return nk_check_launch(STATS ? "nk_conv3x3_halo_kernel<160,8,stats=1>" : "nk_conv3x3_halo_kernel<160,8,stats=0>");
+  if (BN_ == 160) return nk_check_launch(STATS ? "nk_conv3x3_halo_kernel<160,4,stats=1>" : "nk_conv3x3_halo_kernel<160,4,stats=0>");
+  if (MI == 4) return nk_check_launch(STATS ? "nk_conv3x3_halo_kernel<128,8,stats=1>" : "nk_conv3x3_halo_kernel<128,8,stats=0>");
+  return nk_check_launch(STATS ? "nk_conv3x3_halo_kernel<128,4,stats=1>" : "nk_conv3x3_halo_kernel<128,4,stats=0>");
 }
 template <int STATS>
 static int launch_halo_s(const NkGemmParams& p, hipStream_t stream) {

@@ -259,5 +259,5 @@ static int launch_wgrad_halo(NkGemmParams& p, hipStream_t stream) {
   auto kern = p.dbias ? nk_conv3x3_wgrad_halo_kernel<1> : nk_conv3x3_wgrad_halo_kernel<0>;
   nk_optin_lds((const void*)kern, WH_SMEM);
   hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * S)), dim3(512), WH_SMEM, stream, p);
-  return nk_check_launch("nk_conv3x3_wgrad_halo_kernel");
+  return nk_check_launch(p.dbias ? "nk_conv3x3_wgrad_halo_kernel<bias=1>" : "nk_conv3x3_wgrad_halo_kernel<bias=0>");
 }

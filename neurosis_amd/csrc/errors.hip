@@ -9,7 +9,15 @@ void nk_set_error(const char* file, int line, const char* what) {
   snprintf(g_err, sizeof(g_err), "%s:%d: %s", file, line, what);
 }
 
+// ---- launch log (test hook): while it is on, every nk_check_launch records the name it was given.  Host-only and thread-local: nothing is
+// launched, so it works during graph capture; with it off a launch pays the one flag test below.
+#define NK_LAUNCH_LOG_MAX 64
+static thread_local bool g_log_on = false;
+static thread_local int g_log_n = 0;
+static thread_local const char* g_log[NK_LAUNCH_LOG_MAX];     // the callers pass string literals: the pointers stay valid
+
 int nk_check_launch(const char* what) {
+  if (g_log_on && g_log_n < NK_LAUNCH_LOG_MAX) g_log[g_log_n++] = what;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     snprintf(g_err, sizeof(g_err), "%s: launch failed: %s", what, hipGetErrorString(e));
@@ -103,6 +111,27 @@ extern "C" int nk_debug_raise_health(void* stream) {
   if (!d) { nk_set_error(__FILE__, __LINE__, "health word allocation failed"); return NK_ERR_LAUNCH; }
   hipLaunchKernelGGL(nk_raise_health_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, d);
   return nk_check_launch("nk_raise_health_kernel");
+}
+
+// test hooks: mode 1 = log on (and cleared), 2 = cleared, 0 = off (and cleared)
+extern "C" int nk_debug_launch_log(int mode) {
+  NK_CHECK_ARG(mode >= 0 && mode <= 2);
+  if (mode != 2) g_log_on = mode == 1;
+  g_log_n = 0;
+  return NK_OK;
+}
+// the names logged by this thread since the last clear, one per line, into buf[cap] (NUL-terminated; names that do not fit are left out);
+// returns how many were logged (at most NK_LAUNCH_LOG_MAX are kept)
+extern "C" long nk_debug_launch_names(char* buf, long cap) {
+  if (!buf || cap <= 0) return -1;
+  long at = 0;
+  buf[0] = 0;
+  for (int i = 0; i < g_log_n; ++i) {
+    const int w = snprintf(buf + at, (size_t)(cap - at), "%s\n", g_log[i]);
+    if (w < 0 || at + w >= cap) { buf[at] = 0; break; }
+    at += w;
+  }
+  return g_log_n;
 }
 
 // diagnostic: a stream-ordered timestamp (the 100 MHz constant clock, s_memrealtime) into a caller-owned device word -- capturable into a

@@ -1654,7 +1654,7 @@ static int launch_xl(const NkGemmParams& p_in, hipStream_t stream) {
     dim3 grid(((p.M + XL_BM - 1) / XL_BM) * ((p.N + XL_BN - 1) / XL_BN), 1, 1);
     if (p.geglu_h) hipLaunchKernelGGL(kerng, grid, dim3(512), XL_SMEM_BYTES, stream, p);
     else hipLaunchKernelGGL(kern, grid, dim3(512), XL_SMEM_BYTES, stream, p);
-    return nk_check_launch("nk_gemm_xl2g_kernel");
+    return nk_check_launch(p.geglu_h ? "nk_gemm_xl2g_kernel<geglu=1>" : "nk_gemm_xl2g_kernel<geglu=0>");
   }
   return launch_xl_as<AMODE, 64, 64>(p_in, stream);
 }

@@ -802,12 +802,12 @@ static int launch_g2_as(const NkGemmParams& p_in, hipStream_t stream) {
     auto kp = nk_gemm_g2p_kernel<AMODE, BMODE, OUT_F32, BN_>;
     nk_optin_lds((const void*)kp, G2_SMEM_BYTES);
     hipLaunchKernelGGL(kp, grid, dim3(768), G2_SMEM_BYTES, stream, p);
-    return nk_check_launch("nk_gemm_g2p_kernel");
+    return nk_check_launch(BN_ == 160 ? "nk_gemm_g2p_kernel<160>" : "nk_gemm_g2p_kernel<128>");
   }
   auto kern = nk_gemm_g2_kernel<AMODE, BMODE, OUT_F32, BN_>;
   nk_optin_lds((const void*)kern, G2_SMEM_BYTES);
   hipLaunchKernelGGL(kern, grid, dim3(512), G2_SMEM_BYTES, stream, p);
-  return nk_check_launch("nk_gemm_g2_kernel");
+  return nk_check_launch(BN_ == 160 ? "nk_gemm_g2_kernel<160>" : "nk_gemm_g2_kernel<128>");
 }
 template <int AMODE, int BMODE, int OUT_F32>
 static int launch_g2(const NkGemmParams& p, hipStream_t stream) {

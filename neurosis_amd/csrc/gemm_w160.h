@@ -467,5 +467,5 @@ static int launch_w160_as(NkGemmParams& p, int splitk, hipStream_t stream) {
   nk_optin_lds((const void*)kern, W160Cfg<BN_>::SMEM);
   dim3 grid(((p.M + W160_BM - 1) / W160_BM) * ((p.N + BN_ - 1) / BN_), splitk, p.nbatch ? p.nbatch : 1);
   hipLaunchKernelGGL(kern, grid, dim3(512), W160Cfg<BN_>::SMEM, stream, p);
-  return nk_check_launch("nk_gemm_w160_kernel");
+  return nk_check_launch(BN_ == 160 ? "nk_gemm_w160_kernel<160>" : "nk_gemm_w160_kernel<128>");
 }

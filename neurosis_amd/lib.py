@@ -118,6 +118,7 @@ SIGNATURES: dict[str, list] = {
     "nk_ema_flat": [vp, vp, i64, f32, vp],
     "nk_debug_raise_health": [vp],
     "nk_debug_stamp": [vp, vp],
+    "nk_debug_launch_log": [i32],
     "nk_health_clear": [],
     "nk_health_export": [vp, vp],
     "nk_health_import": [vp, vp],
@@ -145,6 +146,7 @@ SIZE_QUERIES: dict[str, list] = {
     "nk_adamw8bit_tensor_bytes": [],
     "nk_gemm_sk_status": [],
     "nk_health_status": [],
+    "nk_debug_launch_names": [C.c_char_p, i64],
 }
 
 _lib = None
@@ -180,6 +182,20 @@ def load() -> C.CDLL:
         fn.restype = i64
     _lib = lib
     return lib
+
+
+def launch_log(mode: int) -> None:
+    """Test hook: 1 = log the kernel name of every launch of this thread (cleared), 2 = clear, 0 = off."""
+    call("nk_debug_launch_log", int(mode))
+
+
+def launched() -> list[str]:
+    """Test hook: the kernel names logged since the last clear, in launch order."""
+    buf = C.create_string_buffer(8192)
+    n = query("nk_debug_launch_names", buf, len(buf))
+    if n < 0:
+        raise NkError("nk_debug_launch_names failed")
+    return buf.value.decode().split("\n")[:-1]
 
 
 def query(name: str, *args) -> int:

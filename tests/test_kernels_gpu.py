@@ -679,7 +679,14 @@ def test_feedforward_projection_with_fused_geglu_forward(ops, shape, monkeypatch
     # bit for bit with every XCD walking k from 0: under the default rotated order (NK_GEMM_KROT, gemm_g2.h OpG2::rotate) the k-slabs of an output
     # element are summed in an order that depends on the XCD its tile lands on, and the fused kernel's column tiles are not the plain one's
     monkeypatch.setenv("NK_GEMM_KROT", "0")
+    from neurosis_amd import lib
+
+    lib.launch_log(1)
     u, h, bwd = ops.linear_geglu_fwd(dev(x), wp, bp)
+    names = lib.launched()
+    lib.launch_log(0)
+    if fused:     # the library's own word for what ran, not this test's belief (tests/gemm_exact.py)
+        assert "nk_gemm_xl2g_kernel<geglu=1>" in names, f"the dispatch moved: the fused GEGLU forward ran {names}; this test needs a shape the kernel takes"
     u2, _ = ops.linear_fwd(dev(x), wp, bp)
     h2 = ops.geglu_fwd(u2)[0]
     assert torch.equal(u, u2) and torch.equal(h, h2)
