@@ -91,9 +91,12 @@ int nk_debug_raise_health(void* stream);
 int nk_debug_stamp(unsigned long long* dst, void* stream);
 /* Test hooks: which kernels did a call launch?  Every launch site reports its kernel's name -- with the template arguments where several
  * instantiations share one (nk_gemm_g2p_kernel<160>, nk_conv3x3_halo_kernel<128,2,1>) -- into a per-thread log while the log is on.
- * nk_debug_launch_log(mode): 1 = on and cleared, 2 = cleared, 0 = off.  nk_debug_launch_names(buf, cap) copies the names logged by the calling
- * thread since the last clear into the HOST buffer, one per line, and returns their number (the log keeps the first 64).  Host-only: nothing
- * is launched, so both may be called while a stream is capturing. */
+ * nk_debug_launch_log(mode): 1 = on and cleared, 2 = cleared, 0 = off.  nk_debug_launch_names(buf, cap) copies the lines logged by the calling
+ * thread since the last clear into the HOST buffer and returns their number (the log keeps the first 64): one line per launch, the name, and
+ * behind a launch of the GEMM / convolution tile engine one more, its plan: `name grid=x,y,z block smem splitk ksplit_len acc zero krot gm
+ * chunk`.  Host-only: nothing is launched, so both may be called while a stream is capturing.
+ * mode 3 = on, cleared and PLAN-ONLY: the tile engine logs the launch it plans for a call and returns NK_OK before it touches the GPU (no
+ * zero-fill, no workspace, no launch; outputs stay unwritten) -- which kernel a problem gets can be asked without a device. */
 int nk_debug_launch_log(int mode);
 long nk_debug_launch_names(char* buf, long cap);
 

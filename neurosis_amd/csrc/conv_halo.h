@@ -6,7 +6,7 @@
 // inputs in LDS: the nine taps of a 64-channel slab read their A fragments from that one image at per-lane addresses
 // (pixel + tap offset), and only the weights stream through the ring.
 //
-// Structure: the two-group staggered loop of nk_gemm_g2_kernel (gemm_g2.h) with the A operand replaced.
+// Structure: the two-group staggered loop of the two-group GEMM (gemm_g2.h) with the A operand replaced.
 //   * tile = 32*TH output pixels x BN output channels (160 or 128); 8 waves = 2 column groups x 4 pixel-row groups; a wave owns
 //     TH/4 tile rows of 32 pixels = MI 16-pixel row blocks, each tile row being 32 CONSECUTIVE rows of the [N*H*W][Cout] output;
 //   * k order is (64-channel slab, tap): the halo of slab s+1 is fetched while slab s is multiplied (two buffers);
@@ -51,10 +51,7 @@ extern "C" int nk_debug_halo_stamps(unsigned long long* host_out, int nwg) {
 #define CH_STAMP_RT(slot)
 #define CH_KSTAMP(t, ph)
 #endif
-#define CH_TW 32
-#define CH_HW (CH_TW + 2)
-#define CH_BSTAGE 20480                         // weights of one k-step: up to 160 rows x 128 B
-#define CH_NS 3
+// (CH_TW, CH_HW and the two weight rings' CH_BSTAGE / CH_NS, CH_BSTAGE_DEEP / CH_NS_DEEP: gemm_plan.h)
 // Round 6: the 128-column tile stages its weights in the R phase, into a ring of FOUR stages.  Phase stamps (tools/halo_stamps.py, the VAE's
 // 128 -> 128 convolution at 1024^2: a k-step of 1 830 cycles against a 1 024-cycle MFMA floor, every k-step alike) put ~450 cycles of stalled
 // weight-DMA issue IN FRONT of the 32 MFMAs of every M phase -- a wave issues in order -- while the R phase ends in 600-900 cycles of waiting
@@ -62,14 +59,9 @@ extern "C" int nk_debug_halo_stamps(unsigned long long* host_out, int nwg) {
 // phase instead, half a k-step earlier, the DMA of k-step t + 2 would race the other group's last reads of k-step t - 1 in a three-stage
 // ring (issued before the barrier, awaited behind it); with four stages it overwrites k-step t - 2's.  (Three k-steps ahead from the M
 // phase was measured first and changed nothing: the weights were never late.)  The 160-column tile has no room for a fourth stage.
-#define CH_BSTAGE_DEEP 16384
-#define CH_NS_DEEP 4
+// (That eight-wave R-phase arrangement was itself superseded by the producer waves below, which kept its four-stage ring.)
 template <int BN_> struct HaloRing {
-#ifdef NK_HALO_FIRE_IN_M      // diagnostic build: the round-5 arrangement for every tile (A/B runs)
-  static constexpr bool DEEP = false;
-#else
   static constexpr bool DEEP = BN_ == 128;
-#endif
   static constexpr int BST = DEEP ? CH_BSTAGE_DEEP : CH_BSTAGE;
   static constexpr int NS = DEEP ? CH_NS_DEEP : CH_NS;
   static constexpr int AHEAD = 2;                                     // k-steps between a stage's DMA and its first read
@@ -78,13 +70,8 @@ template <int BN_> struct HaloRing {
   // 16 KiB = 512 cycles at 128 B/clk, as long as the other group's 512-cycle M phase): whatever the same waves spend issuing DMA -- an LDS-DMA
   // instruction holds the wave's issue until the fill path takes it -- lands on top, in BOTH groups' R phases, twice per k-step.  Waves 8-10
   // stage the weights (pieces pw + 3 i: 6 / 5 / 5 per k-step), wave 11 the halo (44 / 26 pieces per slab over taps 0-6).  Needs three waves
-  // per SIMD, i.e. <= 168 VGPRs: the 160-column tile (233) keeps the eight-wave form.  -DNK_HALO_NO_PROD: the eight-wave form everywhere (A/B).
-#ifdef NK_HALO_NO_PROD
-  static constexpr bool PROD = false;
-#else
-  static constexpr bool PROD = DEEP;
-#endif
-  static constexpr bool FIRE_IN_R = DEEP && !PROD;                    // weights of k-step t + 2 issued in the R phase of k-step t (else: its M phase)
+  // per SIMD, i.e. <= 168 VGPRs: the 160-column tile (233) keeps the eight-wave form, its weights of k-step t + 2 issued in the M phase of k-step t.
+  static constexpr bool PROD = BN_ == 128;
   static constexpr int THREADS = PROD ? 768 : 512;
   static constexpr int WAVES_PER_SIMD = PROD ? 3 : 2;
 };
@@ -102,7 +89,9 @@ struct HaloGeom {
   static constexpr int SMEM = 2 * HBUF + CH_NS * CH_BSTAGE;           // 114688 / 151552 (the 160-column tile)
   static constexpr int SMEM_DEEP = 2 * HBUF + CH_NS_DEEP * CH_BSTAGE_DEEP;   // 118784 / 155648 (the 128-column tile's four-stage ring)
   template <int BN_> static constexpr int smem() { return HaloRing<BN_>::DEEP ? SMEM_DEEP : SMEM; }
+  static_assert(HPIECES == halo_hpieces(TH) && smem<128>() == halo_smem(128, TH) && smem<160>() == halo_smem(160, TH), "the planner's LDS size");
 };
+static_assert(HaloRing<128>::THREADS == halo_threads(128) && HaloRing<160>::THREADS == halo_threads(160), "the planner's block size");
 // halo pieces a halo wave issues at tap t when its NPH pieces are spread over taps 0..LAST
 constexpr int ch_count(int NPH, int LAST, int t) { return t > LAST ? 0 : (NPH + LAST - t) / (LAST + 1); }
 constexpr int ch_start(int NPH, int LAST, int t) { int s = 0; for (int u = 0; u < t; ++u) s += ch_count(NPH, LAST, u); return s; }
@@ -355,12 +344,6 @@ __global__ __launch_bounds__(HaloRing<BN_>::THREADS, HaloRing<BN_>::WAVES_PER_SI
         }
         // the next slab's halo has landed (this wave's share): before the barrier that precedes its first use
         if (tap == 8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      } else if constexpr (R::FIRE_IN_R) {
-        constexpr int tap2 = (tap + 2) % 9;
-        wb.fire_next(t + 2 < nk, tap2 == 8 ? adv_end : adv_tap, ring + sn, wave);
-        // the weights of k-step t + 1 have landed (this wave's share); those of t + 2, just issued, stay in flight
-        if (nbw == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the weights of k-step t + 1 have landed (this wave's share)
       }
@@ -371,7 +354,7 @@ __global__ __launch_bounds__(HaloRing<BN_>::THREADS, HaloRing<BN_>::WAVES_PER_SI
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
-      if constexpr (!R::FIRE_IN_R && !PROD) {
+      if constexpr (!PROD) {
         if (!hwave) {
           // weights of k-step t + 2; the pointer then moves on to k-step t + 3: the next tap, unless t + 2 is a slab's last tap
           constexpr int tap2 = (tap + 2) % 9;
@@ -586,68 +569,3 @@ __global__ __launch_bounds__(HaloRing<BN_>::THREADS, HaloRing<BN_>::WAVES_PER_SI
 #undef CH_BAR
 }
 
-// NK_CONV_HALO=0 keeps every convolution on the gather kernels (A/B runs)
-static bool halo_shape_ok(const NkGemmParams& p) {
-  const NkGather& g = p.ga;
-  if (!p.halo_nb || g.KW != 3 || p.K != 9 * g.C || g.rs != 1 || g.ks != 1 || g.div != 1 || g.off_h != -1 || g.off_w != -1) return false;
-  if (g.Ho != g.H || g.Wo != g.W || (g.C & 63) || p.alpha != 1.0f || p.nbatch) return false;
-  if (p.N % 160 && p.N % 128) return false;
-  if ((p.N & 7) || (p.ldc & 7) || (p.residual && (p.ldr & 7))) return false;
-  return true;
-}
-// column-tile width of the halo-tile launch for N output channels: THE rule (tile planner, launcher and the statistics-epilogue query
-// nk_conv2d_stats_tiles all ask here: the epilogue's partial layout depends on it)
-static int halo_bn(int N) { return N % 160 == 0 ? 160 : 128; }
-// tile height for this problem: 8-row tiles where they still give about one workgroup per CU, else 4-row tiles; 0 = the patches
-// would cover the image with too much waste (ragged small images keep the gather kernels)
-static int halo_tile_rows(const NkGemmParams& p) {
-  const NkGather& g = p.ga;
-  const int bn = halo_bn(p.N);
-  const long txn = (g.W + CH_TW - 1) / CH_TW;
-  for (int th = 8; th >= 4; th -= 4) {
-    const long tyn = (g.H + th - 1) / th;
-    const long cover = txn * CH_TW * tyn * th;
-    if (cover * 100 > (long)g.H * g.W * 115) continue;
-    const long tiles = (long)p.halo_nb * txn * tyn * (p.N / bn);
-    if (th == 8 && tiles < 224) continue;
-    return th;
-  }
-  return 0;
-}
-static bool use_halo(const NkGemmParams& p, int amode, int bmode, int out_f32) {
-  if (amode != OP_KCG || bmode != OP_KC || out_f32) return false;
-  if (const char* e = getenv("NK_CONV_HALO")) if (e[0] == '0') return false;
-  return halo_shape_ok(p) && halo_tile_rows(p) != 0;
-}
-
-template <int BN_, int MI, int STATS>
-static int launch_halo_as(const NkGemmParams& p_in, hipStream_t stream) {
-  NkGemmParams p = p_in;
-  p.k_rotate = k_rotate_on(p.ga.C) ? 1 : 0;          // (channel slabs, not k-steps: 512 input channels and up)
-  auto kern = nk_conv3x3_halo_kernel<BN_, MI, STATS>;
-  nk_optin_lds((const void*)kern, HaloGeom<MI>::template smem<BN_>());
-  const NkGather& g = p.ga;
-  const long tiles = (long)p.halo_nb * ((g.W + CH_TW - 1) / CH_TW) * ((g.H + HaloGeom<MI>::TH - 1) / HaloGeom<MI>::TH) * (p.N / BN_);
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(HaloRing<BN_>::THREADS), HaloGeom<MI>::template smem<BN_>(), stream, p);
-  // <column-tile width, tile rows (MI = 4: 8 rows, MI = 2: 4 rows), statistics epilogue>
-  if (BN_ == 160 && MI == 4) return nk_check_launch(STATS ? "nk_conv3x3_halo_kernel<160,8,stats=1>" : "nk_conv3x3_halo_kernel<160,8,stats=0>");
-  if (BN_ == 160) return nk_check_launch(STATS ? "nk_conv3x3_halo_kernel<160,4,stats=1>" : "nk_conv3x3_halo_kernel<160,4,stats=0>");
-  if (MI == 4) return nk_check_launch(STATS ? "nk_conv3x3_halo_kernel<128,8,stats=1>" : "nk_conv3x3_halo_kernel<128,8,stats=0>");
-  return nk_check_launch(STATS ? "nk_conv3x3_halo_kernel<128,4,stats=1>" : "nk_conv3x3_halo_kernel<128,4,stats=0>");
-}
-template <int STATS>
-static int launch_halo_s(const NkGemmParams& p, hipStream_t stream) {
-  const int th = halo_tile_rows(p);
-  const bool wide = halo_bn(p.N) == 160;
-  if (th == 8) return wide ? launch_halo_as<160, 4, STATS>(p, stream) : launch_halo_as<128, 4, STATS>(p, stream);
-  return wide ? launch_halo_as<160, 2, STATS>(p, stream) : launch_halo_as<128, 2, STATS>(p, stream);
-}
-static int launch_halo(const NkGemmParams& p, hipStream_t stream) {
-  return p.stats_part ? launch_halo_s<1>(p, stream) : launch_halo_s<0>(p, stream);
-}
-// pixel tiles per image of the launch `launch_halo` would make (the statistics epilogue writes one partial row per tile)
-static int halo_tiles_per_image(const NkGemmParams& p) {
-  const int th = halo_tile_rows(p);
-  if (!th) return 0;
-  return ((p.ga.W + CH_TW - 1) / CH_TW) * ((p.ga.H + th - 1) / th);
-}

@@ -24,15 +24,7 @@
 //     sub-block 0 write theirs.
 #pragma once
 
-#define WH_TH 4
-#define WH_TW 32
-#define WH_HS 48                                   // halo slots per row (34 used)
-#define WH_X_BYTES ((WH_TH + 2) * WH_HS * 128)     // 36864
-#define WH_DY_BYTES (WH_TH * WH_TW * 256)          // 32768
-#define WH_STAGE (WH_X_BYTES + WH_DY_BYTES)        // 69632
-#define WH_SMEM (2 * WH_STAGE)                     // 139264
-#define WH_BCO 128
-#define WH_BCI 64
+// (the tile shape, WH_*: gemm_plan.h)
 
 typedef __attribute__((address_space(3))) char* wh_lds;
 typedef __attribute__((address_space(3))) short4_t* wh_lds4;
@@ -200,64 +192,3 @@ __global__ __launch_bounds__(512, 2) void nk_conv3x3_wgrad_halo_kernel(const NkG
   }
 }
 
-// ---- host side -----------------------------------------------------------------------------------------------------------------------
-static bool wgrad_halo_shape_ok(const NkGemmParams& p) {
-  const NkGather& g = p.gb;
-  if (!p.halo_nb || g.KW != 3 || p.N != 9 * g.C || g.rs != 1 || g.ks != 1 || g.div != 1 || g.off_h != -1 || g.off_w != -1) return false;
-  if (g.Ho != g.H || g.Wo != g.W || (g.C % WH_BCI) || (p.M & 7) || p.nbatch || p.ldc != p.N || p.lda != p.M) return false;
-  if (p.K != (long)p.halo_nb * g.H * g.W) return false;
-  // ragged small images (the 26-wide level of a 1216 x 832 bucket) would spend the tile on padding: they keep the gather kernel
-  const long cover = (long)((g.W + WH_TW - 1) / WH_TW) * WH_TW * ((g.H + WH_TH - 1) / WH_TH) * WH_TH;
-  return cover * 100 <= (long)g.H * g.W * 125;
-}
-// pixel-range splits per (co, ci) block: rounds of 256 workgroups at ~3 us per pixel tile against the atomics the splits cost (1.3 TB/s)
-static int wgrad_halo_splits(const NkGemmParams& p, int& per) {
-  const NkGather& g = p.gb;
-  const long T = (long)p.halo_nb * ((g.W + WH_TW - 1) / WH_TW) * ((g.H + WH_TH - 1) / WH_TH);
-  const long nblk = (long)((p.M + WH_BCO - 1) / WH_BCO) * (g.C / WH_BCI);
-  const double dw_bytes = (double)p.M * p.N * 4.0;
-  double best = 1e30;
-  int best_s = 1;
-  for (int s = 1; s <= 64 && s <= T; ++s) {
-    const long tiles = (T + s - 1) / s;
-    const long rounds = (nblk * s + 255) / 256;
-    const double cost = (double)rounds * (tiles * 3.0e-6 + 4.0e-6) + (s > 1 ? s * dw_bytes / 1.3e12 : dw_bytes / 4.0e12);
-    if (cost < best * 0.97) { best = cost; best_s = s; }     // (a larger S must win by 3 %: fewer atomics at a tie)
-  }
-  per = (int)((T + best_s - 1) / best_s);
-  return (int)((T + per - 1) / per);
-}
-// NK_CONV_WGRAD_HALO: 0 = never (A/B runs, tests), 2 = every eligible shape, unset / 1 = by shape.  By shape (tools/bench_conv_wgrad.py,
-// profiles/r04_conv_wgrad.txt, one box, alternating): the kernel wins where the reduction is long -- the 64^2 and 128^2 levels, x1.0-1.8 -- and
-// where the (co, ci) blocks fill the chip without splitting the pixel range (1280 -> 1280 at 32^2: 200 blocks, x1.12); few pixels into a
-// half-empty grid (640 -> 1280 at 32^2: 100 blocks, two splits, as many atomics as products: x0.69) stay with the gather kernel.
-static bool use_wgrad_halo(const NkGemmParams& p, int amode, int bmode, int out_f32) {
-  if (amode != OP_MC || bmode != OP_MCG || !out_f32) return false;
-  int mode = 1;
-  if (const char* e = getenv("NK_CONV_WGRAD_HALO")) mode = atoi(e);
-  if (!mode || !wgrad_halo_shape_ok(p)) return false;
-  if (mode == 2) return true;
-  if (p.M < 64) return false;
-  const long nblk = (long)((p.M + WH_BCO - 1) / WH_BCO) * (p.gb.C / WH_BCI);
-  return p.K >= 16384 || nblk >= 180;
-}
-static int launch_wgrad_halo(NkGemmParams& p, hipStream_t stream) {
-  int per = 0;
-  const int S = wgrad_halo_splits(p, per);
-  const long nblk = (long)((p.M + WH_BCO - 1) / WH_BCO) * (p.gb.C / WH_BCI);
-  // accumulate: 0 = overwrite, 1 = add, 2 = destination known to be zero.  Split pixel ranges meet through atomics and need a zeroed
-  // destination; one range per block stores (or atomically adds to what is there: nobody else touches those elements)
-  if (S > 1 && p.accumulate == 0) {
-    const size_t n = (size_t)p.M * p.N;
-    const unsigned blocks = (unsigned)((n / 4 + 255) / 256 > 2048 ? 2048 : (n / 4 + 255) / 256);
-    hipLaunchKernelGGL(nk_zero_f32_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, (float*)p.C, n);
-    if (p.dbias) hipLaunchKernelGGL(nk_zero_f32_kernel, dim3(1), dim3(256), 0, stream, p.dbias, (size_t)p.M);
-    if (hipGetLastError() != hipSuccess) return NK_ERR_LAUNCH;
-  }
-  p.accumulate = p.accumulate == 1 ? 1 : 0;      // (kernel: 1 = add to what is there; with S > 1 it adds anyway)
-  p.ksplit_len = per;
-  auto kern = p.dbias ? nk_conv3x3_wgrad_halo_kernel<1> : nk_conv3x3_wgrad_halo_kernel<0>;
-  nk_optin_lds((const void*)kern, WH_SMEM);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * S)), dim3(512), WH_SMEM, stream, p);
-  return nk_check_launch(p.dbias ? "nk_conv3x3_wgrad_halo_kernel<bias=1>" : "nk_conv3x3_wgrad_halo_kernel<bias=0>");
-}

@@ -9,15 +9,31 @@ void nk_set_error(const char* file, int line, const char* what) {
   snprintf(g_err, sizeof(g_err), "%s:%d: %s", file, line, what);
 }
 
-// ---- launch log (test hook): while it is on, every nk_check_launch records the name it was given.  Host-only and thread-local: nothing is
-// launched, so it works during graph capture; with it off a launch pays the one flag test below.
+// ---- launch log (test hook): while it is on, every nk_check_launch records the name it was given, and the tile engine (nk_gemm_dispatch) adds
+// the plan of its launch behind the name: `name grid=x,y,z block smem splitk ksplit_len acc zero krot gm chunk` (gemm_plan.h: nk_plan_line).
+// In plan-only mode (3) the tile engine logs name and plan and returns before it touches the GPU: no zero-fill, no workspace, no launch --
+// which kernel a problem gets, and how, can be asked on a machine without one.  Host-only and thread-local: nothing is launched by the
+// hooks, so they work during graph capture; with the log off a launch pays the one flag test below.
 #define NK_LAUNCH_LOG_MAX 64
-static thread_local bool g_log_on = false;
+#define NK_LAUNCH_LOG_TEXT 192
+static thread_local int g_log_mode = 0;
 static thread_local int g_log_n = 0;
-static thread_local const char* g_log[NK_LAUNCH_LOG_MAX];     // the callers pass string literals: the pointers stay valid
+static thread_local const char* g_log[NK_LAUNCH_LOG_MAX];     // string literals of the callers, or rows of g_log_text
+static thread_local char g_log_text[NK_LAUNCH_LOG_MAX][NK_LAUNCH_LOG_TEXT];
+
+int nk_launch_log_mode(void) { return g_log_mode; }
+void nk_launch_log_add(const char* name, const char* text) {
+  if (!g_log_mode) return;
+  if (name && g_log_n < NK_LAUNCH_LOG_MAX) g_log[g_log_n++] = name;
+  if (text && g_log_n < NK_LAUNCH_LOG_MAX) {
+    snprintf(g_log_text[g_log_n], NK_LAUNCH_LOG_TEXT, "%s", text);
+    g_log[g_log_n] = g_log_text[g_log_n];
+    ++g_log_n;
+  }
+}
 
 int nk_check_launch(const char* what) {
-  if (g_log_on && g_log_n < NK_LAUNCH_LOG_MAX) g_log[g_log_n++] = what;
+  if (g_log_mode && g_log_n < NK_LAUNCH_LOG_MAX) g_log[g_log_n++] = what;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     snprintf(g_err, sizeof(g_err), "%s: launch failed: %s", what, hipGetErrorString(e));
@@ -113,15 +129,15 @@ extern "C" int nk_debug_raise_health(void* stream) {
   return nk_check_launch("nk_raise_health_kernel");
 }
 
-// test hooks: mode 1 = log on (and cleared), 2 = cleared, 0 = off (and cleared)
+// test hooks: mode 1 = log on (and cleared), 3 = log on, plan-only (and cleared), 2 = cleared, 0 = off (and cleared)
 extern "C" int nk_debug_launch_log(int mode) {
-  NK_CHECK_ARG(mode >= 0 && mode <= 2);
-  if (mode != 2) g_log_on = mode == 1;
+  NK_CHECK_ARG(mode >= 0 && mode <= 3);
+  if (mode != 2) g_log_mode = mode;
   g_log_n = 0;
   return NK_OK;
 }
-// the names logged by this thread since the last clear, one per line, into buf[cap] (NUL-terminated; names that do not fit are left out);
-// returns how many were logged (at most NK_LAUNCH_LOG_MAX are kept)
+// the lines logged by this thread since the last clear -- a kernel name per launch, and behind a tile-engine launch its plan line -- into
+// buf[cap] (NUL-terminated; lines that do not fit are left out); returns how many were logged (at most NK_LAUNCH_LOG_MAX are kept)
 extern "C" long nk_debug_launch_names(char* buf, long cap) {
   if (!buf || cap <= 0) return -1;
   long at = 0;

@@ -15,13 +15,13 @@
 // ds_read_b128; r-contiguous operands are staged as they lie in memory ([64 k][rows]) and read with
 // gfx950's transposing ds_read_b64_tr_b16, so no operand is ever transposed in HBM.
 //
-// The kernels in this file, all over the same operand loaders, chosen per launch by shape (nk_gemm_dispatch):
+// The kernels in this file, all over the same operand loaders, chosen per launch by shape (nk_gemm_plan in gemm_plan.h, for nk_gemm_dispatch):
 //   nk_gemm_dma_kernel    128x128x64, 8 waves, LDS-DMA (global_load_lds) double buffer, two workgroups per CU: the general kernel
 //   nk_gemm_ring_kernel   the same tile with a 4-stage ring and counted vmcnt for grids of <= one workgroup per CU
 //   nk_gemm_sk_kernel     persistent stream-K over that tile for under-filled bf16-output grids (fix-up through a workspace)
 //   nk_gemm_xl_kernel     256x256x64, 16 waves, one workgroup per CU: large conv-forward grids (gathered A)
 //   nk_gemm_xl2g_kernel   256x256x64, 8 waves in two groups staggered by a barrier, four phases per k-slab: large Linear forward grids
-//   nk_gemm_g2_kernel     (gemm_g2.h) 128x160 / 128x128 two-group staggered ring at one workgroup per CU: the K = 640 / 1280 Linear shapes
+//   nk_gemm_g2p_kernel    (gemm_g2.h) 128x160 / 128x128 two-group staggered ring at one workgroup per CU: the K = 640 / 1280 Linear shapes
 //   nk_conv3x3_halo_kernel (conv_halo.h) 3 x 3 / stride-1 convolutions from an LDS halo tile: each input byte staged once per 9 taps
 //   (variants that lost their A/B -- the register-staged first version, 256x128 "big", the software-pipelined 256x256, other wave shapes --
 //   were removed in round 3; HISTORY.md keeps their measurements)
@@ -32,24 +32,17 @@
 // unfused attention products of the VAE mid block (K10).
 #include "nk_common.h"
 #include "nk_gemm.h"
-#include <stdlib.h>
+#include "gemm_plan.h"      // the launch planner, and the tile-shape constants it shares with the kernels (BM, BN, BK, ...)
 
-#define BM 128
-#define BN 128
-#define BK 64
 #define NTHREADS 256
-#define GROUP_M 8
 #define KC_IMAGE_BYTES (128 * 128)          // [128 rows][64 k] bf16
 #define MC_ROW_BYTES (128 * 2 + 16)         // [64 k][128 r] bf16, rows padded by 16 B
 #define MC_IMAGE_BYTES (BK * MC_ROW_BYTES)  // 17408
 #define OPND_BYTES MC_IMAGE_BYTES           // per-operand slot (max of the two images)
 #define STAGE_BYTES (2 * OPND_BYTES)
-#define CS_LD 132                            // fp32 epilogue staging row stride (floats)
 #define SMEM_BYTES (2 * STAGE_BYTES)        // 69632 >= 128*132*4 = 67584
 
 static_assert(SMEM_BYTES >= BM * CS_LD * 4, "epilogue staging must fit");
-
-enum { OP_KC = 0, OP_KCG = 1, OP_MC = 2, OP_MCT = 3, OP_MCG = 4 };
 
 __device__ __forceinline__ bool is_kc(int mode) { return mode == OP_KC || mode == OP_KCG; }
 
@@ -243,10 +236,6 @@ __device__ __attribute__((aligned(64))) unsigned int nk_zero_page[16];
 
 typedef __attribute__((address_space(1))) const void* nk_gptr;
 typedef __attribute__((address_space(3))) void* nk_lptr;
-
-#define V2_OPND_BYTES 16384
-#define V2_STAGE_BYTES (2 * V2_OPND_BYTES)
-#define V2_SMEM_BYTES (BM * CS_LD * 4)   // 67584: epilogue staging is the larger need (2 stages = 65536)
 
 __device__ __forceinline__ int mc_swz(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 1; }
 
@@ -701,8 +690,6 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void nk_gemm_dma_kernel(const NkGe
 // and raw barriers.  r-contiguous operands are read with ds_read_b64_tr_b16 through inline asm: hipcc would drain vmcnt(0)
 // in front of the builtin whenever an LDS-DMA is outstanding, which here is always.
 // ---------------------------------------------------------------------------------------------
-#define RING_NS 4
-#define RING_SMEM_BYTES (RING_NS * V2_STAGE_BYTES)    // 131072 >= 67584 (epilogue staging)
 
 template <int MODE>
 __device__ __forceinline__ bf16x8_t ring_frag(const char* img, int sub, int ks, int lane) {
@@ -846,10 +833,6 @@ __global__ __launch_bounds__(512, 2) void nk_gemm_ring_kernel(const NkGemmParams
 // slabs in flight in the same LDS.  k-contiguous dense operands, bf16 output with the fused bias / row vector / residual; 8 waves as 2 x 4, 32 x 16
 // per wave.  Column tiles are the slow index of the tile order, so the row tiles that share a weight panel are neighbours on one XCD.
 // ---------------------------------------------------------------------------------------------
-#define R64_NS 8
-#define R64_OPND 8192
-#define R64_STAGE (2 * R64_OPND)
-#define R64_SMEM (R64_NS * R64_STAGE)      // 131072
 #define R64_CS_LD 68
 __global__ __launch_bounds__(512, 2) void nk_gemm_ring64_kernel(const NkGemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -953,22 +936,6 @@ __global__ __launch_bounds__(512, 2) void nk_gemm_ring64_kernel(const NkGemmPara
     }
   }
 }
-// NK_GEMM_R64: 0 = never (A/B runs).  Dense k-contiguous bf16-output launches of at most 512 rows whose 128 x 128 grid would leave most CUs idle.
-static bool use_ring64(const NkGemmParams& p, int amode, int bmode, int out_f32) {
-  if (amode != OP_KC || bmode != OP_KC || out_f32 || p.nbatch || p.geglu_u || p.geglu_h || p.stats_part) return false;
-  if (const char* e = getenv("NK_GEMM_R64")) if (e[0] == '0') return false;
-  if (p.M > 512 || p.K < 4 * BK) return false;
-  // one round at one workgroup per CU (the ring takes 128 KiB of LDS): 308 x 1280 -> 100 tiles, x 3072 -> 240; at 308 x 3840 / 5120 (300 / 400
-  // tiles: two rounds) the 128 x 128 kernels are faster again (16.8 / 17.1 against 19.2 / 19.9 us, tools/bench_skinny.py)
-  const long t64 = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-  return t64 <= 256;
-}
-static int launch_ring64(const NkGemmParams& p, hipStream_t stream) {
-  nk_optin_lds((const void*)nk_gemm_ring64_kernel, R64_SMEM);
-  const unsigned tiles = (unsigned)(((p.M + 63) >> 6) * ((p.N + 63) >> 6));
-  hipLaunchKernelGGL(nk_gemm_ring64_kernel, dim3(tiles), dim3(512), R64_SMEM, stream, p);
-  return nk_check_launch("nk_gemm_ring64_kernel");
-}
 
 // =============================================================================================
 // stream-K main kernel (default).  Measured on the 128x128 data-parallel kernel above: a k-step costs 0.94 us per
@@ -988,9 +955,6 @@ static int launch_ring64(const NkGemmParams& p, hipStream_t stream) {
 //     consumed at the end of the neighbour's.  A waiter only waits for LOWER-indexed workgroups of its own XCD, which the
 //     dispatcher has already handed out; the wait is bounded anyway (a failed launch is flagged, never a hang).
 // =============================================================================================
-#define SK_NT 512
-#define SK_SMEM_BYTES (2 * V2_STAGE_BYTES)
-#define SK_MAX_GRID 512
 #define SK_TILE_FLOATS (BM * BN)
 
 __device__ __forceinline__ void sk_decode(const NkGemmParams& p, int t, int ntm, int ntn, int& m0, int& n0, int& z) {
@@ -1329,10 +1293,6 @@ __global__ __launch_bounds__(SK_NT, 4) void nk_gemm_sk_kernel(const NkGemmParams
 // what bounds the 128 x 128 kernel: half of its 32 B per 1 Ki MAC.  k-contiguous operands, bf16 output.
 // Fragments are read one k sub-step at a time (64 accumulator + 32 fragment registers at 4 waves per SIMD).
 // =============================================================================================
-#define XL_BM 256
-#define XL_BN 256
-#define XL_STAGE_BYTES 65536
-#define XL_SMEM_BYTES (2 * XL_STAGE_BYTES)
 // WM x WN is the per-wave tile: 64 x 64 (16 waves, 4 per SIMD), 128 x 64 (8 waves, 2 per SIMD) or 128 x 128 (4 waves, 1 per SIMD).
 // Larger wave tiles read fewer fragment bytes from LDS per MFMA (0.5 / 0.375 / 0.25 KiB) at the price of fewer waves to hide them.
 template <int AMODE, int WM, int WN>
@@ -1612,117 +1572,62 @@ __global__ __launch_bounds__(512, 2) void nk_gemm_xl2g_kernel(const NkGemmParams
     }
 }
 
-static bool use_xl(const NkGemmParams& p, int amode, int bmode, int out_f32, int splitk);
 __global__ void nk_zero_f32_kernel(float* __restrict__ dst, size_t n);
 #include "gemm_g2.h"
 #include "gemm_w160.h"
 #include "conv_halo.h"
 #include "conv_wgrad_halo.h"
 
-static bool use_xl(const NkGemmParams& p, int amode, int bmode, int out_f32, int splitk) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("NK_GEMM_XL"); on = (e && e[0] == '0') ? 0 : 1; }
-  if (!on || p.nbatch || out_f32 || splitk != 1 || bmode != OP_KC || !(amode == OP_KC || amode == OP_KCG)) return false;
-  const long ntn = (p.N + XL_BN - 1) / XL_BN;
-  const long tiles = (long)((p.M + XL_BM - 1) / XL_BM) * ntn;
-  // at least ~one workgroup per CU, and no more than 12 % of the last column tile wasted (N = 320 / 640 would idle 37 % / 17 %)
-  // ... and rounds of 256 workgroups that are at least 80 % full (320 tiles would run as two rounds at 62 %: measured 775 vs 847 TFLOP/s
-  // against the 128 x 128 kernel's finer rounds)
-  const long rounds = (tiles + 255) / 256;
-  return tiles >= 224 && tiles * 10 >= rounds * 256 * 8 && ntn * XL_BN * 100 <= (long)p.N * 112 && p.K >= 4 * BK;
-}
-template <int AMODE, int WM, int WN>
-static int launch_xl_as(const NkGemmParams& p, hipStream_t stream) {
-  auto kern = nk_gemm_xl_kernel<AMODE, WM, WN>;
-  nk_optin_lds((const void*)kern, XL_SMEM_BYTES);
-  dim3 grid(((p.M + XL_BM - 1) / XL_BM) * ((p.N + XL_BN - 1) / XL_BN), 1, 1);
-  hipLaunchKernelGGL(kern, grid, dim3((XL_BM / WM) * (XL_BN / WN) * 64), XL_SMEM_BYTES, stream, p);
-  return nk_check_launch("nk_gemm_xl_kernel");
-}
-template <int AMODE>
-static int launch_xl(const NkGemmParams& p_in, hipStream_t stream) {
-  // by operand mode: dense k-contiguous A -> the two-group phased kernel (+3..6 % on the Linear shapes); gathered A -> the 16-wave kernel
-  // (the gather's address arithmetic would sit in the phased kernel's read phases, where only one wave per SIMD is there to absorb it:
-  // conv forward 781-785 vs 835-840 TFLOP/s)
-  if (AMODE == OP_KC) {
-    auto kern = nk_gemm_xl2g_kernel<OP_KC, 0>;
-    auto kerng = nk_gemm_xl2g_kernel<OP_KC, 1>;
-    nk_optin_lds((const void*)kern, XL_SMEM_BYTES);
-    nk_optin_lds((const void*)kerng, XL_SMEM_BYTES);
-    NkGemmParams p = p_in;
-    p.k_rotate = k_rotate_on(p.K) ? 1 : 0;
-    dim3 grid(((p.M + XL_BM - 1) / XL_BM) * ((p.N + XL_BN - 1) / XL_BN), 1, 1);
-    if (p.geglu_h) hipLaunchKernelGGL(kerng, grid, dim3(512), XL_SMEM_BYTES, stream, p);
-    else hipLaunchKernelGGL(kern, grid, dim3(512), XL_SMEM_BYTES, stream, p);
-    return nk_check_launch(p.geglu_h ? "nk_gemm_xl2g_kernel<geglu=1>" : "nk_gemm_xl2g_kernel<geglu=0>");
-  }
-  return launch_xl_as<AMODE, 64, 64>(p_in, stream);
+// ---------------------------------------------------------------------------------------------
+// host side: nk_gemm_dispatch = check the arguments, plan (gemm_plan.h), prepare, launch
+// ---------------------------------------------------------------------------------------------
+typedef void (*NkGemmKernel)(const NkGemmParams);
+// every family's launch: the plan has the grid, the block, the LDS bytes and the name
+static int launch_plan(NkGemmKernel kern, const NkGemmPlan& pl, const NkGemmParams& p, hipStream_t stream) {
+  nk_optin_lds((const void*)kern, pl.smem);
+  hipLaunchKernelGGL(kern, dim3(pl.grid[0], pl.grid[1], pl.grid[2]), dim3(pl.block), pl.smem, stream, p);
+  return nk_check_launch(pl.name);
 }
 
-// ---------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------
-template <int AMODE, int BMODE, int OUT_F32>
-static int launch(const NkGemmParams& p_in, int splitk, hipStream_t stream) {
-  NkGemmParams p2 = p_in;
-  const NkGemmParams& p = p2;
-  auto kern8 = nk_gemm_dma_kernel<AMODE, BMODE, OUT_F32, 8>;      // 8 waves per 128 x 128 tile: +4..14 % over 4 waves on every SDXL shape
-  auto kernr = nk_gemm_ring_kernel<AMODE, BMODE, OUT_F32>;
-  nk_optin_lds((const void*)kern8, V2_SMEM_BYTES);
-  nk_optin_lds((const void*)kernr, RING_SMEM_BYTES);
-  int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
-  dim3 grid(ntm * ntn, splitk, p.nbatch ? p.nbatch : 1);
-  {  // patch height: with T tiles over 8 XCDs an XCD runs ~T/8 tiles at a time; a gm x (T/8/gm) patch touches gm + T/8/gm operand
-     // panels, least at gm = sqrt(T/8).  (A fixed 8 gave a 100-tile weight gradient 8 x 1.5 patches: 10 panels per XCD where 7 do.)
-    int per_xcd = (ntm * ntn + 7) / 8, g = 1;
-    while ((g + 1) * (g + 1) <= per_xcd) ++g;
-    p2.group_m = g > GROUP_M ? GROUP_M : g;
-  }
-  p2.k_rotate = k_rotate_on(splitk > 1 ? p.ksplit_len : p.K) ? 1 : 0;      // (nk_gemm_dma_kernel; the ring kernel walks k in order)
-  // under-filled grids (at most one workgroup per CU): the four-stage ring.  (The ring on LARGE grids was measured too: 723 vs 830 TFLOP/s
-  // at 65536 x 1280 x 1280 -- three slabs in flight do not make up for two waves per SIMD meeting at a barrier every k-step.)
-  if (!p.nbatch && (long)ntm * ntn * splitk <= 256) {
-    hipLaunchKernelGGL(kernr, grid, dim3(512), RING_SMEM_BYTES, stream, p);
-    return nk_check_launch("nk_gemm_ring_kernel");
-  }
-  hipLaunchKernelGGL(kern8, grid, dim3(512), V2_SMEM_BYTES, stream, p);
-  return nk_check_launch("nk_gemm_dma_kernel");
+// THE operand-mode ladder: f(Modes<amode, bmode, out_f32>) with the three as compile-time constants, for the six combinations the entry
+// points of ops_gemm.hip use (Linear forward, dgrad, wgrad; convolution forward, dgrad, wgrad)
+template <int A_, int B_, int F32_> struct Modes { static constexpr int A = A_, B = B_, F32 = F32_; };
+template <class Fn>
+static int with_modes(int amode, int bmode, int out_f32, Fn f) {
+#define NK_CASE(A_, B_) \
+  if (amode == A_ && bmode == B_) return out_f32 ? f(Modes<A_, B_, 1>()) : f(Modes<A_, B_, 0>());
+  NK_CASE(OP_KC, OP_KC)
+  NK_CASE(OP_KC, OP_MC)
+  NK_CASE(OP_MC, OP_MC)
+  NK_CASE(OP_KCG, OP_KC)
+  NK_CASE(OP_KCG, OP_MCT)
+  NK_CASE(OP_MC, OP_MCG)
+#undef NK_CASE
+  nk_set_error(__FILE__, __LINE__, "unsupported operand mode combination");
+  return NK_ERR_ARG;
 }
 
+static NkGemmKernel halo_kernel(const NkGemmPlan& pl) {
+  // <column-tile width, MI (4: 8-row tiles, 2: 4-row tiles), statistics epilogue>
+  if (pl.bn == 160) {
+    if (pl.halo_rows == 8) return pl.flag ? nk_conv3x3_halo_kernel<160, 4, 1> : nk_conv3x3_halo_kernel<160, 4, 0>;
+    return pl.flag ? nk_conv3x3_halo_kernel<160, 2, 1> : nk_conv3x3_halo_kernel<160, 2, 0>;
+  }
+  if (pl.halo_rows == 8) return pl.flag ? nk_conv3x3_halo_kernel<128, 4, 1> : nk_conv3x3_halo_kernel<128, 4, 0>;
+  return pl.flag ? nk_conv3x3_halo_kernel<128, 2, 1> : nk_conv3x3_halo_kernel<128, 2, 0>;
+}
 
 // ---- stream-K workspace: one per stream (launches on one stream are ordered; two streams run concurrently) ----
 #include <mutex>
 #include <unordered_map>
 struct SkWorkspace {
-  unsigned* counter = nullptr;
   unsigned* flags = nullptr;
   float* ws = nullptr;
 };
 static std::mutex sk_mutex;
 static std::unordered_map<void*, SkWorkspace> sk_spaces;
 
-// NK_GEMM_SK: 0 = never, 1 = always, 2 = fp32 outputs (weight gradients) only, 3 = by shape, 4 (default) = by shape and
-// bf16 outputs only (weight gradients run on the side stream, where non-persistent grids back-fill the main stream's
-// kernels: measured 203.7 ms/step vs 206.3 without stream-K, 211 with it on every kernel).  By shape:
-// stream-K where the data-parallel grid fills the chip badly or would need split-K, the plain kernel for big grids
-// (measured 5-19 % faster there: its workgroups drift out of phase, the persistent ones load and store in lock-step).
-static bool use_sk(const NkGemmParams& p, int out_f32) {
-  int mode = 4;
-  if (const char* e = getenv("NK_GEMM_SK")) mode = atoi(e);   // read per call: tools/ab_step.py flips it in-process
-  if (mode == 0) return false;
-  if (mode == 1) return true;
-  if (mode == 2) return out_f32 != 0;
-  if (mode == 4 && out_f32) return false;     // by shape, bf16 outputs (main-stream forward / dgrad) only
-  const long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * (p.nbatch ? p.nbatch : 1);
-  const long nk = (p.K + BK - 1) / BK;
-  const long rounds = (tiles + 511) / 512;
-  const double fill = (double)tiles / (double)(rounds * 512);
-  if (tiles >= 1024 && fill >= 0.8) return false;
-  if (tiles >= 512 && fill >= 0.95) return false;
-  return nk >= 24;    // a fix-up costs about as much as 6-8 k-steps
-}
-
-static int sk_prepare(NkGemmParams& p, int grid, hipStream_t stream) {
+static int sk_prepare(NkGemmParams& p, hipStream_t stream) {
   std::lock_guard<std::mutex> lock(sk_mutex);
   SkWorkspace& w = sk_spaces[(void*)stream];
   if (!w.ws) {
@@ -1738,18 +1643,14 @@ static int sk_prepare(NkGemmParams& p, int grid, hipStream_t stream) {
       return NK_ERR_LAUNCH;
     }
     w.ws = (float*)raw;
-    w.flags = (unsigned*)(raw + ws_bytes);
-    w.counter = w.flags + SK_MAX_GRID;         // flags[SK_MAX_GRID + 1] is the timeout mark
+    w.flags = (unsigned*)(raw + ws_bytes);         // flags[SK_MAX_GRID + 1] is the timeout mark
     // zeroed ON THE LAUNCHING STREAM (a null-stream memset is not ordered against a non-blocking stream's kernels)
     if (hipMemsetAsync(w.flags, 0, (SK_MAX_GRID + 64) * sizeof(unsigned), stream) != hipSuccess) return NK_ERR_LAUNCH;
   }
   p.sk_health = nk_health_word();
   if (!p.sk_health) { nk_set_error(__FILE__, __LINE__, "health word allocation failed"); return NK_ERR_LAUNCH; }
-  p.sk_counter = w.counter;
   p.sk_flags = w.flags;
   p.sk_ws = w.ws;
-  p.sk_base = 0;
-  p.sk_epoch = 0;
   return NK_OK;
 }
 
@@ -1774,24 +1675,6 @@ extern "C" int nk_gemm_sk_status(void) {
   return bad;
 }
 
-template <int AMODE, int BMODE, int OUT_F32>
-static int launch_sk(NkGemmParams& p, hipStream_t stream) {
-  auto kern = nk_gemm_sk_kernel<AMODE, BMODE, OUT_F32>;
-  nk_optin_lds((const void*)kern, SK_SMEM_BYTES);
-  const long ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN, nk = (p.K + BK - 1) / BK;
-  const long T = ntm * ntn * (p.nbatch ? p.nbatch : 1), W = T * nk;
-  // persistent grid: two workgroups per CU, at least ~4 k-steps each
-  const int max_grid = SK_MAX_GRID & ~7, min_iters = 4;
-  long grid = (W / min_iters) & ~7l;
-  if (grid > max_grid) grid = max_grid;
-  if (grid < 8) grid = 8;
-  p.sk_chunked = T >= 64;
-  { const char* d = getenv("NK_SK_DEBUG"); p.sk_debug = d ? atoi(d) & 2 : 0; }      // fault injection for tests/test_health_gpu.py
-  if (int e = sk_prepare(p, (int)grid, stream)) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(SK_NT), SK_SMEM_BYTES, stream, p);
-  return nk_check_launch("nk_gemm_sk_kernel");
-}
-
 // zero-fill of a split-K destination (grid-stride, 16 B per lane; n need not be a multiple of 4)
 __global__ __launch_bounds__(256) void nk_zero_f32_kernel(float* __restrict__ dst, size_t n) {
   const size_t n4 = n / 4, stride = (size_t)gridDim.x * 256;
@@ -1800,31 +1683,7 @@ __global__ __launch_bounds__(256) void nk_zero_f32_kernel(float* __restrict__ ds
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) dst[n4 * 4 + threadIdx.x] = 0.f;
 }
 
-static int pick_splitk(int M, int N, int K, int max_split) {
-  // Split K only for grids far below one workgroup per CU.  Each extra split costs M*N*4 bytes of fp32 atomics at the
-  // chip-wide ~1.3 TB/s atomic rate (MI355X_MICROARCH.md), which is 923/K_red of the GEMM's own time per split -- 22 %
-  // per split at a 4096-row reduction -- while under-filled grids are back-filled by the kernels running concurrently
-  // on the other stream (dgrad chain vs weight-gradient stream).
-  int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  int nk = (K + BK - 1) / BK;
-  const int lo = 96, hi = 192;
-  // ... except long reductions into grids that leave half the 512 slots empty (the 128^2- and 64^2-level convolution weight gradients:
-  // 65 536 / 16 384 pixels = 1 024 / 256 k-steps into 135-225 tiles; the 64^2-level Linear ones): the atomics of one extra split are a few
-  // per cent of such a launch and two splits fill the slots -- 65536 x 320 x 5760: 938 -> 587 us, x 8640: 972 -> 617; step -1 ms (round 3)
-  if (tiles >= lo && tiles * 2 <= 512 && nk >= 256 && max_split >= 2) return 2;
-  if (tiles >= lo) return 1;
-  int s = 1;
-  while (s < max_split && tiles * s < hi && nk / (s * 2) >= 8) s *= 2;
-  return s;
-}
-
-static void set_split(NkGemmParams& p, int splitk) {
-  int nk = (p.K + BK - 1) / BK;
-  int per = (nk + splitk - 1) / splitk;
-  p.ksplit_len = per * BK;
-}
-
-// split-K partials are summed with fp32 atomics, which need a zeroed destination (weight gradient and fused bias gradient)
+// split partials are summed with fp32 atomics, which need a zeroed destination (weight gradient and fused bias gradient)
 // (a kernel, not hipMemsetAsync: as a node of a captured hipGraph the memset of a multi-MB buffer was not ordered before the
 // kernel behind it on this ROCm -- replayed weight gradients of the 320/640-channel layers came out as garbage)
 static int zero_split_outputs(const NkGemmParams& p, hipStream_t stream) {
@@ -1841,6 +1700,7 @@ static int zero_split_outputs(const NkGemmParams& p, hipStream_t stream) {
 
 int nk_gemm_dispatch(NkGemmParams& p, int amode, int bmode, int out_f32, int allow_splitk,
                      hipStream_t stream) {
+  // ---- 1. the arguments ----
   NK_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0);
   if (!p.nbatch) NK_CHECK_ARG(((uintptr_t)p.A & 15) == 0 && ((uintptr_t)p.B & 15) == 0 && ((uintptr_t)p.C & 15) == 0);
   for (int z = 0; z < p.nbatch; ++z) NK_CHECK_ARG(((uintptr_t)p.Ab[z] & 15) == 0 && ((uintptr_t)p.Bb[z] & 15) == 0 && ((uintptr_t)p.Cb[z] & 15) == 0);
@@ -1857,121 +1717,85 @@ int nk_gemm_dispatch(NkGemmParams& p, int amode, int bmode, int out_f32, int all
   if (p.fRowsPerBatch.d == 0) p.fRowsPerBatch = make_fastdiv(1);
 
   if (p.dbias || (p.nbatch && p.dbias_b[0])) NK_CHECK_ARG(amode == OP_MC && out_f32);      // weight-gradient launches only
-  if (p.geglu_h) {   // the fused GEGLU forward lives in the 256 x 256 two-group kernel only: the caller asks nk_linear_fwd_geglu_ok first
+  if (p.geglu_h) {
     NK_CHECK_ARG(amode == OP_KC && bmode == OP_KC && !out_f32 && !p.nbatch && (p.N & 255) == 0 && (p.ld_h & 7) == 0 && !p.rowvec && !p.residual && p.alpha == 1.0f);
     NK_CHECK_ARG(((uintptr_t)p.geglu_h & 15) == 0 && (!p.bias || ((uintptr_t)p.bias & 15) == 0));
-    if (!use_xl(p, amode, bmode, out_f32, 1)) {
-      nk_set_error(__FILE__, __LINE__, "fused GEGLU forward on a shape the 256 x 256 kernel does not take (ask nk_linear_fwd_geglu_ok first)");
-      return NK_ERR_ARG;
-    }
-    set_split(p, 1);
-    return launch_xl<OP_KC>(p, stream);
-  }
-  if (p.geglu_u) {   // the fused GEGLU backward lives in the LDS-staged epilogue of the 128 x 128 data-parallel / ring kernels only
+  } else if (p.geglu_u) {
     NK_CHECK_ARG(amode == OP_KC && bmode == OP_MC && !out_f32 && !p.nbatch && (p.N & 7) == 0 && (p.ld_u & 7) == 0 && !p.bias && !p.rowvec && !p.residual);
-    set_split(p, 1);
-    return launch<OP_KC, OP_MC, 0>(p, 1, stream);
   }
-  // 3 x 3 / stride 1 / padding 1 convolutions over whole 64-channel slabs: the halo-tile kernel (conv_halo.h)
-  if (use_halo(p, amode, bmode, out_f32)) return launch_halo(p, stream);
-  // ... and their weight gradients: nine taps from one staged halo per pixel tile (conv_wgrad_halo.h)
-  if (use_wgrad_halo(p, amode, bmode, out_f32)) return launch_wgrad_halo(p, stream);
-  if (p.stats_part) {      // the GroupNorm statistics epilogue exists in the halo-tile kernel only
-    nk_set_error(__FILE__, __LINE__, "statistics epilogue on a convolution the halo-tile kernel does not take (ask nk_conv2d_stats_tiles first)");
+
+  // ---- 2. the plan ----
+  const TileEnv env = tile_env();
+  const NkGemmPlan pl = nk_gemm_plan(p, amode, bmode, out_f32, allow_splitk, env);
+  if (pl.err) {
+    nk_set_error(__FILE__, __LINE__, pl.err);
     return NK_ERR_ARG;
   }
-
-  // Linear weight gradients whose 160-row tiles come out in whole rounds of 256 workgroups (gemm_w160.h), the token range split where the
-  // weight alone is too small a grid (fp32 atomics: zeroed destination, as below)
-  {
-    const W160Plan wp = w160_plan(p, amode, bmode, out_f32, allow_splitk);
-    if (wp.bn) {
-      set_split(p, wp.splitk);
-      if (wp.splitk > 1 && p.accumulate == 0) {
-        NK_CHECK_ARG(p.ldc == p.N);
-        if (int rc = zero_split_outputs(p, stream)) return rc;
-        p.accumulate = 1;
-      } else if (p.accumulate == 2) {
-        p.accumulate = wp.splitk > 1 ? 1 : 0;
-      }
-      p.k_rotate = k_rotate_on(wp.splitk > 1 ? p.ksplit_len : p.K) ? 1 : 0;
-      return wp.bn == 160 ? launch_w160_as<160>(p, wp.splitk, stream) : launch_w160_as<128>(p, wp.splitk, stream);
-    }
-  }
-  // two-group staggered ring at one workgroup per CU (gemm_g2.h): Linear forward / dgrad / wgrad shapes whose 128 x 160 (or
-  // 128 x 128) tiles come out in whole rounds of 256
-  if (use_ring64(p, amode, bmode, out_f32)) return launch_ring64(p, stream);
-  if ((!p.nbatch || p.nbatch <= NK_MAX_BATCH) && use_g2(p, amode, bmode, out_f32, 1) && (g2_mode() == 2 || !use_xl(p, amode, bmode, out_f32, 1))) {
-    if (p.accumulate == 2) p.accumulate = 0;       // no K split here: "destination known zero" means plain stores
-    if (amode == OP_KC && bmode == OP_KC) return out_f32 ? launch_g2<OP_KC, OP_KC, 1>(p, stream) : launch_g2<OP_KC, OP_KC, 0>(p, stream);
-    if (amode == OP_KC && bmode == OP_MC) return out_f32 ? launch_g2<OP_KC, OP_MC, 1>(p, stream) : launch_g2<OP_KC, OP_MC, 0>(p, stream);
-    if (amode == OP_KCG && bmode == OP_KC) return out_f32 ? launch_g2<OP_KCG, OP_KC, 1>(p, stream) : launch_g2<OP_KCG, OP_KC, 0>(p, stream);
-    if (amode == OP_KCG && bmode == OP_MCT) return out_f32 ? launch_g2<OP_KCG, OP_MCT, 1>(p, stream) : launch_g2<OP_KCG, OP_MCT, 0>(p, stream);
-    return out_f32 ? launch_g2<OP_MC, OP_MC, 1>(p, stream) : launch_g2<OP_MC, OP_MC, 0>(p, stream);
+  if (pl.zero_c) NK_CHECK_ARG(p.ldc == p.N);      // the zero-fill takes the destination as one contiguous range
+  const int logging = nk_launch_log_mode();
+  char line[192];
+  if (logging) nk_plan_line(pl, line, sizeof(line));
+  if (logging == 3) {      // plan-only (test hook): the plan is the answer, the GPU is not touched
+    nk_launch_log_add(pl.name, line);
+    return NK_OK;
   }
 
-  // (a launch that carries a fused bias gradient never goes to stream-K, whatever NK_GEMM_SK says: that kernel has no ones-MFMA row sum,
-  // and the gradient would silently stay unwritten)
-  bool has_dbias = p.dbias != nullptr;
-  for (int z = 0; z < p.nbatch && z < NK_MAX_BATCH; ++z) has_dbias = has_dbias || p.dbias_b[z] != nullptr;
-  if (!has_dbias && use_sk(p, out_f32)) {
-    const long ntm_ = (p.M + BM - 1) / BM, ntn_ = (p.N + BN - 1) / BN, nk_ = (p.K + BK - 1) / BK;
-    if (ntm_ * ntn_ * (p.nbatch ? p.nbatch : 1) * nk_ < (1l << 22)) {   // share arithmetic is 32-bit: W * grid < 2^31
-      if (p.accumulate == 2) p.accumulate = 0;     // "destination known zero" only matters to the atomic split-K path
-#define NK_SK_CASE(A_, B_)                                                        \
-      if (amode == A_ && bmode == B_) return out_f32 ? launch_sk<A_, B_, 1>(p, stream) : launch_sk<A_, B_, 0>(p, stream);
-      NK_SK_CASE(OP_KC, OP_KC)
-      NK_SK_CASE(OP_KC, OP_MC)
-      NK_SK_CASE(OP_MC, OP_MC)
-      NK_SK_CASE(OP_KCG, OP_KC)
-      NK_SK_CASE(OP_KCG, OP_MCT)
-      NK_SK_CASE(OP_MC, OP_MCG)
-#undef NK_SK_CASE
-    }
-  }
-  int splitk = 1;
-  if (out_f32 && allow_splitk) splitk = pick_splitk(p.M * (p.nbatch ? p.nbatch : 1), p.N, p.K, 32);
-  if (p.nbatch) NK_CHECK_ARG(p.nbatch <= NK_MAX_BATCH);
-  set_split(p, splitk);
-  // accumulate: 0 = overwrite, 1 = add, 2 = the destination is known to be zero (flat gradient buffer right after
-  // zero_grad): plain stores when there is a single K split, atomics otherwise -- and no memset either way
-  if (out_f32 && splitk > 1 && p.accumulate == 0) {
-    // split-K partials are summed with fp32 atomics, which need a zeroed destination
-    NK_CHECK_ARG(p.ldc == p.N);
+  // ---- 3. prepare ----
+  p.ksplit_len = pl.ksplit_len; p.accumulate = pl.accumulate; p.k_rotate = pl.k_rotate; p.group_m = pl.group_m; p.sk_chunked = pl.sk_chunked;
+  if (pl.zero_c)
     if (int rc = zero_split_outputs(p, stream)) return rc;
-    p.accumulate = 1;
-  } else if (p.accumulate == 2) {
-    p.accumulate = splitk > 1 ? 1 : 0;
+  if (pl.family == NK_FAM_SK) {
+    p.sk_debug = env.sk_debug;
+    if (int rc = sk_prepare(p, stream)) return rc;
   }
 
-  if (use_xl(p, amode, bmode, out_f32, splitk))
-    return amode == OP_KC ? launch_xl<OP_KC>(p, stream) : launch_xl<OP_KCG>(p, stream);
-
-#define NK_CASE(A_, B_)                                                          \
-  if (amode == A_ && bmode == B_) {                                              \
-    return out_f32 ? launch<A_, B_, 1>(p, splitk, stream) : launch<A_, B_, 0>(p, splitk, stream); \
+  // ---- 4. launch ----
+  int rc;
+  switch (pl.family) {
+    case NK_FAM_HALO: rc = launch_plan(halo_kernel(pl), pl, p, stream); break;
+    case NK_FAM_WGRAD_HALO: rc = launch_plan(pl.flag ? nk_conv3x3_wgrad_halo_kernel<1> : nk_conv3x3_wgrad_halo_kernel<0>, pl, p, stream); break;
+    case NK_FAM_W160: rc = launch_plan(pl.bn == 160 ? nk_gemm_w160_kernel<160> : nk_gemm_w160_kernel<128>, pl, p, stream); break;
+    case NK_FAM_RING64: rc = launch_plan(nk_gemm_ring64_kernel, pl, p, stream); break;
+    case NK_FAM_XL: rc = launch_plan(nk_gemm_xl_kernel<OP_KCG, 64, 64>, pl, p, stream); break;
+    case NK_FAM_XL2G: rc = launch_plan(pl.flag ? nk_gemm_xl2g_kernel<OP_KC, 1> : nk_gemm_xl2g_kernel<OP_KC, 0>, pl, p, stream); break;
+    case NK_FAM_G2P:
+      rc = with_modes(amode, bmode, out_f32, [&](auto m) {
+        using M = decltype(m);
+        if constexpr (M::B == OP_MCG) return (int)NK_ERR_ARG;      // (use_g2 never takes the gathered weight gradient)
+        else return launch_plan(pl.bn == 160 ? nk_gemm_g2p_kernel<M::A, M::B, M::F32, 160> : nk_gemm_g2p_kernel<M::A, M::B, M::F32, 128>, pl, p, stream);
+      });
+      break;
+    case NK_FAM_SK:
+      rc = with_modes(amode, bmode, out_f32, [&](auto m) { using M = decltype(m); return launch_plan(nk_gemm_sk_kernel<M::A, M::B, M::F32>, pl, p, stream); });
+      break;
+    case NK_FAM_RING:
+      rc = with_modes(amode, bmode, out_f32, [&](auto m) { using M = decltype(m); return launch_plan(nk_gemm_ring_kernel<M::A, M::B, M::F32>, pl, p, stream); });
+      break;
+    case NK_FAM_DMA:
+      rc = with_modes(amode, bmode, out_f32, [&](auto m) { using M = decltype(m); return launch_plan(nk_gemm_dma_kernel<M::A, M::B, M::F32, 8>, pl, p, stream); });
+      break;
+    default:
+      nk_set_error(__FILE__, __LINE__, "the plan names no kernel");
+      return NK_ERR_ARG;
   }
-  NK_CASE(OP_KC, OP_KC)
-  NK_CASE(OP_KC, OP_MC)
-  NK_CASE(OP_MC, OP_MC)
-  NK_CASE(OP_KCG, OP_KC)
-  NK_CASE(OP_KCG, OP_MCT)
-  NK_CASE(OP_MC, OP_MCG)
-#undef NK_CASE
-  nk_set_error(__FILE__, __LINE__, "unsupported operand mode combination");
-  return NK_ERR_ARG;
+  if (logging) nk_launch_log_add(nullptr, line);
+  return rc;
 }
 
-// pixel tiles per image of the halo-tile launch this convolution would get (= rows per image of the statistics epilogue's partials);
-// 0 when it is not eligible (shape, NK_CONV_HALO=0)
-int nk_halo_bn(int N) { return halo_bn(N); }
-int nk_halo_tiles_per_image(const NkGemmParams& p) {
-  if (!use_halo(p, OP_KCG, OP_KC, 0)) return 0;
-  return halo_tiles_per_image(p);
+// ---- side queries: what the dispatch WOULD do, from the same plan ----
+// pixel tiles per image of the halo-tile launch this convolution would get (= rows per image of the statistics epilogue's partials), and
+// that launch's column-tile width; 0 when its plan is not the halo kernel (shape, NK_CONV_HALO=0)
+int nk_halo_tiles_per_image(const NkGemmParams& p, int* bn) {
+  const NkGemmPlan pl = nk_gemm_plan(p, OP_KCG, OP_KC, 0, 0, tile_env());
+  if (pl.err || pl.family != NK_FAM_HALO) return 0;
+  if (bn) *bn = pl.bn;
+  return pl.tiles_per_image;
 }
 
-
-// 1 when nk_linear_fwd_geglu takes this FeedForward projection (the 256 x 256 two-group kernel's shape rule, whole 256-column tiles)
+// 1 when nk_linear_fwd_geglu takes this FeedForward projection: its plan is the 256 x 256 two-group kernel with the GEGLU epilogue (whole
+// 256-column tiles)
 int nk_geglu_fwd_fusable(const NkGemmParams& p) {
-  return (p.N & 255) == 0 && use_xl(p, OP_KC, OP_KC, 0, 1) ? 1 : 0;
+  if (p.N & 255) return 0;
+  const NkGemmPlan pl = nk_gemm_plan(p, OP_KC, OP_KC, 0, 0, tile_env());
+  return !pl.err && pl.family == NK_FAM_XL2G && pl.flag ? 1 : 0;
 }

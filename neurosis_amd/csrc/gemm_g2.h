@@ -30,7 +30,6 @@
 // Linear forward (KC x KC), dgrad (KC x MC) and wgrad (MC x MC, also the batched form); convolutions keep the gather kernels.
 #pragma once
 
-#define G2_BM 128
 // Diagnostic build only (make EXTRA=-DNK_G2_STAMPS; tools/g2_stamps.py): wave 0 of every workgroup stamps s_memtime at entry, after the
 // prologue, after the k loop and after the epilogue, plus s_memrealtime around the loop (the clock the chip holds: cdna guide section 7).
 // In the shipped library none of this exists.
@@ -42,11 +41,9 @@ __device__ unsigned long long nk_g2_stamp_buf[8 * 4096];
 #define G2_STAMP(slot)
 #define G2_STAMP_RT(slot)
 #endif
-#define G2_STAGE_BYTES 36864                     // A image 16 KiB + B image up to 20 KiB
-#define G2_NS 4
-#define G2_SMEM_BYTES (G2_NS * G2_STAGE_BYTES)   // 147456
+// (G2_BM, G2_NS, G2_STAGE_BYTES, G2_SMEM_BYTES: gemm_plan.h)
 
-// one operand of the tile: ROWS rows (128 for A; 128 or 160 for B), staged by NSW waves (all 8 of nk_gemm_g2_kernel, the 4 producer waves of
+// one operand of the tile: ROWS rows (128 for A; 128 or 160 for B), staged by NSW waves (the 4 producer waves of
 // nk_gemm_g2p_kernel): piece pc = wave + NSW i
 template <int MODE, int ROWS, int NSW = 8>
 struct OpG2 {
@@ -329,147 +326,6 @@ __device__ __forceinline__ void reg_epilogue_col16(const NkGemmParams& p, void* 
   reg_epilogue_col16<OUT_F32, MI>(p, Cv, acc, mbase, nbase, lane, mlimit, none, false);
 }
 
-template <int AMODE, int BMODE, int OUT_F32, int BN_>
-__global__ __launch_bounds__(512, 2) void nk_gemm_g2_kernel(const NkGemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int HN = BN_ / 2, NJ = HN / 16;          // columns per group; 16-column blocks per wave: 4 or 5
-  const int tid = threadIdx.x, lane = tid & 63;
-  G2_STAMP(0);
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = wave >> 2, wq = wave & 3;
-
-  // XCD-aware bijective remap + grouped tile order (4 x ntn patches: with 8 column tiles of 160 an XCD's 32 workgroups
-  // share 4 A panels and the whole of B)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int ntn = (p.N + BN_ - 1) / BN_, ntm = (p.M + G2_BM - 1) / G2_BM;
-  constexpr int GM = 4;
-  const int per_group = GM * ntn;
-  const int group = wg / per_group;
-  const int first_m = group * GM;
-  const int gm = min(GM, ntm - first_m);
-  const int in_group = wg - group * per_group;
-  const int nt = in_group / gm;
-  const int m0 = (first_m + (in_group - nt * gm)) * G2_BM, n0 = nt * BN_;
-  const int nk = (p.K + BK - 1) / BK;
-  const bf16_t* Ap = p.nbatch ? p.Ab[blockIdx.z] : p.A;
-  const bf16_t* Bp = p.nbatch ? p.Bb[blockIdx.z] : p.B;
-  void* Cp = p.nbatch ? p.Cb[blockIdx.z] : p.C;
-
-  constexpr int AF = (AMODE == OP_KC || AMODE == OP_KCG) ? OP_KC : OP_MC;               // the LDS image: the gathers stage the dense layouts
-  constexpr int BF = (BMODE == OP_KC || BMODE == OP_KCG) ? OP_KC : OP_MC;
-  OpG2<AMODE, 128> oa;
-  OpG2<BMODE, BN_> ob;
-  oa.init(Ap, p.lda, p.M, m0, wave, lane, &p.ga, &p.tw);
-  ob.init(Bp, p.ldb, p.N, n0, wave, lane, &p.gb, &p.tw);
-  if (p.k_rotate) { oa.rotate(nk, (xcd * nk) >> 3); ob.rotate(nk, (xcd * nk) >> 3); }
-  typedef __attribute__((address_space(3))) const char* lds_c;
-  const unsigned lds0 = (unsigned)(size_t)(lds_c)smem;
-  FragG2<AF, 128, 2> fa;
-  FragG2<BF, BN_, NJ> fb;
-  fa.init(lds0, wq * 32, lane);
-  fb.init(lds0 + 16384u, grp * HN, lane);
-
-  float4_t acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = (float4_t){0.f, 0.f, 0.f, 0.f};
-  bf16x8_t af[4], bfr[2 * NJ];
-  // bias gradient of a weight-gradient launch (see nk_gemm_dma_kernel): the two column groups hold the same 32 rows per row quarter;
-  // group g sums the 16-row block g.  Swapped operands: the row is on lane & 15, every register of the result holds its sum.
-  constexpr bool CAN_BIAS = AMODE == OP_MC && OUT_F32 == 1;
-  float* const dbias = CAN_BIAS ? (p.nbatch ? p.dbias_b[blockIdx.z] : p.dbias) : nullptr;
-  const bool do_bias = CAN_BIAS && dbias != nullptr && nt == 0;
-  float4_t accb = (float4_t){0.f, 0.f, 0.f, 0.f};
-
-#define G2_BAR() __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0)
-  // this wave's pieces per slab: 4 (BN 128) or 5 / 4 (BN 160, waves 0-3 / 4-7) -- the counted wait leaves exactly one slab in flight
-  const bool five = ob.pieces(wave) + oa.pieces(wave) == 5;
-#define G2_WAIT_ONE_SLAB()                                            \
-  do {                                                                \
-    if (five) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");        \
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");             \
-  } while (0)
-
-  const bf16_t* sa[OpG2<AMODE, 128>::NPW];
-  const bf16_t* sb[OpG2<BMODE, BN_>::NPW];
-  // prologue: slabs 0 and 1 in flight, slab 0 landed for everyone
-  oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);
-  oa.fire(sa, smem, wave); ob.fire(sb, smem + 16384, wave);
-  oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);
-  oa.fire(sa, smem + G2_STAGE_BYTES, wave); ob.fire(sb, smem + G2_STAGE_BYTES + 16384, wave);
-  oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);             // sources of slab 2, fired in the first R phase
-  G2_WAIT_ONE_SLAB();
-  G2_BAR();
-  if (grp == 1) { G2_BAR(); }                                       // the second group runs one barrier behind
-
-  G2_STAMP(1); G2_STAMP_RT(4);
-  unsigned so = 0, sn = 2 * G2_STAGE_BYTES;                         // stage of slab t / of slab t + 2
-  for (int t = 0; t < nk; ++t) {
-    // ---- R: fragment reads of slab t, DMA of slab t + 2, wait for slab t + 1 ----
-    __builtin_amdgcn_sched_barrier(0);
-    g2_read<BF, BN_, NJ>(bfr, fb, so);
-    g2_read<AF, 128, 2>(af, fa, so);
-    oa.fire(sa, smem + sn, wave);                        // the two A pieces here, the two or three B pieces behind the barrier, in the
-    asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // all but the two A pieces just issued: slab t + 1 is complete (this wave's share)
-    G2_BAR();
-    // ---- M: the wave's MFMAs; the next slab's source addresses are computed in their shadow ----
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-    ob.fire(sb, smem + sn + 16384, wave);      // (all five pieces in the R phase instead: 1237 vs 1117 cycles per k-step, tools/g2_stamps.py, round 4)
-    oa.next_sources(p.K, sa);
-    ob.next_sources(p.K, sb);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)     // operands swapped (D = B.A^T): a lane holds 4 consecutive COLUMNS of one row
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ks * NJ + j], af[ks * 2 + i], acc[i][j], 0, 0, 0);
-    if constexpr (CAN_BIAS) {
-      if (do_bias) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)     // (grp is wave-uniform: a select between two compile-time fragments, not an indexed array)
-          accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nk_ones_frag(), grp ? af[ks * 2 + 1] : af[ks * 2], accb, 0, 0, 0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-    G2_BAR();
-    so += G2_STAGE_BYTES; if (so == G2_NS * G2_STAGE_BYTES) so = 0;
-    sn += G2_STAGE_BYTES; if (sn == G2_NS * G2_STAGE_BYTES) sn = 0;
-  }
-  if (grp == 0) { G2_BAR(); }                                       // ... and the first group waits for it here
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the past-the-end zero-page pieces must land before the LDS is given up
-  G2_STAMP(2); G2_STAMP_RT(5);
-#undef G2_BAR
-#undef G2_WAIT_ONE_SLAB
-
-  const int mb = m0 + wq * 32, nb = n0 + grp * HN;
-  if constexpr (CAN_BIAS) {
-    if (do_bias && lane < 16) {
-      const int m = mb + grp * 16 + lane;
-      if (m < p.M) dbias[m] = p.accumulate ? dbias[m] + accb[0] * p.alpha : accb[0] * p.alpha;       // (no K split in this kernel)
-    }
-  }
-#pragma unroll
-  for (int half = 0; half < NJ / 2; ++half) {
-    float4_t pair[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { pair[i][0] = acc[i][2 * half]; pair[i][1] = acc[i][2 * half + 1]; }
-    reg_epilogue_64x32<OUT_F32, 2>(p, Cp, pair, mb, nb + half * 32, lane);
-  }
-  if constexpr (NJ & 1) {
-    float4_t last[2] = {acc[0][NJ - 1], acc[1][NJ - 1]};
-    reg_epilogue_col16<OUT_F32, 2>(p, Cp, last, mb, nb + (NJ - 1) * 16, lane);
-  }
-#ifdef NK_G2_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  G2_STAMP(3);
-#endif
-}
 #ifdef NK_G2_STAMPS
 extern "C" int nk_debug_g2_stamps(unsigned long long* host_out, int nwg) {
   return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(nk_g2_stamp_buf), (size_t)nwg * 8 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
@@ -543,8 +399,9 @@ struct LeanSrcG2 {
   }
 };
 
-// ---- producer-wave variant (round 4, this session) ---------------------------------------------------------------------------------
-// What the loop above waits for (tools/g2_stamps.py: 1 117 cycles per k-step at 4096 x 1280 x 1280 against an MFMA floor of 640): a wave
+// ---- the kernel: compute waves and producer waves (round 4) ---------------------------------------------------------------------------
+// In the first form of this kernel (removed; profiles/r04_g2p_vs_g2.txt has the A/B) every wave staged its own pieces in its R phase, as the
+// header describes.  What that loop waited for (tools/g2_stamps.py: 1 117 cycles per k-step at 4096 x 1280 x 1280 against an MFMA floor of 640): a wave
 // issues IN ORDER, and an LDS-DMA instruction does not issue until the 64 B / clk / CU fill path takes it.  A slab is 36 KiB = 562 cycles of
 // that path, so the 4-5 pieces of a wave cost it ~280 cycles of stalled issue per k-step on top of its fragment reads (~220): an R phase of
 // ~560 cycles against the 320 of the other group's M phase, twice per k-step = the 1 117 measured (attn512.h met the same wall: ~960 of the
@@ -560,8 +417,11 @@ __global__ __launch_bounds__(768, 1) void nk_gemm_g2p_kernel(const NkGemmParams 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int HN = BN_ / 2, NJ = HN / 16;          // columns per group; 16-column blocks per wave: 4 or 5
   const int tid = threadIdx.x, lane = tid & 63;
+  G2_STAMP(0);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
+  // XCD-aware bijective remap + grouped tile order (4 x ntn patches: with 8 column tiles of 160 an XCD's 32 workgroups
+  // share 4 A panels and the whole of B)
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
   const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
@@ -583,67 +443,66 @@ __global__ __launch_bounds__(768, 1) void nk_gemm_g2p_kernel(const NkGemmParams 
   if (wave >= 8) {
     // ================= producer: the tile DMA of all 128 + BN_ rows, pieces pw + 4 i =================
     const int pw = wave - 8;
-    if constexpr ((AMODE == OP_KC || AMODE == OP_MC) && (BMODE == OP_KC || BMODE == OP_MC)) {
-      if (p.lean_src) {     // NK_GEMM_LEAN (default 1): dense operands through LeanSrcG2
-        LeanSrcG2<AMODE, 128, 4> la;
-        LeanSrcG2<BMODE, BN_, 4> lb;
-        const int s0 = p.k_rotate ? (xcd * nk) >> 3 : 0;
-        la.init(Ap, p.lda, p.M, m0, pw, lane, p.K, s0);
-        lb.init(Bp, p.ldb, p.N, n0, pw, lane, p.K, s0);
-        constexpr int PPS = LeanSrcG2<AMODE, 128, 4>::NPW + LeanSrcG2<BMODE, BN_, 4>::NPW;
-        la.fire_next(smem, pw); lb.fire_next(smem + 16384, pw);
-        la.fire_next(smem + G2_STAGE_BYTES, pw); lb.fire_next(smem + G2_STAGE_BYTES + 16384, pw);
-        if constexpr (PPS == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // slab 0 landed
-        G2_BAR();
-        unsigned sn = 2 * G2_STAGE_BYTES;                                // stage of slab t + 2
-        for (int t = 0; t < nk; ++t) {
-          la.fire_next(smem + sn, pw);
-          G2_BAR();                                                      // 2t
-          lb.fire_next(smem + sn + 16384, pw);
-          if constexpr (PPS == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // slab t + 1 landed
-          G2_BAR();                                                      // 2t + 1
-          sn += G2_STAGE_BYTES; if (sn == G2_NS * G2_STAGE_BYTES) sn = 0;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        G2_BAR();
-        return;
+    if constexpr ((AMODE == OP_KC || AMODE == OP_MC) && (BMODE == OP_KC || BMODE == OP_MC)) {      // dense operands: LeanSrcG2
+      LeanSrcG2<AMODE, 128, 4> la;
+      LeanSrcG2<BMODE, BN_, 4> lb;
+      const int s0 = p.k_rotate ? (xcd * nk) >> 3 : 0;
+      la.init(Ap, p.lda, p.M, m0, pw, lane, p.K, s0);
+      lb.init(Bp, p.ldb, p.N, n0, pw, lane, p.K, s0);
+      constexpr int PPS = LeanSrcG2<AMODE, 128, 4>::NPW + LeanSrcG2<BMODE, BN_, 4>::NPW;
+      la.fire_next(smem, pw); lb.fire_next(smem + 16384, pw);
+      la.fire_next(smem + G2_STAGE_BYTES, pw); lb.fire_next(smem + G2_STAGE_BYTES + 16384, pw);
+      if constexpr (PPS == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // slab 0 landed
+      G2_BAR();
+      unsigned sn = 2 * G2_STAGE_BYTES;                                // stage of slab t + 2
+      for (int t = 0; t < nk; ++t) {
+        la.fire_next(smem + sn, pw);
+        G2_BAR();                                                      // 2t
+        lb.fire_next(smem + sn + 16384, pw);
+        if constexpr (PPS == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // slab t + 1 landed
+        G2_BAR();                                                      // 2t + 1
+        sn += G2_STAGE_BYTES; if (sn == G2_NS * G2_STAGE_BYTES) sn = 0;
       }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      G2_BAR();
+      return;
+    } else {      // the gather modes: OpG2::next_sources
+      OpG2<AMODE, 128, 4> oa;
+      OpG2<BMODE, BN_, 4> ob;
+      oa.init(Ap, p.lda, p.M, m0, pw, lane, &p.ga, &p.tw);
+      ob.init(Bp, p.ldb, p.N, n0, pw, lane, &p.gb, &p.tw);
+      if (p.k_rotate) { oa.rotate(nk, (xcd * nk) >> 3); ob.rotate(nk, (xcd * nk) >> 3); }
+      static_assert(OpG2<AMODE, 128, 4>::NPC % 4 == 0 && OpG2<BMODE, BN_, 4>::NPC % 4 == 0, "every producer issues the same number of pieces");
+      constexpr int PPS = OpG2<AMODE, 128, 4>::NPW + OpG2<BMODE, BN_, 4>::NPW;      // pieces per slab and producer: 8 or 9
+      const bf16_t* sa[OpG2<AMODE, 128, 4>::NPW];
+      const bf16_t* sb[OpG2<BMODE, BN_, 4>::NPW];
+      oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);
+      oa.fire(sa, smem, pw); ob.fire(sb, smem + 16384, pw);
+      oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);
+      oa.fire(sa, smem + G2_STAGE_BYTES, pw); ob.fire(sb, smem + G2_STAGE_BYTES + 16384, pw);
+      oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);             // sources of slab 2
+      if constexpr (PPS == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // slab 0 landed
+      G2_BAR();
+      unsigned sn = 2 * G2_STAGE_BYTES;                                // stage of slab t + 2
+      for (int t = 0; t < nk; ++t) {
+        // (the A pieces in front of barrier 2t, the B pieces behind it: 36 KiB are ~560 cycles of the fill path, and all of them in one half k-step
+        // made that half as long -- the compute waves wait at the barrier for the producers)
+        oa.fire(sa, smem + sn, pw);
+        oa.next_sources(p.K, sa);
+        G2_BAR();                                                      // 2t
+        ob.fire(sb, smem + sn + 16384, pw);
+        ob.next_sources(p.K, sb);
+        if constexpr (PPS == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // slab t + 1 landed
+        G2_BAR();                                                      // 2t + 1
+        sn += G2_STAGE_BYTES; if (sn == G2_NS * G2_STAGE_BYTES) sn = 0;
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the past-the-end zero-page pieces land before this wave gives up
+      G2_BAR();
+      return;
     }
-    OpG2<AMODE, 128, 4> oa;
-    OpG2<BMODE, BN_, 4> ob;
-    oa.init(Ap, p.lda, p.M, m0, pw, lane, &p.ga, &p.tw);
-    ob.init(Bp, p.ldb, p.N, n0, pw, lane, &p.gb, &p.tw);
-    if (p.k_rotate) { oa.rotate(nk, (xcd * nk) >> 3); ob.rotate(nk, (xcd * nk) >> 3); }
-    static_assert(OpG2<AMODE, 128, 4>::NPC % 4 == 0 && OpG2<BMODE, BN_, 4>::NPC % 4 == 0, "every producer issues the same number of pieces");
-    constexpr int PPS = OpG2<AMODE, 128, 4>::NPW + OpG2<BMODE, BN_, 4>::NPW;      // pieces per slab and producer: 8 or 9
-    const bf16_t* sa[OpG2<AMODE, 128, 4>::NPW];
-    const bf16_t* sb[OpG2<BMODE, BN_, 4>::NPW];
-    oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);
-    oa.fire(sa, smem, pw); ob.fire(sb, smem + 16384, pw);
-    oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);
-    oa.fire(sa, smem + G2_STAGE_BYTES, pw); ob.fire(sb, smem + G2_STAGE_BYTES + 16384, pw);
-    oa.next_sources(p.K, sa); ob.next_sources(p.K, sb);             // sources of slab 2
-    if constexpr (PPS == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // slab 0 landed
-    G2_BAR();
-    unsigned sn = 2 * G2_STAGE_BYTES;                                // stage of slab t + 2
-    for (int t = 0; t < nk; ++t) {
-      // (the A pieces in front of barrier 2t, the B pieces behind it: 36 KiB are ~560 cycles of the fill path, and all of them in one half k-step
-      // made that half as long -- the compute waves wait at the barrier for the producers)
-      oa.fire(sa, smem + sn, pw);
-      oa.next_sources(p.K, sa);
-      G2_BAR();                                                      // 2t
-      ob.fire(sb, smem + sn + 16384, pw);
-      ob.next_sources(p.K, sb);
-      if constexpr (PPS == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // slab t + 1 landed
-      G2_BAR();                                                      // 2t + 1
-      sn += G2_STAGE_BYTES; if (sn == G2_NS * G2_STAGE_BYTES) sn = 0;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the past-the-end zero-page pieces land before this wave gives up
-    G2_BAR();
-    return;
   }
 
-  // ================= compute: nk_gemm_g2_kernel's two groups without any staging =================
+  // ================= compute: the two groups, without any staging =================
   const int grp = wave >> 2, wq = wave & 3;
   constexpr int AF = (AMODE == OP_KC || AMODE == OP_KCG) ? OP_KC : OP_MC;
   constexpr int BF = (BMODE == OP_KC || BMODE == OP_KCG) ? OP_KC : OP_MC;
@@ -681,6 +540,7 @@ __global__ __launch_bounds__(768, 1) void nk_gemm_g2p_kernel(const NkGemmParams 
 
   G2_BAR();
   if (grp == 1) { G2_BAR(); }                                       // the second group runs one barrier behind
+  G2_STAMP(1); G2_STAMP_RT(4);
   unsigned so = 0;
   for (int t = 0; t < nk; ++t) {
     // ---- R: fragment reads of slab t ----
@@ -715,6 +575,7 @@ __global__ __launch_bounds__(768, 1) void nk_gemm_g2p_kernel(const NkGemmParams 
     so += G2_STAGE_BYTES; if (so == G2_NS * G2_STAGE_BYTES) so = 0;
   }
   if (grp == 0) { G2_BAR(); }
+  G2_STAMP(2); G2_STAMP_RT(5);
 #undef G2_BAR
 
   if constexpr (CAN_BIAS) {
@@ -734,82 +595,9 @@ __global__ __launch_bounds__(768, 1) void nk_gemm_g2p_kernel(const NkGemmParams 
     float4_t last[2] = {acc[0][NJ - 1], acc[1][NJ - 1]};
     reg_epilogue_col16<OUT_F32, 2>(p, Cp, last, mb, nb + (NJ - 1) * 16, lane, -1, pre_r16, pre);
   }
+#ifdef NK_G2_STAMPS
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  G2_STAMP(3);
+#endif
 }
 
-// NK_GEMM_G2P: 1 (default) = the producer-wave variant wherever the two-group kernel is selected; 0 = nk_gemm_g2_kernel (A/B runs)
-static bool g2p_enabled() {
-  const char* e = getenv("NK_GEMM_G2P");
-  return !e || atoi(e) != 0;
-}
-
-// NK_GEMM_G2: 0 = never; 1 (default) = by shape; 2 = every eligible launch (A/B runs)
-static int g2_mode() {
-  int mode = 1;
-  if (const char* e = getenv("NK_GEMM_G2")) mode = atoi(e);     // read per call: tools flip it in-process
-  return mode;
-}
-// tile width for this N: 160 when it divides N (1280, 640, 1920, 3840, 5120, 10240 ...), else 128 when that wastes little
-static int g2_bn(int N) {
-  if (N % 160 == 0) return 160;
-  const int ntn = (N + 127) / 128;
-  return (long)ntn * 128 * 100 <= (long)N * 112 ? 128 : 0;
-}
-static bool use_g2(const NkGemmParams& p, int amode, int bmode, int out_f32, int splitk) {
-  const int mode = g2_mode();
-  if (!mode || splitk != 1) return false;
-  const bool conv = amode == OP_KCG;
-  if (conv) {   // the gather modes decode the tap once per slab: channels in whole 64-deep slabs, full slabs only
-    if (p.ga.C % 64 || p.K % 64) return false;
-    if (bmode == OP_MCT && p.tw.fCout.d % 64) return false;
-  }
-  if (!((amode == OP_KC && bmode == OP_KC) || (amode == OP_KC && bmode == OP_MC) || (amode == OP_MC && bmode == OP_MC) ||
-        (conv && (bmode == OP_KC || bmode == OP_MCT))))
-    return false;
-  if (p.K < 2 * BK) return false;
-  // not the SINGLE weight gradients: in the two-stream step they do better with the co-resident 128 x 128 kernels (187.6 vs 189.0 ms);
-  // the batched ones (three 1280 x 1280 per launch = 240 tiles, one round) do better here: 49.7 vs 65.4 us alone, 177.2 vs 177.6 ms/step
-  if (amode == OP_MC && bmode == OP_MC && !p.nbatch) return false;      // (round 4, with the producer-wave kernel: 158.0 / 157.9 vs 158.0 / 158.9 ms per step -- still nothing)
-  const int bn = g2_bn(p.N);
-  if (!bn) return false;
-  if (mode == 2) return true;
-  // By shape (tools/bench_g2.py, interleaved A/B on the SDXL Linear shapes).  The kernel wins where its tiles come out in ONE or
-  // TWO whole rounds of 256 (one workgroup per CU: 4096 x 1280 -> 256 tiles, 16384 x 640 -> 512, 3840 x 1280 -> 240, three batched
-  // 1280 x 1280 weight gradients -> 240) -- forward +12..29 %, dgrad +5..27 %, wgrad +32..35 % -- and where K is long enough (>= 40
-  // slabs) to amortise a tile's prologue and epilogue over up to four rounds.  It loses where many short rounds follow each other
-  // (at one workgroup per CU nothing overlaps a tile's epilogue: 16384 x 1280 x 640 forward 0.87x, 65536 x 1280 x 1280 0.67x) and
-  // against the 256 x 256 two-group kernel on the shapes that one takes (4096 x 3840 / 10240 x 1280 forward 0.76-0.80x).
-  const long tiles = (long)((p.M + G2_BM - 1) / G2_BM) * ((p.N + bn - 1) / bn) * (p.nbatch ? p.nbatch : 1);
-  const long rounds = (tiles + 255) / 256;
-  const double fill = (double)tiles / (double)(rounds * 256);
-  const long nk = (p.K + BK - 1) / BK;
-  if (fill < 0.85) return false;
-  return rounds <= 2 || (rounds <= 4 && nk >= 40);
-}
-
-// NK_GEMM_KROT: 1 (default) = rotated k order per XCD (OpG2::rotate; the two-group, 128 x 128 double-buffer and 256 x 256 two-group kernels) in launches of at least eight slabs; 0 = every XCD starts at k = 0 (A/B runs)
-static bool k_rotate_on(int k_len) {
-  const char* e = getenv("NK_GEMM_KROT");
-  return (!e || atoi(e) != 0) && (k_len + BK - 1) / BK >= 8;
-}
-
-template <int AMODE, int BMODE, int OUT_F32, int BN_>
-static int launch_g2_as(const NkGemmParams& p_in, hipStream_t stream) {
-  NkGemmParams p = p_in;
-  p.k_rotate = k_rotate_on(p.K) ? 1 : 0;
-  dim3 grid(((p.M + G2_BM - 1) / G2_BM) * ((p.N + BN_ - 1) / BN_), 1, p.nbatch ? p.nbatch : 1);
-  if (g2p_enabled()) {
-    { const char* e = getenv("NK_GEMM_LEAN"); p.lean_src = (!e || atoi(e) != 0) ? 1 : 0; }
-    auto kp = nk_gemm_g2p_kernel<AMODE, BMODE, OUT_F32, BN_>;
-    nk_optin_lds((const void*)kp, G2_SMEM_BYTES);
-    hipLaunchKernelGGL(kp, grid, dim3(768), G2_SMEM_BYTES, stream, p);
-    return nk_check_launch(BN_ == 160 ? "nk_gemm_g2p_kernel<160>" : "nk_gemm_g2p_kernel<128>");
-  }
-  auto kern = nk_gemm_g2_kernel<AMODE, BMODE, OUT_F32, BN_>;
-  nk_optin_lds((const void*)kern, G2_SMEM_BYTES);
-  hipLaunchKernelGGL(kern, grid, dim3(512), G2_SMEM_BYTES, stream, p);
-  return nk_check_launch(BN_ == 160 ? "nk_gemm_g2_kernel<160>" : "nk_gemm_g2_kernel<128>");
-}
-template <int AMODE, int BMODE, int OUT_F32>
-static int launch_g2(const NkGemmParams& p, hipStream_t stream) {
-  return g2_bn(p.N) == 160 ? launch_g2_as<AMODE, BMODE, OUT_F32, 160>(p, stream) : launch_g2_as<AMODE, BMODE, OUT_F32, 128>(p, stream);
-}

@@ -30,8 +30,7 @@
 //   * rotated k order per XCD (OpG2::rotate), XCD-aware tile order, fp32 epilogue through permlane16_swap (32-byte runs per lane).
 #pragma once
 
-#define W160_BM 160
-#define W160_NS 3
+// (W160_BM, W160_NS: gemm_plan.h)
 // Diagnostic build only (make EXTRA=-DNK_W160_STAMPS; tools/w160_stamps.py).  Per workgroup, compute wave 0: s_memtime at entry, behind barrier 0,
 // behind the k loop, behind the epilogue (+ s_memrealtime around the loop: the clock held); producer wave 4: cycles spent issuing DMA, waiting on
 // vmcnt and waiting at the slab barrier, summed over the loop.  None of it exists in the shipped library.
@@ -60,6 +59,7 @@ struct W160Cfg {
   static constexpr int STAGE = A_BYTES + B_BYTES;             // 40960 / 36864
   static constexpr int SMEM = W160_NS * STAGE;                // 122880 / 110592
   static constexpr int NRD = 2 * (NJ + 5);                    // transposing reads per sub-step and wave: 20 / 18
+  static_assert(SMEM == w160_smem(BN_), "the planner's LDS size");
 };
 
 #define W160_RDTR(dst, addr, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF))
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(512, 1) void nk_gemm_w160_kernel(const NkGemmParams
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   W160_STAMP(0);
 
-  // XCD-aware bijective remap + grouped tile order (nk_gemm_g2_kernel's): an XCD's consecutive tiles share GM dy panels and walk the x panels
+  // XCD-aware bijective remap + grouped tile order (nk_gemm_g2p_kernel's): an XCD's consecutive tiles share GM dy panels and walk the x panels
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
   const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
@@ -421,51 +421,3 @@ extern "C" int nk_debug_w160_stamps(unsigned long long* host_out, int nwg) {
 }
 #endif
 
-// NK_GEMM_W160: 0 = never; 1 (default) = by shape; 2 = every eligible launch (tests: ragged shapes, K splits)
-static int w160_mode() {
-  int mode = 1;
-  if (const char* e = getenv("NK_GEMM_W160")) mode = atoi(e);     // read per call: tools and tests flip it in-process
-  return mode;
-}
-struct W160Plan { int bn, splitk; };
-// tile width and token split for this weight gradient, {0, 0} when the kernel does not take it
-static W160Plan w160_plan(const NkGemmParams& p, int amode, int bmode, int out_f32, int allow_splitk) {
-  const int mode = w160_mode();
-  if (!mode || amode != OP_MC || bmode != OP_MC || !out_f32) return {0, 0};
-  if (p.nbatch > NK_MAX_BATCH) return {0, 0};
-  const int nb = p.nbatch ? p.nbatch : 1;
-  const long nk = (p.K + BK - 1) / BK;
-  if (mode == 2) {      // tests: everything, split when asked to by a second variable
-    int sk = 1;
-    if (const char* e = getenv("NK_GEMM_W160_SPLIT")) sk = atoi(e);
-    if (sk < 1 || !allow_splitk || nk < 2 * sk) sk = 1;
-    return {p.N % 160 == 0 || p.N % 128 != 0 ? 160 : 128, sk};
-  }
-  if (p.M % W160_BM) return {0, 0};                        // rows of the weight in whole 160-row tiles (every 640 / 1280-level Linear)
-  if (nk < 32) return {0, 0};                              // (the 308-token context projections stay where they are)
-  W160Plan best = {0, 0};
-  double best_us = 1e30;
-  for (int bn = 160; bn >= 128; bn -= 32) {
-    const long ntn = (p.N + bn - 1) / bn;
-    if (ntn * bn * 100 > (long)p.N * 104) continue;        // at most 4 % of a column tile wasted
-    const long tiles = (long)(p.M / W160_BM) * ntn * nb;
-    for (int sk = 1; sk <= 8; ++sk) {
-      if (sk > 1 && (!allow_splitk || nk / sk < 32)) break;
-      const long wgs = tiles * sk, rounds = (wgs + 255) / 256;
-      if ((double)wgs < 0.85 * (double)(rounds * 256)) continue;
-      // calibrated on tools/bench_w160.py (round 6): a 160 x 160 tile takes ~0.66 us per 64-token slab at the clock the chip holds under this
-      // load; the atomics of a split launch all arrive at its end (one round: nothing left to hide them behind) at ~0.6 TB/s
-      const double us = (double)rounds * (double)((nk + sk - 1) / sk) * 0.66 * bn / 160.0 + (sk > 1 ? sk * (double)p.M * p.N * nb * 4.0 / 0.6e6 : 0.0);
-      if (us < best_us) { best_us = us; best = {bn, sk}; }
-    }
-  }
-  return best;
-}
-template <int BN_>
-static int launch_w160_as(NkGemmParams& p, int splitk, hipStream_t stream) {
-  auto kern = nk_gemm_w160_kernel<BN_>;
-  nk_optin_lds((const void*)kern, W160Cfg<BN_>::SMEM);
-  dim3 grid(((p.M + W160_BM - 1) / W160_BM) * ((p.N + BN_ - 1) / BN_), splitk, p.nbatch ? p.nbatch : 1);
-  hipLaunchKernelGGL(kern, grid, dim3(512), W160Cfg<BN_>::SMEM, stream, p);
-  return nk_check_launch(BN_ == 160 ? "nk_gemm_w160_kernel<160>" : "nk_gemm_w160_kernel<128>");
-}

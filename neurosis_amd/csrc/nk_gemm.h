@@ -32,30 +32,27 @@ struct NkGemmParams {
   void* C;
   long ldc;
   float alpha;
+  int sk_debug;             // stream-K, NK_SK_DEBUG=2 (fault injection): every fix-up wait gives up at once -- tests the fail-closed path
   const float* bias;        // [N] fp32, optional
   const bf16_t* residual;   // [M][ldr] bf16, optional
   long ldr;
   const bf16_t* rowvec;     // [batch][ld_rowvec] bf16 broadcast over the rows of one batch item, optional
   long ld_rowvec;
   FastDiv fRowsPerBatch;
+  // ksplit_len .. k_rotate: set by nk_gemm_dispatch from the launch plan (gemm_plan.h)
   int ksplit_len;
-  int group_m;              // rows of the XCD-local tile patch (nk_gemm_dma_kernel / nk_gemm_ring_kernel), set by the launcher
+  int group_m;              // rows of the XCD-local tile patch (nk_gemm_dma_kernel / nk_gemm_ring_kernel)
   int accumulate;           // fp32 output: 0 = store, 1 = atomic add
-  int lean_src;             // producer-wave two-group kernel: dense operands through LeanSrcG2 (gemm_g2.h), set by the launcher
-  int k_rotate;             // two-group kernels: XCD x starts its k loop x / 8 of the way through K and wraps (OpG2::rotate), set by the launcher
+  int sk_chunked;           // stream-K: 1 = each XCD owns a contiguous eighth of the tile list
+  int k_rotate;             // two-group kernels: XCD x starts its k loop x / 8 of the way through K and wraps (OpG2::rotate)
   // batched launch: blockIdx.z selects one of nbatch (<= NK_MAX_BATCH) problems of identical shape
   int nbatch;
   const bf16_t* Ab[8];
   const bf16_t* Bb[8];
   void* Cb[8];
   // stream-K (nk_gemm_sk_kernel): per-stream workspace owned by the dispatcher
-  unsigned* sk_counter;     // (unused)
-  unsigned sk_base;         // (unused)
   unsigned* sk_flags;       // [grid] flag[ticket] = 1 while that workgroup's partial tile waits in sk_ws; its one reader lowers it
-  unsigned sk_epoch;        // (unused: no per-launch state, so a launch replayed from a hipGraph is a fresh one)
   float* sk_ws;             // [grid][128*128] fp32 partial tiles in accumulator-register order
-  int sk_chunked;           // 1: each XCD owns a contiguous eighth of the tile list
-  int sk_debug;             // NK_SK_DEBUG=2 (fault injection): every fix-up wait gives up at once -- tests the fail-closed path
   unsigned* sk_health;      // backward-health word (errors.hip): raised when a fix-up wait gives up
   // weight-gradient launches (A = dy, r-contiguous): the bias gradient dbias[m] (+)= sum_k A(m, k), accumulated by the first column tile of
   // every row block with one extra MFMA per row block and k sub-step against a fragment of ones (the dy panel is already in registers)
@@ -85,6 +82,6 @@ struct NkGemmParams {
 enum { NK_OP_KC = 0, NK_OP_KCG = 1, NK_OP_MC = 2, NK_OP_MCT = 3, NK_OP_MCG = 4 };
 
 int nk_gemm_dispatch(NkGemmParams& p, int amode, int bmode, int out_f32, int allow_splitk, hipStream_t stream);
-int nk_halo_tiles_per_image(const NkGemmParams& p);
-int nk_halo_bn(int N);        // column-tile width of the halo-tile launch (conv_halo.h: halo_bn)
+// side queries, answered from the plan nk_gemm_dispatch would make (gemm_plan.h)
+int nk_halo_tiles_per_image(const NkGemmParams& p, int* bn);      // 0: not the halo-tile kernel; *bn: the launch's column-tile width
 int nk_geglu_fwd_fusable(const NkGemmParams& p);

@@ -226,13 +226,14 @@ extern "C" int nk_conv2d_fwd(const NkConvDesc* d, const void* x, const void* w, 
 extern "C" long nk_conv2d_stats_tiles(const NkConvDesc* d, int stats_groups) {
   if (check_conv(d)) return 0;
   if (stats_groups < 0 || stats_groups > 32) return 0;
-  if (stats_groups) {
-    if (d->Cout % stats_groups) return 0;
-    const int bn = nk_halo_bn(d->Cout), cpg = d->Cout / stats_groups;
-    if (bn % cpg) return 0;               // a column tile must hold whole groups
-  }
   NkGemmParams p = conv_fwd_params(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  return nk_halo_tiles_per_image(p);
+  int bn = 0;
+  const int tiles = nk_halo_tiles_per_image(p, &bn);
+  if (tiles && stats_groups) {
+    if (d->Cout % stats_groups) return 0;
+    if (bn % (d->Cout / stats_groups)) return 0;               // a column tile must hold whole groups
+  }
+  return tiles;
 }
 
 extern "C" int nk_conv2d_fwd_stats(const NkConvDesc* d, const void* x, const void* w, const float* bias, const void* rowvec,
@@ -282,7 +283,7 @@ extern "C" long nk_conv2d_dgrad_flipped_ok(const NkConvDesc* d) {
   NkConvDesc t = *d;
   t.H = Hin; t.W = Win; t.Cin = d->Cout; t.Cout = d->Cin; t.upsample = 0;
   NkGemmParams p = conv_fwd_params(&t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  return nk_halo_tiles_per_image(p) > 0;
+  return nk_halo_tiles_per_image(p, nullptr) > 0;
 }
 
 extern "C" int nk_conv2d_dgrad_flipped(const NkConvDesc* d, const void* dy, const void* wt, void* dx, void* stream) {

@@ -1,4 +1,4 @@
-"""Bit-for-bit checks of the MFMA tile engine (csrc/gemm.hip, gemm_g2.h, gemm_w160.h, conv_halo.h, conv_wgrad_halo.h) on integer inputs.
+"""Bit-for-bit checks of the MFMA tile engine (csrc/gemm.hip, gemm_plan.h, gemm_g2.h, gemm_w160.h, conv_halo.h, conv_wgrad_halo.h) on integer inputs.
 
 Why exact.  Operands are small integers (exact in bf16), so every product and every partial sum of a GEMM / convolution is an integer below
 2^24 and therefore exact in fp32: the result does not depend on the order of summation at all -- not on the k rotation per XCD, the split-K
@@ -27,7 +27,7 @@ import torch.nn.functional as F
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "neurosis_amd" / "csrc"
-ENGINE_SOURCES = ("gemm.hip", "gemm_g2.h", "gemm_w160.h", "conv_halo.h", "conv_wgrad_halo.h")
+ENGINE_SOURCES = ("gemm.hip", "gemm_plan.h", "gemm_g2.h", "gemm_w160.h", "conv_halo.h", "conv_wgrad_halo.h")
 EXACT_LIMIT = 2 ** 24       # integers of smaller magnitude are exact in fp32, and so are their sums while they stay below it
 ADD_RANGE = 256             # biases, row vectors, residuals, pre-filled destinations: uniform integers in [-256, 256] (exact in bf16)
 SENTINEL = 2.0 ** 100       # exact in bf16 and fp32; no exact result (|.| < 2^24) can equal it
@@ -38,8 +38,9 @@ U32 = 2.0 ** -23            # unit of the derived bound: whether the bf16 MFMA's
 
 # ---- what the library can launch -----------------------------------------------------------------------------------------------------------
 def launch_literals() -> list[str]:
-    """Every kernel name a launch site of the tile engine reports: the string literals inside nk_check_launch(...) in its five sources."""
-    names = []
+    """Every kernel name a launch of the tile engine reports: the launchers pass the plan's name to nk_check_launch, and the planner
+    (gemm_plan.h) is where the names are written -- its kernel-name string literals, plus any literal still inside a nk_check_launch(...)."""
+    names = re.findall(r'"(nk_\w+_kernel(?:<[^">]*>)?)"', (CSRC / "gemm_plan.h").read_text())
     for f in ENGINE_SOURCES:
         for call in re.findall(r"nk_check_launch\((.*?)\);", (CSRC / f).read_text(), flags=re.S):
             names += re.findall(r'"([^"]+)"', call)
@@ -51,7 +52,7 @@ TILES = {
     "nk_gemm_ring64_kernel": (64, 64), "nk_gemm_xl_kernel": (256, 256), "nk_gemm_xl2g_kernel<geglu=0>": (256, 256),
     "nk_gemm_xl2g_kernel<geglu=1>": (256, 256), "nk_gemm_ring_kernel": (128, 128), "nk_gemm_dma_kernel": (128, 128),
     "nk_gemm_sk_kernel": (128, 128), "nk_gemm_g2p_kernel<160>": (128, 160), "nk_gemm_g2p_kernel<128>": (128, 128),
-    "nk_gemm_g2_kernel<160>": (128, 160), "nk_gemm_g2_kernel<128>": (128, 128), "nk_gemm_w160_kernel<160>": (160, 160),
+    "nk_gemm_w160_kernel<160>": (160, 160),
     "nk_gemm_w160_kernel<128>": (160, 128),
     # halo tiles are patches of 8 / 4 image rows x 32 pixels: in the [pixels][channels] output only the column tile is a contiguous range
     "nk_conv3x3_halo_kernel<160,8,stats=0>": (256, 160), "nk_conv3x3_halo_kernel<160,8,stats=1>": (256, 160),
@@ -91,7 +92,7 @@ def _c(id, op, dims, expect, env="", r=8, guard="cols", why_rows="", graph=False
 
 CONV_LD = "the convolution entry points fix ldc to the channel count"
 SPLIT_LD = "split partials meet through atomics on a destination the launcher zeroes: it insists on ldc == N"
-G2P160, G2P128, G2_160, G2_128 = "nk_gemm_g2p_kernel<160>", "nk_gemm_g2p_kernel<128>", "nk_gemm_g2_kernel<160>", "nk_gemm_g2_kernel<128>"
+G2P160, G2P128 = "nk_gemm_g2p_kernel<160>", "nk_gemm_g2p_kernel<128>"
 XL2G, XL, SK, RING, DMA, R64 = "nk_gemm_xl2g_kernel<geglu=0>", "nk_gemm_xl_kernel", "nk_gemm_sk_kernel", "nk_gemm_ring_kernel", "nk_gemm_dma_kernel", "nk_gemm_ring64_kernel"
 W160, W128 = "nk_gemm_w160_kernel<160>", "nk_gemm_w160_kernel<128>"
 WH0, WH1 = "nk_conv3x3_wgrad_halo_kernel<bias=0>", "nk_conv3x3_wgrad_halo_kernel<bias=1>"
@@ -114,10 +115,6 @@ def _table():
         _c("fwd-g2p128-vae-attn-512", "fwd", (16384, 512, 512), G2P128, bias=1, residual=1),
         _c("fwd-g2p128-ragged", "fwd", (4000, 1000, 328), G2P128, env="NK_GEMM_G2=2", residual=1),
         _c("fwd-g2p128-ragged-scalar-stores", "fwd", (520, 1001, 200), G2P128, env="NK_GEMM_G2=2", bias=1, residual=1),
-        _c("fwd-g2-160-no-producer-wave", "fwd", (4096, 1280, 1280), G2_160, env="NK_GEMM_G2P=0", bias=1, residual=1),
-        _c("fwd-g2-160-no-producer-wave-krot0", "fwd", (4096, 1280, 1280), G2_160, env="NK_GEMM_G2P=0 NK_GEMM_KROT=0", bias=1),
-        _c("fwd-g2-128-no-producer-wave-ragged", "fwd", (4000, 1000, 328), G2_128, env="NK_GEMM_G2=2 NK_GEMM_G2P=0", bias=1),
-        _c("fwd-g2-160-no-producer-wave-ragged", "fwd", (1000, 160, 136), G2_160, env="NK_GEMM_G2=2 NK_GEMM_G2P=0", residual=1),
         _c("fwd-xl2g-ff-proj-4096x10240x1280", "fwd", (4096, 10240, 1280), XL2G, bias=1),
         _c("fwd-xl2g-krot0", "fwd", (4096, 10240, 1280), XL2G, env="NK_GEMM_KROT=0", bias=1),
         # the FeedForward projection with the GEGLU in its epilogue: u = x w^T + bias is exact and checked here; h = a gelu(g) is not (GELU) and
@@ -141,8 +138,6 @@ def _table():
         _c("dgrad-g2p160-1280", "dgrad", (4096, 1280, 1280), G2P160, add=1, graph=True),
         _c("dgrad-g2p160-krot0", "dgrad", (4096, 1280, 1280), G2P160, env="NK_GEMM_KROT=0", add=1),
         _c("dgrad-g2p128-ragged", "dgrad", (4000, 1000, 328), G2P128, env="NK_GEMM_G2=2", add=1),
-        _c("dgrad-g2-160-no-producer-wave-ragged", "dgrad", (1000, 160, 136), G2_160, env="NK_GEMM_G2=2 NK_GEMM_G2P=0"),
-        _c("dgrad-g2-160-no-producer-wave-1280", "dgrad", (4096, 1280, 1280), G2_160, env="NK_GEMM_G2P=0", add=1),
         _c("dgrad-sk-4096x640x2560", "dgrad", (4096, 640, 2560), SK, add=1),
         _c("dgrad-sk-ragged", "dgrad", (1000, 328, 200), SK, env="NK_GEMM_SK=1", add=1),
         _c("dgrad-ring-4096x640x640", "dgrad", (4096, 640, 640), RING, add=1),
@@ -555,7 +550,7 @@ def environment(pairs):
 
 
 def wgrad_halo_splits(c: Case) -> int:
-    """Pixel-range splits of the halo-tile weight gradient: the cost rule of conv_wgrad_halo.h (wgrad_halo_splits), restated -- the launch name
+    """Pixel-range splits of the halo-tile weight gradient: the cost rule of gemm_plan.h (wgrad_halo_splits), restated -- the launch name
     does not carry the number, and the cases mean "one" or "several"."""
     N, H, W, Cin, Cout = c.dims[:5]
     T = N * (-(-W // 32)) * (-(-H // 4))

@@ -218,12 +218,14 @@ def test_planted_fault_is_caught(fault):
 
 # ---- the hooks -------------------------------------------------------------------------------------------------------------------------------
 def test_launch_log_hooks_are_host_only():
-    """On, empty, off -- without a device: the hooks touch no GPU state (which is what lets them run during graph capture)."""
+    """On, empty, plan-only, off -- without a device: the hooks touch no GPU state (which is what lets them run during graph capture)."""
     from neurosis_amd import lib
 
     lib.launch_log(1)
     assert lib.launched() == []
     lib.launch_log(2)
+    lib.launch_log(3)
+    assert lib.launched() == []
     lib.launch_log(0)
     with pytest.raises(lib.NkError):
-        lib.launch_log(3)
+        lib.launch_log(4)
