@@ -256,6 +256,19 @@ int nk_geglu_bwd_s(const void* dy, const void* s, void* du, long M, int I, void*
 int nk_silu_fwd(const void* x, void* y, long n, void* stream);
 int nk_silu_bwd(const void* dy, const void* x, void* dx, long n, void* stream);
 
+/* nn.Dropout of the training path (openaimodel.py:284 ResBlock.out_layers; modules/attention.py:69 FeedForward.net[1], :210 to_out[1];
+ * modules/diffusion/model.py:106,125 ResnetBlock.dropout): y = x * mask * scale (+ residual) on bf16 rows, in place allowed (y == x).  The mask
+ * is never stored: Philox4x32-10, one call per 8 consecutive LOGICAL elements e = row * cols + col (the row strides play no part, so one
+ * mask over [rows, cols] can be laid over a column half of a wider buffer), counter (e / 8 low, e / 8 high, site, step low word), key
+ * (seed low, seed high); element j = e % 8 takes the 16-bit half (word[j >> 1] >> 16 (j & 1)) & 0xffff and is kept iff half >= thr.
+ * thr = round(p * 65536) and scale = 1 / (1 - p) come from the host.  kept: y = bf16(fmul_rn(x, scale)), dropped: +0; with a residual
+ * y = bf16(fadd_rn(residual, that fp32 value)).  {seed, step} are two 64-bit words READ FROM DEVICE MEMORY at `token` (a captured launch
+ * sees a new mask on every replay).  The backward is the same call on dy.  cols % 8 == 0, 16-byte-aligned rows. */
+int nk_dropout(const void* x, const void* residual, void* y, long rows, int cols, long ld_x, long ld_res, long ld_y, const void* token,
+               int site, int thr, float scale, void* stream);
+/* one draw: state = {seed, step} (two 64-bit words, one persistent allocation per device): step += 1; token = {seed, step} */
+int nk_dropout_draw(void* state, void* token, void* stream);
+
 /* out = a + b on flat bf16 arrays: gradient join where one tensor feeds two consumers (skip connections,
  * openaimodel.py:832-836) */
 int nk_add(const void* a, const void* b, void* out, long n, void* stream);

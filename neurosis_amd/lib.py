@@ -99,6 +99,8 @@ SIGNATURES: dict[str, list] = {
     "nk_batchnorm_eval": [vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, f32, vp],
     "nk_silu_bwd": [vp, vp, vp, i64, vp],
     "nk_add": [vp, vp, vp, i64, vp],
+    "nk_dropout": [vp, vp, vp, i64, i32, i64, i64, i64, vp, i32, i32, f32, vp],
+    "nk_dropout_draw": [vp, vp, vp],
     "nk_cat_channels": [vp, vp, vp, i64, i32, i32, vp],
     "nk_split_channels": [vp, vp, vp, i64, i32, i32, vp],
     "nk_upsample2x_bwd": [vp, vp, i32, i32, i32, i32, vp],

@@ -50,8 +50,7 @@ class FeedForward(nn.Module):
 
     def __init__(self, dim: int, dim_out: Optional[int] = None, mult: int = 4, glu: bool = False, dropout: float = 0.0):
         super().__init__()
-        if dropout != 0.0:
-            raise NotImplementedError("dropout > 0 is not on the SDXL training path (configs use 0.0)")
+        self.dropout_p = ops.check_dropout_rate(dropout, "FeedForward")
         inner_dim = int(dim * mult)
         dim_out = dim_out or dim
         if not glu:
@@ -60,22 +59,39 @@ class FeedForward(nn.Module):
 
     def fwd(self, x: Tensor, residual: Optional[Tensor] = None, x_saved=None, recompute_h: bool = False):
         """x_saved / recompute_h (selective recompute, BasicTransformerBlock.recompute): the projection's input is rebuilt by `x_saved()` and
-        the GEGLU product h = a * gelu(g) from the kept projection output u when the weight gradients need them; neither is held."""
+        the GEGLU product h = a * gelu(g) from the kept projection output u when the weight gradients need them; neither is held.
+
+        Dropout (training, rate > 0) sits between the GEGLU and net[2] and keeps both fused epilogues.  With m' = mask / (1 - p) over [M, I]:
+        h is multiplied by m' in place, and so is what the backward's epilogue reads -- BOTH halves of s = [gelu(g) | a gelu'(g)] (its products
+        d s1 m' and d s2 m' are then d/da and d/dg of (a gelu(g) m') . d), or, in the u = [a | g] form, the a half alone: the g half of the
+        fused backward, d a m' gelu'(g), comes out right by itself, its a half d gelu(g) takes m' afterwards, and h rebuilt from the masked u
+        is already masked (bf16(a m') gelu(g): it differs from the forward's bf16(a gelu(g)) m' by one rounding)."""
         proj = self.net[0].proj
+        p = self.dropout_p if self.training else 0.0
         # round 6: unless h must be rebuilt from u in backward (selective recompute), the projection's epilogue keeps the saved-derivative
         # form s = [gelu(g) | a gelu'(g)] instead of u = [a | g]: the backward's epilogue is then two products per element
         save_s = not recompute_h and ops.geglu_save_enabled()
         u, g, b_proj = ops.linear_geglu_fwd(x, proj.weight, proj.bias, x_saved, save_derivative=save_s)     # the GEGLU rides in the projection's epilogue where it can
+        if p > 0.0:
+            inner, site, tok = g.shape[1], ops.dropout_site(self), ops.dropout_token()
+            ops.dropout_mask_like(g, p, site, tok)
+            ops.dropout_mask_like(u[:, :inner], p, site, tok)
+            if save_s:
+                ops.dropout_mask_like(u[:, inner:], p, site, tok)
         y, b_out = linear_module_fwd(self.net[2], g, residual, x_saved=(lambda: ops.geglu_fwd(u)[0]) if recompute_h else None)
         del g
 
         def bwd(dy: Tensor):
             # net[2]'s input gradient with the GEGLU backward in its epilogue: one launch, d(a * gelu(g)) never goes to HBM
-            return b_proj(b_out(dy, geglu_s=u) if save_s else b_out(dy, geglu_u=u))
+            du = b_out(dy, geglu_s=u) if save_s else b_out(dy, geglu_u=u)
+            if p > 0.0 and not save_s:
+                ops.dropout_mask_like(du[:, :inner], p, site, tok)
+            return b_proj(du)
 
         return y, bwd
 
     def forward(self, x: Tensor) -> Tensor:
+        ops.dropout_open(self)
         return _token_module_forward(self, x)
 
 
@@ -95,8 +111,7 @@ class CrossAttention(nn.Module):
 
     def __init__(self, query_dim: int, context_dim: Optional[int] = None, heads: int = 8, dim_head: int = 64, dropout: float = 0.0, backend=None, **kwargs):
         super().__init__()
-        if dropout != 0.0:
-            raise NotImplementedError("attention dropout > 0 is not on the SDXL training path")
+        self.dropout_p = ops.check_dropout_rate(dropout, "CrossAttention")
         inner_dim = dim_head * heads
         context_dim = context_dim or query_dim
         self.heads, self.dim_head = heads, dim_head
@@ -104,6 +119,16 @@ class CrossAttention(nn.Module):
         self.to_k = nn.Linear(context_dim, inner_dim, bias=False)
         self.to_v = nn.Linear(context_dim, inner_dim, bias=False)
         self.to_out = nn.Sequential(nn.Linear(inner_dim, query_dim), nn.Dropout(dropout))
+
+    def _out_fwd(self, o: Tensor, residual: Optional[Tensor]):
+        """to_out = [Linear, Dropout] (+ the block's residual).  Without dropout the residual rides in the Linear's epilogue; with it the Linear
+        runs bare and nk_dropout adds the residual behind the mask, in place.  bwd(dy) -> do (dy itself also feeds the residual branch: a new buffer)."""
+        p = self.dropout_p if self.training else 0.0
+        if p == 0.0:
+            return linear_module_fwd(self.to_out[0], o, residual)
+        y, b_lin = linear_module_fwd(self.to_out[0], o)
+        y, b_drop = ops.dropout_fwd(y, p, ops.dropout_site(self), residual=residual, inplace=True)
+        return y, lambda dy: b_lin(b_drop(dy))
 
     def fwd(self, x: Tensor, context: Optional[Tensor], B: int, residual: Optional[Tensor] = None, need_dctx: bool = False, x_saved=None):
         """x [B*L, C]; context [B*Lc, Cc] or None (self-attention).  Returns (out, bwd); bwd(dy) -> (dx, dctx|None).
@@ -120,7 +145,7 @@ class CrossAttention(nn.Module):
             qkv = ops.gemm_nt(x, w_qkv)
             q, k, v = qkv[:, :inner], qkv[:, inner:2 * inner], qkv[:, 2 * inner:]
             o, b_att = ops.attention_fwd(q, k, v, B, self.heads, self.dim_head)
-            y, b_out = linear_module_fwd(self.to_out[0], o, residual)
+            y, b_out = self._out_fwd(o, residual)
 
             def bwd(dy: Tensor):
                 do = b_out(dy)
@@ -151,7 +176,7 @@ class CrossAttention(nn.Module):
             k = ops.gemm_nt(ctx, ops.w2d(wk))
             v = ops.gemm_nt(ctx, ops.w2d(wv))
         o, b_att = ops.attention_fwd(q, k, v, B, self.heads, self.dim_head)
-        y, b_out = linear_module_fwd(self.to_out[0], o, residual)
+        y, b_out = self._out_fwd(o, residual)
         del x, ctx                      # (the closure below reaches the layer's input through x_back / ctx_back only)
 
         def bwd(dy: Tensor):
@@ -196,6 +221,7 @@ class CrossAttention(nn.Module):
             raise NotImplementedError("mask / additional_tokens / cross-frame attention are video features outside the SDXL path")
         B, L, _ = x.shape
         ins = [x] if context is None else [x, context]
+        ops.dropout_open(self)
 
         def run(x, context=None):
             need_dctx = context is not None and context.requires_grad
@@ -279,9 +305,11 @@ class BasicTransformerBlock(nn.Module):
         if not (self.checkpoint and ops.recording()):
             return self._fwd(x, context, B, need_dctx)
         y, _ = self._fwd(x, context, B, need_dctx)
+        tok = ops.dropout_token(required=False)       # the re-run must see this forward's masks, whatever was drawn since
 
         def bwd(dy: Tensor):
-            _, b = self._fwd(x, context, B, need_dctx)
+            with ops.dropout_token_scope(tok):
+                _, b = self._fwd(x, context, B, need_dctx)
             return b(dy)
 
         return y, bwd
@@ -291,6 +319,7 @@ class BasicTransformerBlock(nn.Module):
             raise NotImplementedError("video-only arguments are outside the SDXL path")
         B, L, _ = x.shape
         ins = [x] if context is None else [x, context]
+        ops.dropout_open(self)
 
         def run(x, context=None):
             need_dctx = context is not None and context.requires_grad
@@ -373,6 +402,7 @@ class SpatialTransformer(nn.Module):
                 raise NotImplementedError("per-block context lists are not used by the SDXL configs")
             context = context[0]
         ins = [x] if context is None else [x, context]
+        ops.dropout_open(self)
 
         def run(x, context=None):
             need_dctx = context is not None and context.requires_grad

@@ -87,7 +87,8 @@ class ResnetBlock(nn.Module):
         if temb_channels > 0:
             self.temb_proj = nn.Linear(temb_channels, out_channels)
         self.norm2 = Normalize(out_channels)
-        self.dropout = nn.Identity()
+        self.dropout_p = ops.check_dropout_rate(dropout, "ResnetBlock")
+        self.dropout = nn.Dropout(dropout) if dropout > 0.0 else nn.Identity()
         self.conv2 = Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1)
         if self.in_channels != self.out_channels:
             if self.use_conv_shortcut:
@@ -113,11 +114,15 @@ class ResnetBlock(nn.Module):
         return self.conv2.fwd(h, residual=s, need_dx=False, stats_groups=groups if want_sums else None)[0]
 
     def fwdb(self, x: Img):
-        """(y, bwd); bwd(dy tokens) -> dx tokens"""
+        """(y, bwd); bwd(dy tokens) -> dx tokens.  Training with dropout > 0: norm2 + swish -> dropout -> conv2 (model.py:123-126), the mask laid
+        over h2 in place and over its gradient before norm2's backward; `fwd` (the frozen first stage, eval) has none."""
         n1, n2 = self.norm1, self.norm2
         h0, b_n1 = ops.groupnorm_fwd(x, n1.weight, n1.bias, n1.num_groups, n1.eps, True)
         h1, b_c1 = self.conv1.fwd(h0)
         h2, b_n2 = ops.groupnorm_fwd(h1, n2.weight, n2.bias, n2.num_groups, n2.eps, True)
+        b_drop = None
+        if self.training and self.dropout_p > 0.0:
+            _, b_drop = ops.dropout_fwd(h2.t, self.dropout_p, ops.dropout_site(self), inplace=True)
         b_short = None
         if self.in_channels != self.out_channels:
             short, b_short = (self.conv_shortcut if self.use_conv_shortcut else self.nin_shortcut).fwd(x)
@@ -127,7 +132,8 @@ class ResnetBlock(nn.Module):
         y, b_c2 = self.conv2.fwd(h2, residual=skip)
 
         def bwd(dy: Tensor) -> Tensor:
-            dh1 = b_n2(b_c2(dy)[0].t)
+            dh2 = b_c2(dy)[0].t
+            dh1 = b_n2(dh2 if b_drop is None else b_drop(dh2, inplace=True))
             dh0 = b_c1(dh1)[0].t
             through_skip = dy if b_short is None else b_short(dy)[0].t
             return b_n1(dh0, dx_add=through_skip)
@@ -277,6 +283,7 @@ class Encoder(nn.Module):
     def fwdb(self, x: Img):
         """encode (+ quant_conv when standalone) keeping the backward: (moments Img, bwd); bwd(d_moments tokens) -> None (the
         image needs no gradient)."""
+        ops.dropout_open(self)      # (training with ddconfig.dropout > 0: one draw per micro-batch; else nothing)
         tape = []
 
         def run(pair):
@@ -416,6 +423,7 @@ class Decoder(nn.Module):
         """(image Img, bwd); bwd(d_image tokens) -> dz tokens"""
         if self.give_pre_end or self.tanh_out:
             raise NotImplementedError("give_pre_end / tanh_out are not used by the SD/SDXL autoencoder configs")
+        ops.dropout_open(self)      # (training with ddconfig.dropout > 0: one draw per micro-batch; else nothing)
         tape = []
 
         def run(pair):

@@ -81,6 +81,7 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
 
     def forward(self, x: Tensor, emb: Tensor, context: Optional[Tensor] = None, image_only_indicator=None, time_context=None, num_video_frames=None):
         ins = [x, emb] if context is None else [x, emb, context]
+        ops.dropout_open(self)
 
         def run(x, emb, context=None):
             img = Img.from_nchw(x)
@@ -157,11 +158,11 @@ class ResBlock(TimestepBlock):
                  use_scale_shift_norm: bool = False, dims: int = 2, use_checkpoint: bool = False, up: bool = False, down: bool = False,
                  kernel_size: int = 3, exchange_temb_dims: bool = False, skip_t_emb: bool = False):
         super().__init__()
-        if use_scale_shift_norm or up or down or exchange_temb_dims or skip_t_emb or dropout != 0.0:
-            raise NotImplementedError("ResBlock: scale-shift norm / resblock_updown / dropout>0 are not used by the SD/SDXL configs")
+        if use_scale_shift_norm or up or down or exchange_temb_dims or skip_t_emb:
+            raise NotImplementedError("ResBlock: scale-shift norm / resblock_updown are not used by the SD/SDXL configs")
         self.channels = channels
         self.emb_channels = emb_channels
-        self.dropout = dropout
+        self.dropout = self.dropout_p = ops.check_dropout_rate(dropout, "ResBlock")
         self.out_channels = out_channels if out_channels is not None else channels
         self.use_conv = use_conv
         self.use_checkpoint = use_checkpoint
@@ -189,6 +190,11 @@ class ResBlock(TimestepBlock):
         eo, b_eo = linear_module_fwd(self.emb_layers[1], es)
         h2, b_c1 = self.in_layers[2].fwd(h1, rowvec=eo, stats_groups=32)      # the epilogue sums h2 for gn2: no statistics pass there
         h3, b_gn2 = ops.groupnorm_fwd(h2, gn2.weight, gn2.bias, 32, gn2.eps, silu=True)
+        b_drop = None
+        if self.training and self.dropout_p > 0.0:
+            # out_layers = GroupNorm, SiLU, Dropout, conv: h3 is masked IN PLACE (nk_groupnorm_bwd reads its input and statistics, never its
+            # output), so the convolution and its weight gradient read the dropped tensor
+            _, b_drop = ops.dropout_fwd(h3.t, self.dropout_p, ops.dropout_site(self), inplace=True)
         skip = self.skip_connection
         b_skip = None
         if isinstance(skip, nn.Identity):
@@ -202,7 +208,7 @@ class ResBlock(TimestepBlock):
 
         def bwd(dy: Tensor):
             dh3, _ = b_c2(dy)
-            dh2 = b_gn2(dh3.t)
+            dh2 = b_gn2(dh3.t if b_drop is None else b_drop(dh3.t, inplace=True))
             dh1, deo = b_c1(dh2)
             dxs = dy if b_skip is None else b_skip(dy)
             dx = b_gn1(dh1.t, dxs)
@@ -217,14 +223,18 @@ class ResBlock(TimestepBlock):
         if not (self.use_checkpoint and ops.recording()):
             return self._fwd(x, emb)
         out, _ = self._fwd(x, emb)
+        tok = ops.dropout_token(required=False)       # the re-run must see this forward's mask, whatever was drawn since
 
         def bwd(dy: Tensor):
-            _, b = self._fwd(x, emb)
+            with ops.dropout_token_scope(tok):
+                _, b = self._fwd(x, emb)
             return b(dy)
 
         return out, bwd
 
     def forward(self, x: Tensor, emb: Tensor) -> Tensor:
+        ops.dropout_open(self)
+
         def run(x, emb):
             img = Img.from_nchw(x)
             out, bwd = self.fwd(img, as_tokens(emb))
@@ -307,7 +317,7 @@ class UNetModel(nn.Module):
             raise ValueError("UNetModel: num_attention_blocks needs one entry per level, like num_res_blocks")
 
         self.attention_resolutions = attention_resolutions
-        self.dropout = dropout
+        self.dropout = ops.check_dropout_rate(dropout, "UNetModel")
         self.channel_mult = channel_mult
         self.conv_resample = conv_resample
         self.num_classes = num_classes
@@ -332,7 +342,7 @@ class UNetModel(nn.Module):
                 heads, dim_head = num_heads, ch // num_heads
             else:
                 heads, dim_head = ch // num_head_channels, num_head_channels
-            return SpatialTransformer(ch, heads, dim_head, depth=level_depth, context_dim=context_dim, disable_self_attn=disabled_sa,
+            return SpatialTransformer(ch, heads, dim_head, depth=level_depth, dropout=dropout, context_dim=context_dim, disable_self_attn=disabled_sa,
                                       use_linear=use_linear_in_transformer, attn_type=spatial_transformer_attn_type, use_checkpoint=use_checkpoint)
 
         def res(cin, cout):
@@ -457,6 +467,8 @@ class UNetModel(nn.Module):
         hook_raw = self.grad_ready_hook
         need_dctx = bool(need_dctx) and context is not None
         need_dy = bool(need_dy) and y is not None and self.num_classes is not None
+        if self.training and self.dropout > 0.0:
+            ops.dropout_open(self)          # one draw per micro-batch, inside the chain: a captured forward draws on every replay
         t_emb = ops.timestep_embedding(timesteps, self.model_channels)
         emb, b_time = self._mlp_fwd(self.time_embed, t_emb, need_dx=False)
         b_label = None

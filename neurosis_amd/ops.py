@@ -954,6 +954,153 @@ def silu_fwd(x: Tensor):
     return y, bwd
 
 
+# ------------------------------------------------------------------------------------------------
+# dropout: counter-based masks, never stored (csrc/dropout.hip has the definition; tests/dropout_ref.py restates it)
+# ------------------------------------------------------------------------------------------------
+# One persistent {seed, step} pair of 64-bit words per device.  It is created on first use (seed = torch.initial_seed(), step = 0) and never
+# reallocated: captured graphs hold its address, dropout_seed() writes INTO it.  A "draw" (nk_dropout_draw, one lane) advances the step and
+# copies {seed, step} into a token; every mask of one micro-batch of one model reads that token, told apart by a site id.  Ranks seeded
+# alike draw alike (as under Lightning's seed_everything): dropout_seed(seed + rank) is the way out.  The counter is not part of any
+# state_dict (torch's generator state is not either).
+_dropout = threading.local()          # .token: the current draw's token (per thread, like _recording)
+_dropout_states: dict = {}            # device index -> int64 [2] tensor {seed, step}
+
+
+def _as_i64(v: int) -> int:
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def _dropout_state_tensor(device=None) -> Tensor:
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"dropout: the counter lives on a GPU, got device {dev}")
+    idx = torch.cuda.current_device() if dev.index is None else dev.index
+    st = _dropout_states.get(idx)
+    if st is None:
+        if capturing():
+            raise RuntimeError("dropout: the first draw on a device cannot happen inside a hipGraph capture (it allocates the counter)")
+        st = _dropout_states[idx] = torch.tensor([_as_i64(torch.initial_seed()), 0], dtype=torch.int64, device=torch.device("cuda", idx))
+    return st
+
+
+def dropout_seed(seed: int, step: int = 0, device=None) -> None:
+    """Set the dropout counter of `device` (default: the current one) to (seed, step), in place: graphs captured earlier stay valid and draw
+    from the new pair on their next replay."""
+    st = _dropout_state_tensor(device)
+    st.copy_(torch.tensor([_as_i64(int(seed)), _as_i64(int(step))], dtype=torch.int64))
+
+
+def dropout_state(device=None) -> tuple:
+    """(seed, step) of `device`'s dropout counter; step = the number of draws since dropout_seed / creation.  Synchronises."""
+    seed, step = _dropout_state_tensor(device).tolist()
+    return seed & ((1 << 64) - 1), step & ((1 << 64) - 1)
+
+
+def dropout_consts(p: float) -> tuple:
+    """(thr, scale) the kernel takes for rate p: keep iff the element's 16-bit half >= thr = round(p * 65536) (the rate is thereby quantised
+    to 1 / 65536); scale = 1 / (1 - p), rounded to fp32 where it is passed"""
+    return int(round(p * 65536)), 1.0 / (1.0 - p)
+
+
+def check_dropout_rate(p, owner: str) -> float:
+    """p in [0, 1) or ValueError naming `owner`.  (The reference's nn.Dropout also takes p = 1, all zeros: refused here, 1 / (1 - p) has no value.)"""
+    try:
+        ok = 0.0 <= float(p) < 1.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{owner}: dropout must be a rate in [0, 1), got {p!r}")
+    return float(p)
+
+
+def dropout_draw(device=None) -> Tensor:
+    """Open a draw: advance `device`'s step and return the token {seed, step} (int64 [2], a fresh device tensor -- under a hipGraph capture it
+    comes from the chain's pool, so every replay fills the same address).  The token becomes the current one of this thread: dropout_fwd binds
+    it.  Callers: the entry of a training forward (dropout_open); backward, checkpoint re-runs and selective recompute never draw."""
+    st = _dropout_state_tensor(device)
+    tok = torch.empty(2, dtype=torch.int64, device=st.device)
+    call("nk_dropout_draw", st.data_ptr(), tok.data_ptr(), _stream())
+    _dropout.token = tok
+    return tok
+
+
+def dropout_open(top) -> bool:
+    """Entry of a forward of module `top`: when some module under it is training with a dropout rate > 0, give every such module its site id
+    -- its index in top.modules(), a function of the structure alone -- and draw.  Otherwise nothing happens (no launch, no step)."""
+    sites = [(i, m) for i, m in enumerate(top.modules()) if m.training and getattr(m, "dropout_p", 0.0) > 0.0]
+    if not sites:
+        return False
+    for i, m in sites:
+        m.__dict__["_nk_site"] = i
+    p = next(top.parameters(), None)
+    dropout_draw(p.device if p is not None and p.is_cuda else None)
+    return True
+
+
+def dropout_site(module) -> int:
+    """the site id dropout_open gave `module`; a module used on its own is index 0 of its own modules()"""
+    return module.__dict__.get("_nk_site", 0)
+
+
+def dropout_token(required: bool = True) -> Optional[Tensor]:
+    tok = getattr(_dropout, "token", None)
+    if tok is None and required:
+        raise RuntimeError("dropout: no draw is open on this thread (ops.dropout_draw() / ops.dropout_open(module) at the entry of the forward)")
+    return tok
+
+
+class dropout_token_scope:
+    """`with ops.dropout_token_scope(tok):` -- re-install the token of an earlier forward around its re-run (activation checkpointing)."""
+
+    def __init__(self, token: Optional[Tensor]):
+        self.token = token
+
+    def __enter__(self):
+        self.prev = getattr(_dropout, "token", None)
+        _dropout.token = self.token
+
+    def __exit__(self, *exc):
+        _dropout.token = self.prev
+
+
+def dropout_mask_like(x: Tensor, p: float, site: int, token: Tensor, residual: Optional[Tensor] = None, inplace: bool = True) -> Tensor:
+    """Apply the (token, site) mask of rate p, times 1 / (1 - p), to the token matrix x [rows, cols] (+ residual): in place, or into a new dense
+    tensor.  x may be a column slice of a wider buffer -- the mask goes by the LOGICAL index row * cols + col -- so one mask over [M, I]
+    can be laid over each half of an [M, 2I] buffer.  cols % 8 == 0 and 16-byte-aligned rows."""
+    _check2d(x, "x")
+    rows, cols = x.shape
+    y = x if inplace else torch.empty(rows, cols, dtype=BF16, device=x.device)
+    if residual is not None:
+        _check2d(residual, "residual")
+        if residual.shape != x.shape:
+            raise ValueError(f"dropout: residual {tuple(residual.shape)} does not match x {tuple(x.shape)}")
+    for name, t in (("x", x), ("residual", residual)):
+        if t is not None and (cols % 8 or t.stride(0) % 8 or t.data_ptr() % 16):
+            raise ValueError(f"dropout: {name} needs cols % 8 == 0 and 16-byte-aligned rows, got shape {tuple(t.shape)} stride {t.stride()}")
+    if token.dtype != torch.int64 or token.numel() != 2 or token.device != x.device:
+        raise ValueError("dropout: token must be the int64 [2] tensor of ops.dropout_draw() on x's device")
+    if rows == 0:
+        return y
+    thr, scale = dropout_consts(check_dropout_rate(p, "dropout"))
+    call("nk_dropout", x.data_ptr(), _p(residual), y.data_ptr(), rows, cols, x.stride(0), residual.stride(0) if residual is not None else 0, y.stride(0),
+         token.data_ptr(), int(site), thr, scale, _stream())
+    return y
+
+
+def dropout_fwd(x: Tensor, p: float, site: int, residual: Optional[Tensor] = None, inplace: bool = False):
+    """nn.Dropout(p) in training mode on a token matrix, with an optional residual added behind it: y = residual + x * mask / (1 - p).
+    The CURRENT token is bound into the closure, so a backward -- or a recomputation -- that runs after later draws regenerates the mask of
+    its own forward.  bwd(dy, inplace=False) -> dx = dy * mask / (1 - p) (the residual branch is the caller's)."""
+    tok = dropout_token()
+    y = dropout_mask_like(x, p, site, tok, residual, inplace)
+
+    def bwd(dy: Tensor, inplace: bool = False) -> Tensor:
+        return dropout_mask_like(dy, p, site, tok, None, inplace)
+
+    return y, bwd
+
+
 def cat_fwd(a: Img, b: Img):
     """torch.cat([a, b], dim=1) on channels-last images.  bwd(dout) -> (da, db) token matrices."""
     if (a.N, a.H, a.W) != (b.N, b.H, b.W):

@@ -725,7 +725,28 @@ def _(dy, w, u):
     return dy.new_empty(dy.shape[0], 2 * w.shape[1])
 
 
-OPS = ("cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
+# ---------------------------------------------------------------------------------------------------------------
+# dropout: y = residual + x * mask(token, site) / (1 - p), the mask regenerated from a counter (csrc/dropout.hip), never stored
+# ---------------------------------------------------------------------------------------------------------------
+@_op("dropout")
+def dropout(x: Tensor, token: Tensor, p: float, site: int, residual: Optional[Tensor] = None) -> Tensor:
+    """nn.Dropout(p) in training mode on a bf16 token matrix [rows, cols] (cols % 8 == 0), optional residual added behind the mask.  token:
+    the int64 [2] {seed, step} tensor of neurosis_amd.ops.dropout_draw().  Its own backward is the same call on the gradient."""
+    return ops.dropout_mask_like(x, p, site, token, residual, inplace=False)
+
+
+@dropout.register_fake
+def _(x, token, p, site, residual=None):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+dropout.register_autograd(lambda ctx, dy: (torch.ops.neurosis_hip.dropout(dy.contiguous(), ctx.saved_tensors[0], ctx.p, ctx.site), None, None, None,
+                                           dy if ctx.has_residual else None),
+                          setup_context=lambda ctx, inputs, output: (ctx.save_for_backward(inputs[1]), setattr(ctx, "p", inputs[2]),
+                                                                     setattr(ctx, "site", inputs[3]), setattr(ctx, "has_residual", inputs[4] is not None)))
+
+
+OPS = ("dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
        "flat_allreduce_start", "flat_allreduce_wait", "conv2d_fwd_stats", "linear_dgrad_geglu", "linear_fwd_geglu", "linear_fwd", "linear_dgrad", "linear_wgrad", "colsum", "linear", "layernorm_fwd", "layernorm_bwd", "layernorm", "groupnorm_silu_fwd",
        "groupnorm_silu_bwd", "groupnorm_silu", "geglu_fwd", "geglu_bwd", "geglu", "attention_fwd", "attention_bwd", "attention", "conv2d_fwd",
        "conv2d_dgrad", "conv2d_wgrad", "conv2d", "timestep_embedding", "nchw_to_nlc", "nlc_to_nchw")
