@@ -213,6 +213,18 @@ int nk_groupnorm_apply(const void* x, const float* sums, const float* gamma, con
 int nk_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
                      const float* rstd, const void* dx_add, void* dx, float* dgamma, float* dbeta, float* ws,
                      int N, int HW, int C, int G, int silu, int accumulate, void* stream);
+/* Scale-shift modulated GroupNorm (ResBlock use_scale_shift_norm): y = silu?(GN(x) * (1 + scale) + shift) with mod = bf16 [N][2C], per
+ * image scale in the first C columns and shift in the last C; 1 + scale and the whole affine in fp32.  _mod_fwd is the one-call form,
+ * _mod_apply consumes sums like nk_groupnorm_apply; ws as for nk_groupnorm_fwd / _bwd.  The backward also writes dmod = bf16 [N][2C],
+ * d_scale | d_shift; every reduction goes through fixed-order partials (no atomics, no memset).  With mod == 0 all three compute what the
+ * unmodulated entry points do, bit for bit. */
+int nk_groupnorm_mod_fwd(const void* x, const float* gamma, const float* beta, const void* mod, void* y, float* mean, float* rstd,
+                         float* ws, int N, int HW, int C, int G, float eps, int silu, void* stream);
+int nk_groupnorm_mod_apply(const void* x, const float* sums, const float* gamma, const float* beta, const void* mod, void* y, float* mean,
+                           float* rstd, int N, int HW, int C, int G, float eps, int silu, void* stream);
+int nk_groupnorm_mod_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const void* mod, const float* mean,
+                         const float* rstd, const void* dx_add, void* dx, float* dgamma, float* dbeta, void* dmod, float* ws,
+                         int N, int HW, int C, int G, int silu, int accumulate, void* stream);
 
 /* nn.LayerNorm(C) over rows of [M][C] (attention.py:468-470).  mean/rstd: [M] fp32. */
 int nk_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
@@ -279,6 +291,12 @@ int nk_split_channels(const void* src, void* a, void* b, long rows, int Ca, int 
 
 /* backward of F.interpolate(scale_factor=2, mode="nearest") (openaimodel.py:140): 2x2 sum-pool */
 int nk_upsample2x_bwd(const void* dup, void* dx, int N, int H, int W, int C, void* stream);
+/* nearest 2x as a materialised copy, x [N][H][W][C] -> up [N][2H][2W][C] (its backward is nk_upsample2x_bwd); and avg_pool2d(2, 2) in
+ * floor mode, x [N][H][W][C] -> y [N][H/2][W/2][C] (fp32 sum, one rounding), whose backward writes dy / 4 to the four inputs of each
+ * window and zeros into an odd last row or column.  C % 8 == 0. */
+int nk_upsample2x_fwd(const void* x, void* up, int N, int H, int W, int C, void* stream);
+int nk_avgpool2x_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream);
+int nk_avgpool2x_bwd(const void* dy, void* dx, int N, int H, int W, int C, void* stream);
 
 /* boundary layout/dtype conversion: NCHW (fp32 or bf16) <-> channels-last bf16 with channels padded to Cpad */
 int nk_nchw_to_nhwc(const void* src, int src_is_f32, void* dst, int N, int C, int HW, int Cpad, float scale,

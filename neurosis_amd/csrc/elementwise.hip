@@ -389,6 +389,90 @@ extern "C" int nk_upsample2x_bwd(const void* dup, void* dx, int N, int H, int W,
   return nk_check_launch("upsample2x_bwd");
 }
 
+// ---- parameter-free resampling (Upsample / Downsample with use_conv=False, the up / down ResBlock; openaimodel.py:96-197) ----
+// nearest 2x forward, materialised: up[n, h, w, :] = x[n, h/2, w/2, :]   (its backward is up2_bwd_kernel)
+__global__ void up2_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ up, int N, int H, int W, int C) {
+  const int cpr = C >> 3;
+  const long total = (long)N * 2 * H * 2 * W * cpr;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    int ch = (int)(i % cpr);
+    long pix = i / cpr;
+    int w = (int)(pix % (2 * W));
+    long t = pix / (2 * W);
+    int h = (int)(t % (2 * H));
+    int n = (int)(t / (2 * H));
+    *(uint4_t*)(up + i * 8) = *(const uint4_t*)(x + (((long)n * H + (h >> 1)) * W + (w >> 1)) * C + ch * 8);
+  }
+}
+extern "C" int nk_upsample2x_fwd(const void* x, void* up, int N, int H, int W, int C, void* stream) {
+  NK_CHECK_ARG(x && up && N > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0);
+  hipLaunchKernelGGL(up2_fwd_kernel, dim3(ew_blocks((long)N * 4 * H * W * (C >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (bf16_t*)up, N, H, W, C);
+  return nk_check_launch("upsample2x_fwd");
+}
+
+// avg_pool2d(2, 2), floor mode: y[n, h, w, :] = mean of x[n, 2h..2h+1, 2w..2w+1, :], summed in fp32 and rounded once; an odd last row or
+// column of x is not read
+__global__ void avgpool2x_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int N, int H, int W, int C) {
+  const int cpr = C >> 3, Ho = H >> 1, Wo = W >> 1;
+  const long total = (long)N * Ho * Wo * cpr;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    int ch = (int)(i % cpr);
+    long pix = i / cpr;
+    int w = (int)(pix % Wo);
+    long t = pix / Wo;
+    int h = (int)(t % Ho);
+    int n = (int)(t / Ho);
+    const bf16_t* s = x + (((long)n * H + 2 * h) * W + 2 * w) * C + ch * 8;
+    float acc[8], f[8];
+    unpack8(*(const uint4_t*)s, acc);
+    unpack8(*(const uint4_t*)(s + C), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += f[e];
+    unpack8(*(const uint4_t*)(s + (long)W * C), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += f[e];
+    unpack8(*(const uint4_t*)(s + (long)W * C + C), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = (acc[e] + f[e]) * 0.25f;
+    *(uint4_t*)(y + i * 8) = pack8(acc);
+  }
+}
+// ... backward: dx[n, h, w, :] = dy[n, h/2, w/2, :] / 4; zeros in the odd last row or column the forward dropped
+__global__ void avgpool2x_bwd_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx, int N, int H, int W, int C) {
+  const int cpr = C >> 3, Ho = H >> 1, Wo = W >> 1;
+  const long total = (long)N * H * W * cpr;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    int ch = (int)(i % cpr);
+    long pix = i / cpr;
+    int w = (int)(pix % W);
+    long t = pix / W;
+    int h = (int)(t % H);
+    int n = (int)(t / H);
+    uint4_t out = {0u, 0u, 0u, 0u};
+    if ((h >> 1) < Ho && (w >> 1) < Wo) {
+      float f[8];
+      unpack8(*(const uint4_t*)(dy + (((long)n * Ho + (h >> 1)) * Wo + (w >> 1)) * C + ch * 8), f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] *= 0.25f;
+      out = pack8(f);
+    }
+    *(uint4_t*)(dx + i * 8) = out;
+  }
+}
+extern "C" int nk_avgpool2x_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
+  NK_CHECK_ARG(x && y && N > 0 && H > 1 && W > 1 && C > 0 && (C & 7) == 0);
+  hipLaunchKernelGGL(avgpool2x_fwd_kernel, dim3(ew_blocks((long)N * (H >> 1) * (W >> 1) * (C >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (bf16_t*)y, N, H, W, C);
+  return nk_check_launch("avgpool2x_fwd");
+}
+extern "C" int nk_avgpool2x_bwd(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
+  NK_CHECK_ARG(dy && dx && N > 0 && H > 1 && W > 1 && C > 0 && (C & 7) == 0);
+  hipLaunchKernelGGL(avgpool2x_bwd_kernel, dim3(ew_blocks((long)N * H * W * (C >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                     (const bf16_t*)dy, (bf16_t*)dx, N, H, W, C);
+  return nk_check_launch("avgpool2x_bwd");
+}
+
 // ---- layout / dtype boundary: NCHW (fp32 or bf16) <-> channels-last bf16 with channel padding ---
 // tile of 32 pixels x 32 channels through LDS
 template <typename SrcT>

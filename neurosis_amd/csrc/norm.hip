@@ -99,8 +99,20 @@ __global__ __launch_bounds__(1024) void gn_reduce_partials_kernel(const float* _
 // Half a bf16 ulp is 1.95e-3: beyond |mean| / sigma ~ 64 the statistics are no longer bf16-accurate.  The network's activations stay
 // far below that; tests/test_norm_reductions_gpu.py holds the statistics to their derived bounds up to 32.
 // ------------------------------------------------------------------------------------------------
+// Scale-shift modulation (ResBlock use_scale_shift_norm, openaimodel.py:332-336): GN(x) * (1 + s_nc) + t_nc is a GroupNorm whose affine
+// differs per image, gamma'_nc = gamma_c (1 + s_nc), beta'_nc = beta_c (1 + s_nc) + t_nc.  mod: bf16 [N][2C], scale | shift; all in fp32.
+// With s = t = 0 both come out as gamma_c and beta_c exactly, so the MOD kernels then compute what the plain ones do, bit for bit.
+__device__ __forceinline__ void gn_modulate(const bf16_t* __restrict__ mod, int n, int c, int C, float& ga, float& be) {
+  const float s1 = 1.0f + bf2f(mod[(long)n * 2 * C + c]);
+  const float t = bf2f(mod[(long)n * 2 * C + C + c]);
+  ga = ga * s1;
+  be = be * s1 + t;
+}
+
+template <bool MOD>
 __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const bf16_t* __restrict__ x, const float* __restrict__ stats,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              const bf16_t* __restrict__ mod,
                                                               bf16_t* __restrict__ y, float* __restrict__ mean_out,
                                                               float* __restrict__ rstd_out, int HW, int C, int G,
                                                               float eps, int silu, int rows_per) {
@@ -116,9 +128,11 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const bf16_t* __re
     float m = stats[(long)n * 2 * G + 2 * g] * inv_cnt;
     float var = fmaxf(stats[(long)n * 2 * G + 2 * g + 1] * inv_cnt - m * m, 0.f);
     float rs = rsqrtf(var + eps);
-    float a = rs * gamma[c];
+    float ga = gamma[c], be = beta[c];
+    if constexpr (MOD) gn_modulate(mod, n, c, C, ga, be);
+    float a = rs * ga;
     sc[c] = a;
-    sh[c] = beta[c] - m * a;
+    sh[c] = be - m * a;
     if (blockIdx.x == 0 && (c % cpg) == 0) { mean_out[n * G + g] = m; rstd_out[n * G + g] = rs; }
   }
   __syncthreads();
@@ -159,8 +173,11 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const bf16_t* __re
 //   per channel: a_c = sum dz, b_c = sum dz*xhat           -> dbeta += a, dgamma += b
 //   per (n,g):   s1 = sum_c gamma_c a_c, s2 = sum_c gamma_c b_c -> gsum[n][g][2]
 // ------------------------------------------------------------------------------------------------
+//   MOD: gamma, beta are the image's gamma'_nc, beta'_nc; the channel partials stay per image (a_nc, b_nc) for the folds below
+template <bool MOD>
 __global__ __launch_bounds__(GN_THREADS, 4) void gn_bwd_stats_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const bf16_t* __restrict__ mod,
                                                                   const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                   float* __restrict__ gsum, float* __restrict__ chan_part,
                                                                   int HW, int C, int G, int silu, int rows_per) {
@@ -186,6 +203,7 @@ __global__ __launch_bounds__(GN_THREADS, 4) void gn_bwd_stats_kernel(const bf16_
       a[e] = 0.f; b[e] = 0.f;
       mu[e] = mean[n * G + g]; rs[e] = rstd[n * G + g];
       ga[e] = gamma[c]; be[e] = beta[c];
+      if constexpr (MOD) gn_modulate(mod, n, c, C, ga[e], be[e]);
     }
     const long base = ((long)n * HW) * C + (ch0 + chunk) * 8;
     auto one = [&](const uint4_t& rx, const uint4_t& rd) {
@@ -238,7 +256,11 @@ __global__ __launch_bounds__(GN_THREADS, 4) void gn_bwd_stats_kernel(const bf16_
     const float* src = (i & 1) ? cb : ca;
     const int c_lo = max(g * cpg, ch0 * 8), c_hi = min((g + 1) * cpg, (ch0 + cpr) * 8);
     float acc = 0.f;
-    for (int c = c_lo; c < c_hi; ++c) acc += gamma[c] * src[c - ch0 * 8];
+    for (int c = c_lo; c < c_hi; ++c) {
+      float gc = gamma[c];
+      if constexpr (MOD) { float bc = 0.f; gn_modulate(mod, n, c, C, gc, bc); }
+      acc += gc * src[c - ch0 * 8];
+    }
     part[i] = acc;
   }
 }
@@ -269,9 +291,64 @@ __global__ __launch_bounds__(1024) void colpart_reduce_kernel(const float* __res
   }
 }
 
+// The modulated GroupNorm's parameter gradients from the same per-(image, split) channel partials (row r belongs to image r / nsplit):
+//   dgamma[c] += sum_n (1 + s_nc) b_nc ; dbeta[c] += sum_n (1 + s_nc) a_nc.  Same block shape and summation order as colpart_reduce_kernel.
+__global__ __launch_bounds__(1024) void colpart_reduce_mod_kernel(const float* __restrict__ part, const bf16_t* __restrict__ mod,
+                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta, int nrows, int nsplit,
+                                                                  int C, int accumulate) {
+  __shared__ float sa[16][64], sb[16][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + tx;
+  float a = 0.f, b = 0.f;
+  if (c < C) {
+#pragma unroll 4
+    for (int r = ty; r < nrows; r += 16) {
+      const float s1 = 1.0f + bf2f(mod[(long)(r / nsplit) * 2 * C + c]);
+      a += s1 * part[(long)r * 2 * C + c];
+      b += s1 * part[(long)r * 2 * C + C + c];
+    }
+  }
+  sa[ty][tx] = a;
+  sb[ty][tx] = b;
+  __syncthreads();
+  if (ty == 0 && c < C) {
+#pragma unroll
+    for (int j = 1; j < 16; ++j) { a += sa[j][tx]; b += sb[j][tx]; }
+    dgamma[c] = accumulate ? dgamma[c] + a : a;
+    dbeta[c] = accumulate ? dbeta[c] + b : b;
+  }
+}
+
+// ... and the gradient of the modulation itself, dmod[n] = [d_scale | d_shift]: with a_nc = sum_hw dz, b_nc = sum_hw dz*xhat (the image's
+// nsplit partial rows, summed in a fixed order)  d_shift = a_nc,  d_scale = gamma_c b_nc + beta_c a_nc.  grid (C / 64, N).
+__global__ __launch_bounds__(1024) void gn_dmod_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, bf16_t* __restrict__ dmod, int nsplit, int C) {
+  __shared__ float sa[16][64], sb[16][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + tx, n = blockIdx.y;
+  float a = 0.f, b = 0.f;
+  if (c < C) {
+    for (int r = ty; r < nsplit; r += 16) {
+      b += part[((long)n * nsplit + r) * 2 * C + c];
+      a += part[((long)n * nsplit + r) * 2 * C + C + c];
+    }
+  }
+  sa[ty][tx] = a;
+  sb[ty][tx] = b;
+  __syncthreads();
+  if (ty == 0 && c < C) {
+#pragma unroll
+    for (int j = 1; j < 16; ++j) { a += sa[j][tx]; b += sb[j][tx]; }
+    dmod[(long)n * 2 * C + c] = f2bf(gamma[c] * b + beta[c] * a);
+    dmod[(long)n * 2 * C + C + c] = f2bf(a);
+  }
+}
+
 // GroupNorm backward, pass 2: dx = rstd * (dz*gamma - (s1 + xhat*s2)/cnt) (+ dx_add)
+template <bool MOD>
 __global__ __launch_bounds__(GN_THREADS) void gn_bwd_apply_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const bf16_t* __restrict__ mod,
                                                                   const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                   const float* __restrict__ gsum, const bf16_t* __restrict__ dx_add,
                                                                   bf16_t* __restrict__ dx, int HW, int C, int G, int silu,
@@ -293,9 +370,11 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_apply_kernel(const bf16_t* 
     const int g = c / cpg;
     const float mu = mean[n * G + g], rs = rstd[n * G + g];
     const float s1 = gsum[(long)n * 2 * G + 2 * g] * inv_cnt, s2 = gsum[(long)n * 2 * G + 2 * g + 1] * inv_cnt;
-    const float a = rs * gamma[c];
+    float ga = gamma[c], be = beta[c];
+    if constexpr (MOD) gn_modulate(mod, n, c, C, ga, be);
+    const float a = rs * ga;
     p_a[c] = a;
-    p_b[c] = beta[c] - mu * a;
+    p_b[c] = be - mu * a;
     p_c[c] = -rs * rs * s2;
     p_d[c] = -rs * s1 + mu * rs * rs * s2;
   }
@@ -385,8 +464,8 @@ extern "C" int nk_groupnorm_fwd(const void* x, const float* gamma, const float* 
   if (int e = nk_check_launch("gn_stats_kernel")) return e;
   hipLaunchKernelGGL(gn_reduce_partials_kernel, dim3(N), dim3(1024), 0, stream, part, stats, nsplit * nz, 2 * G);
   if (int e = nk_check_launch("gn_reduce_partials_kernel")) return e;
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(nsplit, N), dim3(GN_THREADS), 2 * C * sizeof(float), stream,
-                     (const bf16_t*)x, stats, gamma, beta, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, rows_per);
+  hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(nsplit, N), dim3(GN_THREADS), 2 * C * sizeof(float), stream,
+                     (const bf16_t*)x, stats, gamma, beta, (const bf16_t*)nullptr, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, rows_per);
   return nk_check_launch("gn_apply_kernel");
 }
 
@@ -449,8 +528,8 @@ extern "C" int nk_groupnorm_apply(const void* x, const float* sums, const float*
   NK_CHECK_ARG(x && sums && gamma && beta && y && mean && rstd);
   int nsplit;
   int rows_per = gn_rows_per(N, HW, &nsplit);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(nsplit, N), dim3(GN_THREADS), 2 * C * sizeof(float), stream, (const bf16_t*)x, sums, gamma, beta,
-                     (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, rows_per);
+  hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(nsplit, N), dim3(GN_THREADS), 2 * C * sizeof(float), stream, (const bf16_t*)x, sums, gamma, beta,
+                     (const bf16_t*)nullptr, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, rows_per);
   return nk_check_launch("gn_apply_kernel");
 }
 
@@ -467,17 +546,77 @@ extern "C" int nk_groupnorm_bwd(const void* dy, const void* x, const float* gamm
   float* part = ws;
   float* gsum = part + (long)N * nsplit * nz * 2 * G;
   float* chan = gsum + (long)N * 2 * G;
-  hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(nsplit, N, nz), dim3(GN_THREADS), 2 * C * sizeof(float), stream,
-                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, part, chan, HW, C, G, silu, rows_per);
+  hipLaunchKernelGGL(gn_bwd_stats_kernel<false>, dim3(nsplit, N, nz), dim3(GN_THREADS), 2 * C * sizeof(float), stream,
+                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, (const bf16_t*)nullptr, mean, rstd, part, chan, HW, C, G, silu, rows_per);
   if (int e = nk_check_launch("gn_bwd_stats_kernel")) return e;
   hipLaunchKernelGGL(gn_reduce_partials_kernel, dim3(N), dim3(1024), 0, stream, part, gsum, nsplit * nz, 2 * G);
   if (int e = nk_check_launch("gn_reduce_partials_kernel")) return e;
   hipLaunchKernelGGL(colpart_reduce_kernel, dim3((C + 63) / 64), dim3(1024), 0, stream, chan, dgamma, dbeta, N * nsplit, C, accumulate);
   if (int e = nk_check_launch("colpart_reduce_kernel")) return e;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(nsplit, N), dim3(GN_THREADS), 4 * C * sizeof(float), stream,
-                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, gsum, (const bf16_t*)dx_add,
+  hipLaunchKernelGGL(gn_bwd_apply_kernel<false>, dim3(nsplit, N), dim3(GN_THREADS), 4 * C * sizeof(float), stream,
+                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, (const bf16_t*)nullptr, mean, rstd, gsum, (const bf16_t*)dx_add,
                      (bf16_t*)dx, HW, C, G, silu, rows_per);
   return nk_check_launch("gn_bwd_apply_kernel");
+}
+
+// ---- the modulated forms (scale-shift norm): same passes, same workspace (nk_groupnorm_ws_floats), mod = bf16 [N][2C] scale | shift ----
+static int gn_mod_apply_launch(const void* x, const float* sums, const float* gamma, const float* beta, const void* mod, void* y, float* mean,
+                               float* rstd, int N, int HW, int C, int G, float eps, int silu, hipStream_t stream) {
+  int nsplit;
+  int rows_per = gn_rows_per(N, HW, &nsplit);
+  hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(nsplit, N), dim3(GN_THREADS), 2 * C * sizeof(float), stream, (const bf16_t*)x, sums, gamma, beta,
+                     (const bf16_t*)mod, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, rows_per);
+  return nk_check_launch("gn_apply_kernel<mod>");
+}
+
+extern "C" int nk_groupnorm_mod_fwd(const void* x, const float* gamma, const float* beta, const void* mod, void* y, float* mean, float* rstd,
+                                    float* ws, int N, int HW, int C, int G, float eps, int silu, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
+  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
+  NK_CHECK_ARG(x && gamma && beta && mod && y && mean && rstd && ws);
+  int nsplit;
+  gn_rows_per(N, HW, &nsplit);
+  float* stats = ws + (long)N * nsplit * gn_nz(C) * 2 * G;
+  if (int e = nk_groupnorm_sums(x, stats, ws, N, HW, C, G, stream_)) return e;
+  return gn_mod_apply_launch(x, stats, gamma, beta, mod, y, mean, rstd, N, HW, C, G, eps, silu, stream);
+}
+
+extern "C" int nk_groupnorm_mod_apply(const void* x, const float* sums, const float* gamma, const float* beta, const void* mod, void* y,
+                                      float* mean, float* rstd, int N, int HW, int C, int G, float eps, int silu, void* stream_) {
+  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
+  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
+  NK_CHECK_ARG(x && sums && gamma && beta && mod && y && mean && rstd);
+  return gn_mod_apply_launch(x, sums, gamma, beta, mod, y, mean, rstd, N, HW, C, G, eps, silu, (hipStream_t)stream_);
+}
+
+extern "C" int nk_groupnorm_mod_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const void* mod, const float* mean,
+                                    const float* rstd, const void* dx_add, void* dx, float* dgamma, float* dbeta, void* dmod, float* ws,
+                                    int N, int HW, int C, int G, int silu, int accumulate, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
+  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
+  NK_CHECK_ARG(dy && x && gamma && beta && mod && mean && rstd && dx && dgamma && dbeta && dmod && ws);
+  int nsplit;
+  int rows_per = gn_rows_per(N, HW, &nsplit);
+  const int nz = gn_nz(C);
+  float* part = ws;
+  float* gsum = part + (long)N * nsplit * nz * 2 * G;
+  float* chan = gsum + (long)N * 2 * G;
+  hipLaunchKernelGGL(gn_bwd_stats_kernel<true>, dim3(nsplit, N, nz), dim3(GN_THREADS), 2 * C * sizeof(float), stream,
+                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, (const bf16_t*)mod, mean, rstd, part, chan, HW, C, G, silu, rows_per);
+  if (int e = nk_check_launch("gn_bwd_stats_kernel<mod>")) return e;
+  hipLaunchKernelGGL(gn_reduce_partials_kernel, dim3(N), dim3(1024), 0, stream, part, gsum, nsplit * nz, 2 * G);
+  if (int e = nk_check_launch("gn_reduce_partials_kernel")) return e;
+  hipLaunchKernelGGL(colpart_reduce_mod_kernel, dim3((C + 63) / 64), dim3(1024), 0, stream, chan, (const bf16_t*)mod, dgamma, dbeta, N * nsplit,
+                     nsplit, C, accumulate);
+  if (int e = nk_check_launch("colpart_reduce_mod_kernel")) return e;
+  hipLaunchKernelGGL(gn_dmod_kernel, dim3((C + 63) / 64, N), dim3(1024), 0, stream, chan, gamma, beta, (bf16_t*)dmod, nsplit, C);
+  if (int e = nk_check_launch("gn_dmod_kernel")) return e;
+  hipLaunchKernelGGL(gn_bwd_apply_kernel<true>, dim3(nsplit, N), dim3(GN_THREADS), 4 * C * sizeof(float), stream,
+                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, (const bf16_t*)mod, mean, rstd, gsum, (const bf16_t*)dx_add,
+                     (bf16_t*)dx, HW, C, G, silu, rows_per);
+  return nk_check_launch("gn_bwd_apply_kernel<mod>");
 }
 
 // ------------------------------------------------------------------------------------------------

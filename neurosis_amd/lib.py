@@ -70,6 +70,9 @@ SIGNATURES: dict[str, list] = {
     "nk_groupnorm_sums_from_parts": [vp, vp, vp, i32, i32, i32, vp],
     "nk_groupnorm_apply": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "nk_groupnorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "nk_groupnorm_mod_fwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
+    "nk_groupnorm_mod_apply": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
+    "nk_groupnorm_mod_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "nk_layernorm_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp],
     "nk_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "nk_layernorm_bwd_dx": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
@@ -104,6 +107,9 @@ SIGNATURES: dict[str, list] = {
     "nk_cat_channels": [vp, vp, vp, i64, i32, i32, vp],
     "nk_split_channels": [vp, vp, vp, i64, i32, i32, vp],
     "nk_upsample2x_bwd": [vp, vp, i32, i32, i32, i32, vp],
+    "nk_upsample2x_fwd": [vp, vp, i32, i32, i32, i32, vp],
+    "nk_avgpool2x_fwd": [vp, vp, i32, i32, i32, i32, vp],
+    "nk_avgpool2x_bwd": [vp, vp, i32, i32, i32, i32, vp],
     "nk_nchw_to_nhwc": [vp, i32, vp, i32, i32, i32, i32, f32, vp],
     "nk_nhwc_to_nchw": [vp, vp, i32, i32, i32, i32, i32, vp],
     "nk_cast_f32_to_bf16": [vp, vp, i64, vp],

@@ -98,7 +98,8 @@ class TimestepEmbedSequential(nn.Sequential, TimestepBlock):
 
 
 class Upsample(nn.Module):
-    """openaimodel.py:96-143: nearest 2x (fused into the conv's gather) then 3x3 conv."""
+    """openaimodel.py:96-143: nearest 2x, then (use_conv) a 3x3 conv whose gather does the upsampling -- nothing is materialised.  Without
+    the conv it is a copy kernel and has no parameters."""
 
     def __init__(self, channels: int, use_conv: bool, dims: int = 2, out_channels: Optional[int] = None, padding: int = 1,
                  third_up: bool = False, kernel_size: int = 3, scale_factor: int = 2):
@@ -107,20 +108,26 @@ class Upsample(nn.Module):
         self.out_channels = out_channels or channels
         self.use_conv = use_conv
         self.dims = dims
-        if dims != 2 or scale_factor != 2 or not use_conv:
-            raise NotImplementedError("Upsample: the SD/SDXL path uses dims=2, scale 2, conv_resample=True")
-        self.conv = conv_nd(dims, self.channels, self.out_channels, kernel_size, padding=padding)
+        self.third_up = third_up
+        self.scale_factor = scale_factor
+        if dims != 2 or scale_factor != 2:
+            raise NotImplementedError("Upsample: the MI355X path implements dims=2, scale_factor=2 (dims=3 / third_up are the video options)")
+        if use_conv:
+            self.conv = conv_nd(dims, self.channels, self.out_channels, kernel_size, padding=padding)
 
     def fwd(self, x: Img, need_dx: bool = True):
         assert x.C == self.channels
-        return self.conv.fwd(x, upsample=True, need_dx=need_dx)
+        if self.use_conv:
+            return self.conv.fwd(x, upsample=True, need_dx=need_dx)
+        y, b = ops.upsample2x_fwd(x)
+        return y, (lambda dy: (Img(b(dy), x.N, x.H, x.W) if need_dx else None, None))
 
     def forward(self, x: Tensor) -> Tensor:
         return _plain_forward(self, x)
 
 
 class Downsample(nn.Module):
-    """openaimodel.py:146-197: 3x3 stride-2 conv."""
+    """openaimodel.py:146-197: 3x3 stride-2 conv, or (use_conv=False) avg_pool2d(2, 2): no parameters, an odd last row / column dropped."""
 
     def __init__(self, channels: int, use_conv: bool, dims: int = 2, out_channels: Optional[int] = None, padding: int = 1, third_down: bool = False):
         super().__init__()
@@ -128,13 +135,20 @@ class Downsample(nn.Module):
         self.out_channels = out_channels or channels
         self.use_conv = use_conv
         self.dims = dims
-        if dims != 2 or not use_conv:
-            raise NotImplementedError("Downsample: the SD/SDXL path uses dims=2, conv_resample=True")
-        self.op = conv_nd(dims, self.channels, self.out_channels, 3, stride=2, padding=padding)
+        if dims != 2:
+            raise NotImplementedError("Downsample: the MI355X path implements dims=2 (dims=3 / third_down are the video options)")
+        if use_conv:
+            self.op = conv_nd(dims, self.channels, self.out_channels, 3, stride=2, padding=padding)
+        else:
+            assert self.channels == self.out_channels, "Downsample(use_conv=False) cannot change the channel count"
+            self.op = nn.AvgPool2d(kernel_size=2, stride=2)     # the reference's module at this name; fwd runs ops.avgpool2x_fwd
 
     def fwd(self, x: Img, need_dx: bool = True):
         assert x.C == self.channels
-        return self.op.fwd(x, need_dx=need_dx)
+        if self.use_conv:
+            return self.op.fwd(x, need_dx=need_dx)
+        y, b = ops.avgpool2x_fwd(x)
+        return y, (lambda dy: (Img(b(dy), x.N, x.H, x.W) if need_dx else None, None))
 
     def forward(self, x: Tensor) -> Tensor:
         return _plain_forward(self, x)
@@ -152,14 +166,19 @@ def _plain_forward(mod: nn.Module, x: Tensor) -> Tensor:
 class ResBlock(TimestepBlock):
     """openaimodel.py:200-342.  h = conv(silu(GN(x))) + emb ; out = skip(x) + conv(silu(GN(h))).
     GN+SiLU is one kernel, the emb add and the skip add are conv epilogues, the skip-path gradient is an
-    epilogue of the first GroupNorm's backward."""
+    epilogue of the first GroupNorm's backward.
+
+    use_scale_shift_norm (the ADM block): emb_layers gives [scale | shift] and h = conv(silu(GN(h) * (1 + scale) + shift)) -- a GroupNorm
+    with a per-image affine, one kernel again (ops.groupnorm_mod_fwd); the first conv then adds no emb, and the emb gradient is that kernel's
+    dmod.  up / down (resblock_updown): silu(GN(x)) and x are both resampled before the first conv and the skip: nearest 2x rides in the
+    conv's gather, avg_pool2d(2, 2) is ops.avgpool2x_fwd, and the skip reads the resampled x."""
 
     def __init__(self, channels: int, emb_channels: int, dropout: float, out_channels: Optional[int] = None, use_conv: bool = False,
                  use_scale_shift_norm: bool = False, dims: int = 2, use_checkpoint: bool = False, up: bool = False, down: bool = False,
                  kernel_size: int = 3, exchange_temb_dims: bool = False, skip_t_emb: bool = False):
         super().__init__()
-        if use_scale_shift_norm or up or down or exchange_temb_dims or skip_t_emb:
-            raise NotImplementedError("ResBlock: scale-shift norm / resblock_updown are not used by the SD/SDXL configs")
+        if exchange_temb_dims or skip_t_emb:
+            raise NotImplementedError("ResBlock: exchange_temb_dims / skip_t_emb are options of the video UNet, which is not on the MI355X path")
         self.channels = channels
         self.emb_channels = emb_channels
         self.dropout = self.dropout_p = ops.check_dropout_rate(dropout, "ResBlock")
@@ -167,11 +186,22 @@ class ResBlock(TimestepBlock):
         self.use_conv = use_conv
         self.use_checkpoint = use_checkpoint
         self.use_scale_shift_norm = use_scale_shift_norm
+        self.exchange_temb_dims = exchange_temb_dims
         padding = kernel_size // 2
         self.in_layers = nn.Sequential(nn.GroupNorm(32, channels), nn.SiLU(), conv_nd(dims, channels, self.out_channels, kernel_size, padding=padding))
-        self.updown = False
-        self.h_upd = self.x_upd = nn.Identity()
-        self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_channels, self.out_channels))
+        self.updown = up or down
+        self._up, self._down = bool(up), bool(down) and not up
+        if up:
+            self.h_upd = Upsample(channels, False, dims)
+            self.x_upd = Upsample(channels, False, dims)
+        elif down:
+            self.h_upd = Downsample(channels, False, dims)
+            self.x_upd = Downsample(channels, False, dims)
+        else:
+            self.h_upd = self.x_upd = nn.Identity()
+        self.skip_t_emb = skip_t_emb
+        self.emb_out_channels = 2 * self.out_channels if use_scale_shift_norm else self.out_channels
+        self.emb_layers = nn.Sequential(nn.SiLU(), nn.Linear(emb_channels, self.emb_out_channels))
         self.out_layers = nn.Sequential(
             nn.GroupNorm(32, self.out_channels), nn.SiLU(), nn.Dropout(p=dropout),
             zero_module(conv_nd(dims, self.out_channels, self.out_channels, kernel_size, padding=padding)),
@@ -183,35 +213,71 @@ class ResBlock(TimestepBlock):
         else:
             self.skip_connection = conv_nd(dims, channels, self.out_channels, 1)
 
+    def _skip_fwd(self, x: Img):
+        """The skip connection on the (resampled) input: (s tokens on the output grid, bwd(dy tokens) -> gradient tokens on x's grid).
+        down: pool, then the skip.  up: an identity or 1x1 skip commutes with nearest upsampling (pointwise: bit-identical), so it runs on the
+        small grid and its result is copied up; a 3x3 skip upsamples in its gather, the reference's order."""
+        skip = self.skip_connection
+        b_res = None
+        if self._down:
+            x, b_res = ops.avgpool2x_fwd(x)
+        if isinstance(skip, nn.Identity):
+            s, b_skip = x.t, None
+        elif skip.kernel_size == 1:
+            s, b_skip = ops.linear_fwd(x.t, skip.weight, skip.bias)
+        else:
+            si, b_skip3 = skip.fwd(x, upsample=self._up)
+            s, b_skip = si.t, (lambda g: b_skip3(g)[0].t)
+        b_up = None
+        if self._up and (b_skip is None or skip.kernel_size == 1):
+            sup, b_up = ops.upsample2x_fwd(Img(s, x.N, x.H, x.W))
+            s = sup.t
+        if b_skip is None and b_res is None and b_up is None:
+            return s, None
+
+        def bwd(dy: Tensor) -> Tensor:
+            if b_up is not None:
+                dy = b_up(dy)
+            if b_skip is not None:
+                dy = b_skip(dy)
+            return dy if b_res is None else b_res(dy)
+
+        return s, bwd
+
     def _fwd(self, x: Img, emb: Tensor):
         gn1, gn2 = self.in_layers[0], self.out_layers[0]
+        ssn = self.use_scale_shift_norm
         h1, b_gn1 = ops.groupnorm_fwd(x, gn1.weight, gn1.bias, 32, gn1.eps, silu=True)
+        b_pool = None
+        if self._down:
+            h1, b_pool = ops.avgpool2x_fwd(h1)
         es, b_es = ops.silu_fwd(emb)
-        eo, b_eo = linear_module_fwd(self.emb_layers[1], es)
-        h2, b_c1 = self.in_layers[2].fwd(h1, rowvec=eo, stats_groups=32)      # the epilogue sums h2 for gn2: no statistics pass there
-        h3, b_gn2 = ops.groupnorm_fwd(h2, gn2.weight, gn2.bias, 32, gn2.eps, silu=True)
+        eo, b_eo = linear_module_fwd(self.emb_layers[1], es)          # [N, Cout], or [N, 2 Cout] = scale | shift
+        # the epilogue sums h2 for gn2: no statistics pass there
+        h2, b_c1 = self.in_layers[2].fwd(h1, rowvec=None if ssn else eo, upsample=self._up, stats_groups=32)
+        if ssn:
+            h3, b_gn2 = ops.groupnorm_mod_fwd(h2, gn2.weight, gn2.bias, eo, 32, gn2.eps, silu=True)
+        else:
+            h3, b_gn2 = ops.groupnorm_fwd(h2, gn2.weight, gn2.bias, 32, gn2.eps, silu=True)
         b_drop = None
         if self.training and self.dropout_p > 0.0:
             # out_layers = GroupNorm, SiLU, Dropout, conv: h3 is masked IN PLACE (nk_groupnorm_bwd reads its input and statistics, never its
             # output), so the convolution and its weight gradient read the dropped tensor
             _, b_drop = ops.dropout_fwd(h3.t, self.dropout_p, ops.dropout_site(self), inplace=True)
-        skip = self.skip_connection
-        b_skip = None
-        if isinstance(skip, nn.Identity):
-            s = x.t
-        elif skip.kernel_size == 1:
-            s, b_skip = ops.linear_fwd(x.t, skip.weight, skip.bias)
-        else:
-            si, b_skip3 = skip.fwd(x)
-            s, b_skip = si.t, (lambda g: b_skip3(g)[0].t)
+        s, b_skip = self._skip_fwd(x)
         out, b_c2 = self.out_layers[3].fwd(h3, residual=s, stats_groups=32)   # ... and the block's output for the GroupNorm that reads it next
 
         def bwd(dy: Tensor):
             dh3, _ = b_c2(dy)
             dh2 = b_gn2(dh3.t if b_drop is None else b_drop(dh3.t, inplace=True))
-            dh1, deo = b_c1(dh2)
+            if ssn:
+                dh2, deo = dh2                      # the emb gradient is the modulation's, [d_scale | d_shift]
+                dh1, _ = b_c1(dh2)
+            else:
+                dh1, deo = b_c1(dh2)
+            dh1 = dh1.t if b_pool is None else b_pool(dh1.t)
             dxs = dy if b_skip is None else b_skip(dy)
-            dx = b_gn1(dh1.t, dxs)
+            dx = b_gn1(dh1, dxs)
             demb = b_es(b_eo(deo))
             return dx, demb
 
@@ -297,8 +363,6 @@ class UNetModel(nn.Module):
             assert num_head_channels != -1, "UNetModel: num_heads = -1 needs num_head_channels"
         if num_head_channels == -1:
             assert num_heads != -1, "UNetModel: num_head_channels = -1 needs num_heads"
-        if resblock_updown:
-            raise NotImplementedError("resblock_updown=True is not used by the SD/SDXL configs")
         self.in_channels = in_channels
         self.model_channels = model_channels
         self.out_channels = out_channels
@@ -345,8 +409,9 @@ class UNetModel(nn.Module):
             return SpatialTransformer(ch, heads, dim_head, depth=level_depth, dropout=dropout, context_dim=context_dim, disable_self_attn=disabled_sa,
                                       use_linear=use_linear_in_transformer, attn_type=spatial_transformer_attn_type, use_checkpoint=use_checkpoint)
 
-        def res(cin, cout):
-            return ResBlock(cin, time_embed_dim, dropout, out_channels=cout, dims=dims, use_checkpoint=use_checkpoint, use_scale_shift_norm=use_scale_shift_norm)
+        def res(cin, cout, **updown):
+            return ResBlock(cin, time_embed_dim, dropout, out_channels=cout, dims=dims, use_checkpoint=use_checkpoint, use_scale_shift_norm=use_scale_shift_norm,
+                            **updown)
 
         self.input_blocks = nn.ModuleList([TimestepEmbedSequential(conv_nd(dims, in_channels, model_channels, 3, padding=1))])
         input_block_chans = [model_channels]
@@ -364,7 +429,8 @@ class UNetModel(nn.Module):
                 input_block_chans.append(ch)
             if level != len(channel_mult) - 1:
                 out_ch = ch
-                self.input_blocks.append(TimestepEmbedSequential(Downsample(ch, conv_resample, dims=dims, out_channels=out_ch)))
+                self.input_blocks.append(TimestepEmbedSequential(
+                    res(ch, out_ch, down=True) if resblock_updown else Downsample(ch, conv_resample, dims=dims, out_channels=out_ch)))
                 ch = out_ch
                 input_block_chans.append(ch)
                 ds *= 2
@@ -387,7 +453,7 @@ class UNetModel(nn.Module):
                         layers.append(make_st(ch, transformer_depth[level], disabled_sa))
                 if level and i == self.num_res_blocks[level]:
                     out_ch = ch
-                    layers.append(Upsample(ch, conv_resample, dims=dims, out_channels=out_ch))
+                    layers.append(res(ch, out_ch, up=True) if resblock_updown else Upsample(ch, conv_resample, dims=dims, out_channels=out_ch))
                     ds //= 2
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
 

@@ -727,6 +727,39 @@ def groupnorm_fwd(x: Img, weight: Tensor, bias: Tensor, groups: int, eps: float,
     return Img(y, x.N, x.H, x.W), bwd
 
 
+def groupnorm_mod_fwd(x: Img, weight: Tensor, bias: Tensor, mod: Tensor, groups: int, eps: float, silu: bool):
+    """Scale-shift modulated GroupNorm (+SiLU): y = silu?(GN(x) * (1 + scale) + shift), mod = bf16 [N, 2C] with scale in the first C columns
+    and shift in the last (ResBlock use_scale_shift_norm, openaimodel.py:332-336).  bwd(dy, dx_add=None) -> (dx token matrix, dmod [N, 2C])."""
+    if not x.t.is_contiguous():
+        raise ValueError("groupnorm_mod: x must be dense channels-last")
+    N, HW, Cc = x.N, x.H * x.W, x.C
+    _check2d(mod, "mod")
+    if tuple(mod.shape) != (N, 2 * Cc) or not mod.is_contiguous():
+        raise ValueError(f"groupnorm_mod: mod must be a dense [{N}, {2 * Cc}] (scale | shift) matrix, got {tuple(mod.shape)}")
+    y = torch.empty_like(x.t)
+    mean = torch.empty(N, groups, dtype=torch.float32, device=x.t.device)
+    rstd = torch.empty_like(mean)
+    nws = query("nk_groupnorm_ws_floats", N, HW, Cc, groups)
+    if x.sums is not None and x.sums.shape == (N, 2 * groups):
+        call("nk_groupnorm_mod_apply", x.t.data_ptr(), x.sums.data_ptr(), weight.data_ptr(), bias.data_ptr(), mod.data_ptr(), y.data_ptr(),
+             mean.data_ptr(), rstd.data_ptr(), N, HW, Cc, groups, float(eps), int(silu), _stream())
+    else:
+        ws = _ws(nws, x.t.device)
+        call("nk_groupnorm_mod_fwd", x.t.data_ptr(), weight.data_ptr(), bias.data_ptr(), mod.data_ptr(), y.data_ptr(), mean.data_ptr(),
+             rstd.data_ptr(), ws.data_ptr(), N, HW, Cc, groups, float(eps), int(silu), _stream())
+
+    def bwd(dy: Tensor, dx_add: Optional[Tensor] = None):
+        dx = torch.empty_like(x.t)
+        dmod = torch.empty_like(mod)
+        ws2 = _ws(nws, dy.device)
+        call("nk_groupnorm_mod_bwd", dy.data_ptr(), x.t.data_ptr(), weight.data_ptr(), bias.data_ptr(), mod.data_ptr(), mean.data_ptr(),
+             rstd.data_ptr(), _p(dx_add), dx.data_ptr(), grad_flat(weight).data_ptr(), grad_flat(bias).data_ptr(), dmod.data_ptr(),
+             ws2.data_ptr(), N, HW, Cc, groups, int(silu), int(state_of(weight).grad_accumulate), _stream())
+        return dx, dmod
+
+    return Img(y, x.N, x.H, x.W), bwd
+
+
 def layernorm_fwd(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5):
     """LayerNorm over the last dim of a dense token matrix.  bwd(dy, dx_add=None) -> dx."""
     _check2d(x, "x")
@@ -873,6 +906,42 @@ def maxpool2x2_fwd(x: Img):
         return dx
 
     return Img(y, x.N, x.H // 2, x.W // 2), bwd
+
+
+def avgpool2x_fwd(x: Img):
+    """avg_pool2d(2, 2) (floor mode: an odd last row or column is dropped) on channels-last tokens -- Downsample(use_conv=False) and the
+    down ResBlock (openaimodel.py:146-197).  (y Img, bwd); bwd(dy tokens) -> dx tokens, zero where the forward read nothing."""
+    if not x.t.is_contiguous():
+        raise ValueError("avgpool2x: x must be dense channels-last")
+    if x.H < 2 or x.W < 2:
+        raise ValueError(f"avgpool2x: a {x.H} x {x.W} image has no 2 x 2 window")
+    y = torch.empty(x.N * (x.H // 2) * (x.W // 2), x.C, dtype=BF16, device=x.t.device)
+    call("nk_avgpool2x_fwd", x.t.data_ptr(), y.data_ptr(), x.N, x.H, x.W, x.C, _stream())
+    N, H, W, Cc = x.N, x.H, x.W, x.C
+
+    def bwd(dy: Tensor) -> Tensor:
+        dx = torch.empty(N * H * W, Cc, dtype=BF16, device=dy.device)
+        call("nk_avgpool2x_bwd", dy.data_ptr(), dx.data_ptr(), N, H, W, Cc, _stream())
+        return dx
+
+    return Img(y, N, H // 2, W // 2), bwd
+
+
+def upsample2x_fwd(x: Img):
+    """Nearest 2x upsampling as a materialised copy -- Upsample(use_conv=False) and the skip path of the up ResBlock (where a convolution
+    follows, its gather does this for free: conv2d_fwd(upsample=True)).  (y Img, bwd); bwd(dy tokens) -> dx tokens."""
+    if not x.t.is_contiguous():
+        raise ValueError("upsample2x: x must be dense channels-last")
+    N, H, W, Cc = x.N, x.H, x.W, x.C
+    y = torch.empty(N * 4 * H * W, Cc, dtype=BF16, device=x.t.device)
+    call("nk_upsample2x_fwd", x.t.data_ptr(), y.data_ptr(), N, H, W, Cc, _stream())
+
+    def bwd(dy: Tensor) -> Tensor:
+        dx = torch.empty(N * H * W, Cc, dtype=BF16, device=dy.device)
+        call("nk_upsample2x_bwd", dy.data_ptr(), dx.data_ptr(), N, H, W, Cc, _stream())
+        return dx
+
+    return Img(y, N, 2 * H, 2 * W), bwd
 
 
 def maxpool_fwd(x: Img, kernel_size: int, stride: int):

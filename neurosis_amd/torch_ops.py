@@ -8,6 +8,8 @@ C-ABI -- but every kernel family is ALSO a dispatcher-visible
     torch.ops.neurosis_hip.linear(x, w, bias)                      differentiable (autograd -> _dgrad / _wgrad ops)
     torch.ops.neurosis_hip.layernorm(x, gamma, beta, eps)           "
     torch.ops.neurosis_hip.groupnorm_silu(x, gamma, beta, N, groups, eps, silu)
+    torch.ops.neurosis_hip.groupnorm_mod(x, gamma, beta, mod, N, groups, eps, silu)     scale-shift norm; also differentiable in mod
+    torch.ops.neurosis_hip.avgpool2x(x, N, H, W) / upsample2x_nearest(x, N, H, W)       the parameter-free resamplers
     torch.ops.neurosis_hip.geglu(u)                                 "
     torch.ops.neurosis_hip.attention(q, k, v, B, heads)             "
     torch.ops.neurosis_hip.conv2d(x, w, bias, N, H, W, stride, padding)     channels-last tokens in / out
@@ -235,6 +237,70 @@ def _gn_bwd(ctx, dy):
 
 
 groupnorm_silu.register_autograd(_gn_bwd, setup_context=_gn_setup)
+
+
+# ... with the per-image scale-shift modulation of the ADM ResBlock: y = silu?(GN(x) * (1 + mod[:, :C]) + mod[:, C:]), mod bf16 [N, 2C]
+@_op("groupnorm_mod_fwd")
+def groupnorm_mod_fwd(x: Tensor, gamma: Tensor, beta: Tensor, mod: Tensor, N: int, groups: int, eps: float, silu: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    HW, C = x.shape[0] // N, x.shape[1]
+    y = torch.empty_like(x)
+    mean = torch.empty(N, groups, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    ws = ops._ws(ops.query("nk_groupnorm_ws_floats", N, HW, C, groups), x.device)
+    ops.call("nk_groupnorm_mod_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mod.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(),
+             N, HW, C, groups, float(eps), int(silu), ops._stream())
+    return y, mean, rstd
+
+
+@groupnorm_mod_fwd.register_fake
+def _(x, gamma, beta, mod, N, groups, eps, silu):
+    return torch.empty_like(x), x.new_empty(N, groups, dtype=torch.float32), x.new_empty(N, groups, dtype=torch.float32)
+
+
+@_op("groupnorm_mod_bwd")
+def groupnorm_mod_bwd(dy: Tensor, x: Tensor, gamma: Tensor, beta: Tensor, mod: Tensor, mean: Tensor, rstd: Tensor, N: int, groups: int,
+                      silu: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    HW, C = x.shape[0] // N, x.shape[1]
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty_like(dg)
+    dmod = torch.empty_like(mod)
+    ws = ops._ws(ops.query("nk_groupnorm_ws_floats", N, HW, C, groups), x.device)
+    ops.call("nk_groupnorm_mod_bwd", dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mod.data_ptr(), mean.data_ptr(), rstd.data_ptr(), None,
+             dx.data_ptr(), dg.data_ptr(), db.data_ptr(), dmod.data_ptr(), ws.data_ptr(), N, HW, C, groups, int(silu), 0, ops._stream())
+    return dx, dg, db, dmod
+
+
+@groupnorm_mod_bwd.register_fake
+def _(dy, x, gamma, beta, mod, mean, rstd, N, groups, silu):
+    return torch.empty_like(x), gamma.new_empty(gamma.shape, dtype=torch.float32), gamma.new_empty(gamma.shape, dtype=torch.float32), torch.empty_like(mod)
+
+
+@_op("groupnorm_mod")
+def groupnorm_mod(x: Tensor, gamma: Tensor, beta: Tensor, mod: Tensor, N: int, groups: int, eps: float, silu: bool) -> Tensor:
+    return torch.ops.neurosis_hip.groupnorm_mod_fwd(x, gamma, beta, mod, N, groups, eps, silu)[0]
+
+
+@groupnorm_mod.register_fake
+def _(x, gamma, beta, mod, N, groups, eps, silu):
+    return torch.empty_like(x)
+
+
+def _gnm_setup(ctx, inputs, output):
+    x, gamma, beta, mod, N, groups, eps, silu = inputs
+    _, mean, rstd = torch.ops.neurosis_hip.groupnorm_mod_fwd(x, gamma, beta, mod, N, groups, eps, silu)
+    ctx.save_for_backward(x, gamma, beta, mod, mean, rstd)
+    ctx.meta = (N, groups, silu)
+
+
+def _gnm_bwd(ctx, dy):
+    x, gamma, beta, mod, mean, rstd = ctx.saved_tensors
+    N, groups, silu = ctx.meta
+    dx, dg, db, dmod = torch.ops.neurosis_hip.groupnorm_mod_bwd(dy.contiguous(), x, gamma, beta, mod, mean, rstd, N, groups, silu)
+    return dx, dg, db, dmod, None, None, None, None
+
+
+groupnorm_mod.register_autograd(_gnm_bwd, setup_context=_gnm_setup)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -528,6 +594,53 @@ def _(dup, N, H, W):
     return dup.new_empty(N * H * W, dup.shape[1])
 
 
+@_op("upsample2x_nearest")
+def upsample2x_nearest(x: Tensor, N: int, H: int, W: int) -> Tensor:
+    """Upsample.forward without its conv (openaimodel.py:126-143, use_conv=False): x [N*H*W, C] -> [N*2H*2W, C]"""
+    up = torch.empty(N * 4 * H * W, x.shape[1], dtype=BF16, device=x.device)
+    ops.call("nk_upsample2x_fwd", x.data_ptr(), up.data_ptr(), N, H, W, x.shape[1], ops._stream())
+    return up
+
+
+@upsample2x_nearest.register_fake
+def _(x, N, H, W):
+    return x.new_empty(N * 4 * H * W, x.shape[1])
+
+
+upsample2x_nearest.register_autograd(lambda ctx, dup: (torch.ops.neurosis_hip.upsample2x_nearest_bwd(dup.contiguous(), *ctx.geom), None, None, None),
+                                     setup_context=lambda ctx, inputs, output: setattr(ctx, "geom", inputs[1:]))
+
+
+@_op("avgpool2x")
+def avgpool2x(x: Tensor, N: int, H: int, W: int) -> Tensor:
+    """Downsample.forward without its conv (openaimodel.py:183-197, use_conv=False): avg_pool2d(2, 2), x [N*H*W, C] -> [N*(H//2)*(W//2), C]"""
+    y = torch.empty(N * (H // 2) * (W // 2), x.shape[1], dtype=BF16, device=x.device)
+    ops.call("nk_avgpool2x_fwd", x.data_ptr(), y.data_ptr(), N, H, W, x.shape[1], ops._stream())
+    return y
+
+
+@avgpool2x.register_fake
+def _(x, N, H, W):
+    return x.new_empty(N * (H // 2) * (W // 2), x.shape[1])
+
+
+@_op("avgpool2x_bwd")
+def avgpool2x_bwd(dy: Tensor, N: int, H: int, W: int) -> Tensor:
+    """dy [N*(H//2)*(W//2), C] -> dx [N*H*W, C]: a quarter of each window's gradient to its four inputs, zeros in a dropped odd row / column"""
+    dx = torch.empty(N * H * W, dy.shape[1], dtype=BF16, device=dy.device)
+    ops.call("nk_avgpool2x_bwd", dy.data_ptr(), dx.data_ptr(), N, H, W, dy.shape[1], ops._stream())
+    return dx
+
+
+@avgpool2x_bwd.register_fake
+def _(dy, N, H, W):
+    return dy.new_empty(N * H * W, dy.shape[1])
+
+
+avgpool2x.register_autograd(lambda ctx, dy: (torch.ops.neurosis_hip.avgpool2x_bwd(dy.contiguous(), *ctx.geom), None, None, None),
+                            setup_context=lambda ctx, inputs, output: setattr(ctx, "geom", inputs[1:]))
+
+
 @_op("upsample2x_nearest_conv")
 def upsample2x_nearest_conv(x: Tensor, w: Tensor, bias: Optional[Tensor], N: int, H: int, W: int) -> Tensor:
     """Upsample.forward with use_conv (openaimodel.py:126-143): nearest x2 then 3 x 3 / padding 1 conv, the upsampled map never written"""
@@ -746,7 +859,7 @@ dropout.register_autograd(lambda ctx, dy: (torch.ops.neurosis_hip.dropout(dy.con
                                                                      setattr(ctx, "site", inputs[3]), setattr(ctx, "has_residual", inputs[4] is not None)))
 
 
-OPS = ("dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
+OPS = ("groupnorm_mod_fwd", "groupnorm_mod_bwd", "groupnorm_mod", "upsample2x_nearest", "avgpool2x", "avgpool2x_bwd", "dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
        "flat_allreduce_start", "flat_allreduce_wait", "conv2d_fwd_stats", "linear_dgrad_geglu", "linear_fwd_geglu", "linear_fwd", "linear_dgrad", "linear_wgrad", "colsum", "linear", "layernorm_fwd", "layernorm_bwd", "layernorm", "groupnorm_silu_fwd",
        "groupnorm_silu_bwd", "groupnorm_silu", "geglu_fwd", "geglu_bwd", "geglu", "attention_fwd", "attention_bwd", "attention", "conv2d_fwd",
        "conv2d_dgrad", "conv2d_wgrad", "conv2d", "timestep_embedding", "nchw_to_nlc", "nlc_to_nchw")
