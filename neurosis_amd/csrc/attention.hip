@@ -17,6 +17,7 @@
 //           dK/dV kernel (keys on lanes, loops over query tiles, no atomics).  P is recomputed from LSE.
 #include "../../include/neurosis_hip.h"
 #include "nk_common.h"
+#include "attn_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -53,13 +54,7 @@ __device__ __forceinline__ void attn_wg(const AttnParams& p, int& bx, int& hd, i
   b = t / p.H;
   hd = t - b * p.H;
 }
-// the grid to launch for the 3-D extent `g` (sets p.gx); NK_ATTN_XCD=0 keeps the 3-D grid (A/B runs)
-static dim3 attn_grid(AttnParams& p, dim3 g) {
-  const char* e = getenv("NK_ATTN_XCD");
-  if (e && e[0] == '0') { p.gx = 0; return g; }
-  p.gx = (int)g.x;
-  return dim3(g.x * g.y * g.z, 1, 1);
-}
+// (which grid a launch gets, and its p.gx: attn_plan.h, attn_launch)
 
 #define LOG2E 1.4426950408889634f
 #define NEG_BIG (-1.0e30f)
@@ -721,15 +716,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attn64_fwd_kernel(const AttnParams
 // dS = p * (dP - delta)  (a second block for -delta does not fit the 168 registers of three waves per SIMD).  Also written out for the dK / dV kernel, which runs behind this one: -delta, -LSE * log2(e) (what ITS chains start
 // from, fetched by DMA) and Q' itself as [B][H][Lq][64] (its A operand: both kernels then see bit-identical scores, and so does the
 // forward's LSE).
-struct Attn64Ws {       // layout of the backward workspace (floats) for head dim 64
-  long ndelta, nlse2, qs, part;
-  __host__ __device__ static Attn64Ws make(long B, long H, long Lq) {
-    Attn64Ws w;
-    const long n = (B * H * Lq + 63) & ~63l;
-    w.ndelta = 0; w.nlse2 = n; w.qs = 2 * n; w.part = 2 * n + B * H * Lq * 32;
-    return w;
-  }
-};
+// (Attn64Ws, the layout of the workspace: attn_plan.h)
 template <int NW = 4>
 __global__ __launch_bounds__(NW * 64, 3) void attn64_bwd_dq_kernel(const AttnParams p) {
   constexpr int TILE = 64 * 128, STAGE = 2 * TILE;
@@ -1114,7 +1101,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attn64_bwd_dkdv_kernel(const AttnP
 // dK / dV leave as fp32 partials per query split (summed by attn_dkv_reduce_kernel) or, with one split, directly.
 // CAUSAL (the trainable text towers' self-attention, Lq == Lk <= 96, nk_attention_bwd_causal): P recomputed from the causal forward's
 // log-sum-exp is zeroed where key j > query i, which zeroes dS there too (dS = P o (dP - delta)); every other step is the same.
-#define SMALL_DSROW 72                               // bytes per row of the dS^T image [96 keys][32 queries] (64 + 8: conflict-free 8-byte writes)
+// (SMALL_DSROW, bytes per row of the dS^T image [96 keys][32 queries]: attn_plan.h)
 template <bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void attn64_bwd_small_kernel(const AttnParams p) {
   constexpr int TILE = 32 * 128, STAGE = 3 * TILE + 256 + 1024;   // Q' image, dO image, [32] -lse2, [32] -delta | O rows | 4 x 256 B raw log-sum-exp
@@ -1726,265 +1713,127 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_bwd_dq_kernel(const AttnParam
 // ================================================================================================
 #include "attn512.h"
 #include "attn512_bwd.h"
+static_assert(ATTN512_BWD_ROWS == A5B_ROWS && ATTN512_BWD_SMEM == A5B_SMEM, "attn_plan.h restates attn512_bwd.h's tile");
 
-static int attn_check(const NkAttnDesc* d) {
+// the family's switches, read per call (tests and A/B runs flip them in-process) -- here and nowhere else
+static AttnEnv attn_env() {
+  const char *x = getenv("NK_ATTN_XCD"), *a = getenv("NK_ATTN64"), *s = getenv("NK_ATTN64_SMALL");
+  return AttnEnv{!(x && x[0] == '0'), !a || atoi(a) != 0, !s || atoi(s) != 0};
+}
+
+static int attn_check(const NkAttnDesc* d, int pass) {
   NK_CHECK_ARG(d != nullptr);
   NK_CHECK_ARG(d->B > 0 && d->H > 0 && d->Lq > 0 && d->Lk > 0 && d->D > 0);
   NK_CHECK_ARG((d->D & 7) == 0 && (d->D <= 160 || d->D == 512));     // 512: attn512.h (forward), attn512_bwd.h (backward)
   NK_CHECK_ARG((d->sq & 7) == 0 && (d->sk & 7) == 0 && (d->sv & 7) == 0 && (d->so & 7) == 0);
   NK_CHECK_ARG((d->bq & 7) == 0 && (d->bk & 7) == 0 && (d->bv & 7) == 0 && (d->bo & 7) == 0);
   NK_CHECK_ARG(d->B <= 65535 && d->H <= 65535);
+  if (pass == ATTN_PASS_FWD) return NK_OK;
+  NK_CHECK_ARG((d->sdq & 7) == 0 && (d->sdk & 7) == 0 && (d->sdv & 7) == 0 && (d->sdo & 7) == 0);
+  NK_CHECK_ARG((d->bdq & 7) == 0 && (d->bdk & 7) == 0 && (d->bdv & 7) == 0 && (d->bdo & 7) == 0);
   return NK_OK;
 }
-static int attn_dp(int D) { return D <= 64 ? 64 : (D <= 96 ? 96 : 160); }
-// waves per workgroup: 4 x 32 rows.  (A 2-wave variant -- twice the workgroups for SDXL's L = 1024 layers, which give only 640 -- was
-// measured SLOWER: forward 72 vs 65 us, backward 200 vs 181 us, twice the K/V tile loads per query row and half the waves sharing a tile.)
-static constexpr int ATTN_NW = 4;
 
-// NK_ATTN64=0: the generic kernels for head dim 64 as well (A/B switch of round 4; read per call)
-static bool attn64_enabled() {
-  const char* e = getenv("NK_ATTN64");
-  return !e || atoi(e) != 0;
+// the kernels' parameters from the descriptor and the caller's pointers ptr[AttnPtr] (null where the pass has none); the launcher adds gx
+static AttnParams attn_params(const NkAttnDesc* d, const NkAttnPlan& pl, void* const* ptr) {
+  AttnParams p = {};
+  p.Q = (const bf16_t*)ptr[AP_Q]; p.K = (const bf16_t*)ptr[AP_K]; p.V = (const bf16_t*)ptr[AP_V];
+  p.O = (bf16_t*)ptr[AP_O]; p.Oc = (const bf16_t*)ptr[AP_O];      // written by the forward, read by the backward
+  p.dO = (const bf16_t*)ptr[AP_DO]; p.dQ = (bf16_t*)ptr[AP_DQ]; p.dK = (bf16_t*)ptr[AP_DK]; p.dV = (bf16_t*)ptr[AP_DV];
+  p.LSE = (float*)ptr[AP_LSE]; p.delta = (float*)ptr[AP_WS];
+  p.B = d->B; p.H = d->H; p.Lq = d->Lq; p.Lk = d->Lk; p.D = d->D;
+  p.sq = d->sq; p.sk = d->sk; p.sv = d->sv; p.so = d->so;
+  p.bq = d->bq; p.bk = d->bk; p.bv = d->bv; p.bo = d->bo;
+  p.sdq = d->sdq; p.sdk = d->sdk; p.sdv = d->sdv; p.sdo = d->sdo;
+  p.bdq = d->bdq; p.bdk = d->bdk; p.bdv = d->bdv; p.bdo = d->bdo;
+  p.scale = d->scale;
+  p.causal = d->causal != 0;
+  p.qsplit = pl.qsplit;
+  p.dkv_part = pl.qsplit > 1 ? p.delta + pl.ws.part : nullptr;
+  return p;
 }
+
 template <typename K>
-static void set_smem(K kern, int bytes) {
-  nk_optin_lds((const void*)kern, bytes);
+static void attn_launch_kernel(K kern, const NkAttnLaunch& L, hipStream_t stream, const AttnParams& p) {
+  if (L.smem) nk_optin_lds((const void*)kern, L.smem);
+  hipLaunchKernelGGL(kern, dim3(L.grid[0], L.grid[1], L.grid[2]), dim3(L.block), L.smem, stream, p);
+}
+// the plan's launches, in order
+static int attn_run(const NkAttnPlan& pl, AttnParams p, hipStream_t stream) {
+  for (int i = 0; i < pl.n; ++i) {
+    const NkAttnLaunch& L = pl.launch[i];
+    p.gx = L.gx;
+    switch (L.kernel) {
+#define ATTN_KERNEL(id, ...) case id: attn_launch_kernel(__VA_ARGS__, L, stream, p); break;
+      ATTN_KERNEL(AK_FWD64, attn64_fwd_kernel<ATTN_NW>)
+      ATTN_KERNEL(AK_FWD_DP64, attn_fwd_kernel<64, ATTN_NW>)
+      ATTN_KERNEL(AK_FWD_DP96, attn_fwd_kernel<96, ATTN_NW>)
+      ATTN_KERNEL(AK_FWD_DP160, attn_fwd_kernel<160, ATTN_NW>)
+      ATTN_KERNEL(AK_FWD512, attn512_fwd_kernel)
+      ATTN_KERNEL(AK_BWD64_SMALL, attn64_bwd_small_kernel<false>)
+      ATTN_KERNEL(AK_BWD64_SMALL_CAUSAL, attn64_bwd_small_kernel<true>)
+      ATTN_KERNEL(AK_BWD64_DQ, attn64_bwd_dq_kernel<ATTN_NW>)
+      ATTN_KERNEL(AK_BWD64_DKDV, attn64_bwd_dkdv_kernel<ATTN_NW>)
+      ATTN_KERNEL(AK_BWD_DQ_DP64, attn_bwd_dq_kernel<64, ATTN_NW>)
+      ATTN_KERNEL(AK_BWD_DQ_DP96, attn_bwd_dq_kernel<96, ATTN_NW>)
+      ATTN_KERNEL(AK_BWD_DQ_DP160, attn_bwd_dq_kernel<160, ATTN_NW>)
+      ATTN_KERNEL(AK_BWD_DKDV_DP64, attn_bwd_dkdv_kernel<64, ATTN_NW>)
+      ATTN_KERNEL(AK_BWD_DKDV_DP96, attn_bwd_dkdv_kernel<96, ATTN_NW>)
+      ATTN_KERNEL(AK_BWD_DKDV_DP160, attn_bwd_dkdv_kernel<160, ATTN_NW>)
+      ATTN_KERNEL(AK_DKV_REDUCE, attn_dkv_reduce_kernel)
+      ATTN_KERNEL(AK_DELTA512, attn512_delta_kernel)
+      ATTN_KERNEL(AK_BWD512_DQ, attn512_bwd_kernel<0>)
+      ATTN_KERNEL(AK_BWD512_DKDV, attn512_bwd_kernel<1>)
+#undef ATTN_KERNEL
+    }
+    if (int e = nk_check_launch(L.name)) return e;
+  }
+  return NK_OK;
+}
+
+// One pass: check the descriptor, plan, check what the plan says about shape and pointers, fill the parameters, launch.  In plan-only mode
+// (nk_debug_launch_log(3)) the plan is the answer: name and plan line per launch, and nothing touches the device or the pointers.
+static int attn_pass(const NkAttnDesc* d, int pass, void* const* ptr, void* stream) {
+  if (int e = attn_check(d, pass)) return e;
+  const NkAttnPlan pl = nk_attn_plan(d, pass, attn_env());
+  if (pl.err) {
+    nk_set_error(__FILE__, __LINE__, pl.err);
+    return NK_ERR_ARG;
+  }
+  if (nk_launch_log_mode() == 3) {
+    char line[192];
+    for (int i = 0; i < pl.n; ++i) {
+      nk_attn_plan_line(pl, i, line, sizeof(line));
+      nk_launch_log_add(pl.launch[i].name, line);
+    }
+    return NK_OK;
+  }
+  for (int i = 0; i < AP_N; ++i) {
+    if (pl.need >> i & 1) NK_CHECK_ARG(ptr[i] != nullptr);
+    if (pl.align16 >> i & 1) NK_CHECK_ARG(((uintptr_t)ptr[i] & 15) == 0);      // 16-byte loads and stores
+  }
+  return attn_run(pl, attn_params(d, pl, ptr), (hipStream_t)stream);
 }
 
 extern "C" int nk_attention_fwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, void* o, float* lse,
-                                void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (int e = attn_check(d)) return e;
-  NK_CHECK_ARG(q && k && v && o && (lse || d->D == 512));
-  AttnParams p = {};
-  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)o; p.LSE = lse;
-  p.B = d->B; p.H = d->H; p.Lq = d->Lq; p.Lk = d->Lk; p.D = d->D;
-  p.sq = d->sq; p.sk = d->sk; p.sv = d->sv; p.so = d->so;
-  p.bq = d->bq; p.bk = d->bk; p.bv = d->bv; p.bo = d->bo;
-  p.scale = d->scale;
-  p.causal = d->causal != 0;
-  NK_CHECK_ARG(!d->causal || d->Lq == d->Lk);
-  constexpr int nw = ATTN_NW;
-  dim3 grid((d->Lq + nw * 32 - 1) / (nw * 32), d->H, d->B);
-  const dim3 lgrid = attn_grid(p, grid);       // 1-D, XCD-aware (attn_wg)
-  if (d->D == 512 || (d->D == 64 && attn64_enabled())) NK_CHECK_ARG(((uintptr_t)o & 15) == 0);      // 16-byte output stores
-  if (d->D == 512) {
-    // the VAE mid block's single head: one workgroup per CU, 512 registers per lane, all 160 KiB of LDS (attn512.h); lse may be null
-    NK_CHECK_ARG(!d->causal);
-    const int smem512 = 5 * 32 * 1024;
-    set_smem(attn512_fwd_kernel, smem512);
-    hipLaunchKernelGGL(attn512_fwd_kernel, lgrid, dim3(256), smem512, stream, p);
-    return nk_check_launch("attn512_fwd_kernel");
-  }
-  const int dp = attn_dp(d->D);
-  const int smem = 2 * 2 * 64 * (dp * 2 + 16);
-#define FWD_CASE(DP_)                                                                          \
-  if (dp == DP_) {                                                                             \
-    set_smem(attn_fwd_kernel<DP_, ATTN_NW>, smem);                                                \
-    hipLaunchKernelGGL((attn_fwd_kernel<DP_, ATTN_NW>), lgrid, dim3(ATTN_NW * 64), smem, stream, p); \
-  }
-  if (d->D == 64 && attn64_enabled()) {
-    const int smem64 = 3 * 2 * 64 * 128;
-    set_smem(attn64_fwd_kernel<ATTN_NW>, smem64);
-    hipLaunchKernelGGL((attn64_fwd_kernel<ATTN_NW>), lgrid, dim3(ATTN_NW * 64), smem64, stream, p);
-    return nk_check_launch("attn64_fwd_kernel");
-  }
-  FWD_CASE(64) FWD_CASE(96) FWD_CASE(160)
-#undef FWD_CASE
-  return nk_check_launch("attn_fwd_kernel");
+                                void* stream) {
+  void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, o, lse};
+  return attn_pass(d, ATTN_PASS_FWD, ptr, stream);
 }
 
-// NK_ATTN64_SMALL=0: cross-attention backward through the two-kernel path (A/B switch of round 4; read per call)
-static bool attn64_small_enabled() {
-  const char* e = getenv("NK_ATTN64_SMALL");
-  return !e || atoi(e) != 0;
-}
-// query splits of the one-kernel backward: enough workgroups for the chip (two per CU fit), at least two 32-query tiles each
-static int attn_small_qsplit(const NkAttnDesc* d) {
-  const int base = d->B * d->H;
-  int s = 1;
-  while (s < 64 && base * s * 2 <= 512 && d->Lq / (s * 2) >= 64) s *= 2;      // (at most one round of two workgroups per CU)
-  return s;
-}
-static int attn_qsplit(const NkAttnDesc* d) {
-  // a single key block (cross-attention, Lk = 77) gives only B*H workgroups that each walk the whole query range:
-  // split the query range so the grid has >= ~512 workgroups
-  if (d->Lk > 128 || d->Lq < 512) return 1;
-  int base = d->B * d->H;
-  int s = 1;
-  while (s < 16 && base * s < 512 && d->Lq / (s * 2) >= 128) s *= 2;
-  return s;
-}
-#define ATTN64_SMALL_SMEM (96 * 128 + 3 * (3 * 32 * 128 + 256 + 1024) + 2 * 96 * SMALL_DSROW)
-extern "C" long nk_attention_bwd_ws_floats(const NkAttnDesc* d) {
-  int s = attn_qsplit(d);
-  if (d->D == 64 && d->Lk <= 96 && attn_small_qsplit(d) > s) s = attn_small_qsplit(d);
-  long part = s > 1 ? (long)s * 2 * d->B * d->Lk * d->H * d->D : 0;
-  if (d->D == 64) return Attn64Ws::make(d->B, d->H, d->Lq).part + part + 64;     // -delta, -lse2, Q' (whichever kernels run)
-  long delta = (long)d->B * d->H * d->Lq;
-  return delta + part + 64;
-}
+extern "C" long nk_attention_bwd_ws_floats(const NkAttnDesc* d) { return attn_ws(d, d->D == 64).total; }
 
 extern "C" int nk_attention_bwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, const void* o,
                                 const float* lse, const void* d_o, void* dq, void* dk, void* dv, float* delta_ws,
-                                void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (int e = attn_check(d)) return e;
-  NK_CHECK_ARG(q && k && v && o && lse && d_o && dq && dk && dv && delta_ws);
-  NK_CHECK_ARG(!d->causal);   // the causal variant serves the frozen text encoders: forward only
-  NK_CHECK_ARG((d->sdq & 7) == 0 && (d->sdk & 7) == 0 && (d->sdv & 7) == 0 && (d->sdo & 7) == 0);
-  NK_CHECK_ARG((d->bdq & 7) == 0 && (d->bdk & 7) == 0 && (d->bdv & 7) == 0 && (d->bdo & 7) == 0);
-  AttnParams p = {};
-  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.Oc = (const bf16_t*)o;
-  p.dO = (const bf16_t*)d_o; p.dQ = (bf16_t*)dq; p.dK = (bf16_t*)dk; p.dV = (bf16_t*)dv;
-  p.LSE = (float*)lse; p.delta = delta_ws;
-  p.B = d->B; p.H = d->H; p.Lq = d->Lq; p.Lk = d->Lk; p.D = d->D;
-  p.sq = d->sq; p.sk = d->sk; p.sv = d->sv; p.so = d->so;
-  p.bq = d->bq; p.bk = d->bk; p.bv = d->bv; p.bo = d->bo;
-  p.sdq = d->sdq; p.sdk = d->sdk; p.sdv = d->sdv; p.sdo = d->sdo;
-  p.bdq = d->bdq; p.bdk = d->bdk; p.bdv = d->bdv; p.bdo = d->bdo;
-  p.scale = d->scale;
-  if (d->D == 512) {
-    // head dim 512 (the VAE mid block under autoencoder training): delta = rowsum(dO o O), then the same kernel template twice --
-    // dQ per 32-query block, dK / dV per 32-key block -- recomputing the scores tile by tile from the forward's log-sum-exp (attn512_bwd.h)
-    NK_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 15) == 0 && ((uintptr_t)d_o & 15) == 0);
-    {
-      const long rows = (long)d->B * d->H * d->Lq;
-      hipLaunchKernelGGL(attn512_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, p);
-      if (int e = nk_check_launch("attn512_delta_kernel")) return e;
-    }
-    set_smem(attn512_bwd_kernel<0>, A5B_SMEM);
-    set_smem(attn512_bwd_kernel<1>, A5B_SMEM);
-    hipLaunchKernelGGL(attn512_bwd_kernel<0>, dim3((d->Lq + A5B_ROWS - 1) / A5B_ROWS, d->H, d->B), dim3(256), A5B_SMEM, stream, p);
-    if (int e = nk_check_launch("attn512_bwd_kernel<0>")) return e;
-    hipLaunchKernelGGL(attn512_bwd_kernel<1>, dim3((d->Lk + A5B_ROWS - 1) / A5B_ROWS, d->H, d->B), dim3(256), A5B_SMEM, stream, p);
-    return nk_check_launch("attn512_bwd_kernel<1>");
-  }
-  NK_CHECK_ARG(d->D <= 160);
-  if (d->D == 64 && attn64_enabled())      // 16-byte gradient stores
-    NK_CHECK_ARG(((uintptr_t)dq & 15) == 0 && ((uintptr_t)dk & 15) == 0 && ((uintptr_t)dv & 15) == 0);
-  if (d->D == 64 && d->Lk <= 96 && attn64_enabled() && attn64_small_enabled()) {
-    // head dim 64, at most 96 keys (cross-attention): everything in one kernel (+ the sum of the query splits' dK / dV partials)
-    NK_CHECK_ARG(((uintptr_t)delta_ws & 15) == 0);
-    const Attn64Ws w = Attn64Ws::make(d->B, d->H, d->Lq);
-    p.qsplit = attn_small_qsplit(d);
-    p.dkv_part = p.qsplit > 1 ? delta_ws + w.part : nullptr;
-    const int smem = ATTN64_SMALL_SMEM;
-    set_smem(attn64_bwd_small_kernel<false>, smem);
-    const dim3 lgrid = attn_grid(p, dim3(p.qsplit, d->H, d->B));
-    hipLaunchKernelGGL(attn64_bwd_small_kernel<false>, lgrid, dim3(256), smem, stream, p);
-    if (int e = nk_check_launch("attn64_bwd_small_kernel")) return e;
-    if (p.qsplit > 1) {
-      long total = (long)d->B * d->Lk * ((long)d->H * d->D / 4);
-      long blocks = (total + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, p);
-      if (int e = nk_check_launch("attn_dkv_reduce_kernel")) return e;
-    }
-    return NK_OK;
-  }
-  if (d->D == 64 && attn64_enabled()) {
-    // head dim 64: the dQ kernel (which also writes -delta, -lse2 and Q' into the workspace), then dK / dV
-    NK_CHECK_ARG(((uintptr_t)delta_ws & 15) == 0);
-    const Attn64Ws w = Attn64Ws::make(d->B, d->H, d->Lq);
-    constexpr int nw = ATTN_NW;
-    {
-      dim3 grid((d->Lq + nw * 32 - 1) / (nw * 32), d->H, d->B);
-      const dim3 lgrid = attn_grid(p, grid);       // 1-D, XCD-aware (attn_wg)
-      const int smem = 3 * 2 * 64 * 128;
-      set_smem(attn64_bwd_dq_kernel<ATTN_NW>, smem);
-      hipLaunchKernelGGL((attn64_bwd_dq_kernel<ATTN_NW>), lgrid, dim3(nw * 64), smem, stream, p);
-      if (int e = nk_check_launch("attn64_bwd_dq_kernel")) return e;
-    }
-    p.qsplit = attn_qsplit(d);
-    p.dkv_part = p.qsplit > 1 ? delta_ws + w.part : nullptr;
-    {
-      dim3 grid(((d->Lk + nw * 32 - 1) / (nw * 32)) * p.qsplit, d->H, d->B);
-      const dim3 lgrid = attn_grid(p, grid);       // 1-D, XCD-aware (attn_wg)
-      const int smem = 3 * (2 * 32 * 128 + 256);
-      set_smem(attn64_bwd_dkdv_kernel<ATTN_NW>, smem);
-      hipLaunchKernelGGL((attn64_bwd_dkdv_kernel<ATTN_NW>), lgrid, dim3(nw * 64), smem, stream, p);
-      if (int e = nk_check_launch("attn64_bwd_dkdv_kernel")) return e;
-    }
-    if (p.qsplit > 1) {
-      long total = (long)d->B * d->Lk * ((long)d->H * d->D / 4);
-      long blocks = (total + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, p);
-      if (int e = nk_check_launch("attn_dkv_reduce_kernel")) return e;
-    }
-    return NK_OK;
-  }
-  // order: dQ kernel first (it also produces delta = rowsum(dO * O) for the dK / dV kernel), then dK / dV
-  const int dp = attn_dp(d->D);
-  {
-    constexpr int nw = ATTN_NW;
-    dim3 grid((d->Lq + nw * 32 - 1) / (nw * 32), d->H, d->B);
-    const dim3 lgrid = attn_grid(p, grid);       // 1-D, XCD-aware (attn_wg)
-    const int smem = 2 * 2 * 64 * (dp * 2 + 16);
-#define Q_CASE(DP_)                                                                          \
-  if (dp == DP_) {                                                                             \
-    set_smem(attn_bwd_dq_kernel<DP_, ATTN_NW>, smem);                                                \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DP_, ATTN_NW>), lgrid, dim3(ATTN_NW * 64), smem, stream, p); \
-  }
-    Q_CASE(64) Q_CASE(96) Q_CASE(160)
-#undef Q_CASE
-  }
-  if (int e = nk_check_launch("attn_bwd_dq_kernel")) return e;
-  p.qsplit = attn_qsplit(d);
-  p.dkv_part = p.qsplit > 1 ? delta_ws + (((long)d->B * d->H * d->Lq + 3) & ~3l) : nullptr;
-  {
-    constexpr int nw = ATTN_NW;
-    dim3 grid(((d->Lk + nw * 32 - 1) / (nw * 32)) * p.qsplit, d->H, d->B);
-    const dim3 lgrid = attn_grid(p, grid);       // 1-D, XCD-aware (attn_wg)
-    const int smem = 2 * (2 * 32 * (dp * 2 + 16) + 256);
-#define KV_CASE(DP_)                                                                          \
-  if (dp == DP_) {                                                                             \
-    set_smem(attn_bwd_dkdv_kernel<DP_, ATTN_NW>, smem);                                                \
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DP_, ATTN_NW>), lgrid, dim3(ATTN_NW * 64), smem, stream, p); \
-  }
-    KV_CASE(64) KV_CASE(96) KV_CASE(160)
-#undef KV_CASE
-    if (int e = nk_check_launch("attn_bwd_dkdv_kernel")) return e;
-    if (p.qsplit > 1) {
-      long total = (long)d->B * d->Lk * ((long)d->H * d->D / 4);
-      long blocks = (total + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, p);
-      if (int e = nk_check_launch("attn_dkv_reduce_kernel")) return e;
-    }
-  }
-  return NK_OK;
+                                void* stream) {
+  void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, (void*)o, (void*)lse, (void*)d_o, dq, dk, dv, delta_ws};
+  return attn_pass(d, ATTN_PASS_BWD, ptr, stream);
 }
 
 // Backward of the CAUSAL forward (nk_attention_fwd with d->causal): the text towers when they are trained (configs/sdxl/sdxl-te.example.yaml).
-// Head dim 64, Lq == Lk <= 96 (77 tokens): the one-kernel backward above in its causal instantiation, one query split, so dK / dV leave
-// directly and no workspace is needed.  nk_attention_bwd keeps refusing causal descriptors.
+// nk_attention_bwd keeps refusing causal descriptors.
 extern "C" int nk_attention_bwd_causal(const NkAttnDesc* d, const void* q, const void* k, const void* v, const void* o,
-                                       const float* lse, const void* d_o, void* dq, void* dk, void* dv, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (int e = attn_check(d)) return e;
-  NK_CHECK_ARG(q && k && v && o && lse && d_o && dq && dk && dv);
-  NK_CHECK_ARG(d->causal && d->D == 64 && d->Lq == d->Lk && d->Lk <= 96);
-  NK_CHECK_ARG((d->sdq & 7) == 0 && (d->sdk & 7) == 0 && (d->sdv & 7) == 0 && (d->sdo & 7) == 0);
-  NK_CHECK_ARG((d->bdq & 7) == 0 && (d->bdk & 7) == 0 && (d->bdv & 7) == 0 && (d->bdo & 7) == 0);
-  NK_CHECK_ARG(((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && ((uintptr_t)v & 15) == 0 && ((uintptr_t)o & 15) == 0 &&
-               ((uintptr_t)d_o & 15) == 0);
-  NK_CHECK_ARG(((uintptr_t)dq & 15) == 0 && ((uintptr_t)dk & 15) == 0 && ((uintptr_t)dv & 15) == 0);
-  AttnParams p = {};
-  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.Oc = (const bf16_t*)o;
-  p.dO = (const bf16_t*)d_o; p.dQ = (bf16_t*)dq; p.dK = (bf16_t*)dk; p.dV = (bf16_t*)dv;
-  p.LSE = (float*)lse;
-  p.B = d->B; p.H = d->H; p.Lq = d->Lq; p.Lk = d->Lk; p.D = d->D;
-  p.sq = d->sq; p.sk = d->sk; p.sv = d->sv; p.so = d->so;
-  p.bq = d->bq; p.bk = d->bk; p.bv = d->bv; p.bo = d->bo;
-  p.sdq = d->sdq; p.sdk = d->sdk; p.sdv = d->sdv; p.sdo = d->sdo;
-  p.bdq = d->bdq; p.bdk = d->bdk; p.bdv = d->bdv; p.bdo = d->bdo;
-  p.scale = d->scale;
-  p.causal = 1;
-  p.qsplit = 1;
-  set_smem(attn64_bwd_small_kernel<true>, ATTN64_SMALL_SMEM);
-  const dim3 lgrid = attn_grid(p, dim3(1, d->H, d->B));
-  hipLaunchKernelGGL(attn64_bwd_small_kernel<true>, lgrid, dim3(256), ATTN64_SMALL_SMEM, stream, p);
-  return nk_check_launch("attn64_bwd_small_kernel<causal>");
+                                       const float* lse, const void* d_o, void* dq, void* dk, void* dv, void* stream) {
+  void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, (void*)o, (void*)lse, (void*)d_o, dq, dk, dv, nullptr};
+  return attn_pass(d, ATTN_PASS_BWD_CAUSAL, ptr, stream);
 }

@@ -11,8 +11,11 @@ void nk_set_error(const char* file, int line, const char* what) {
 
 // ---- launch log (test hook): while it is on, every nk_check_launch records the name it was given, and the tile engine (nk_gemm_dispatch) adds
 // the plan of its launch behind the name: `name grid=x,y,z block smem splitk ksplit_len acc zero krot gm chunk` (gemm_plan.h: nk_plan_line).
-// In plan-only mode (3) the tile engine logs name and plan and returns before it touches the GPU: no zero-fill, no workspace, no launch --
-// which kernel a problem gets, and how, can be asked on a machine without one.  Host-only and thread-local: nothing is launched by the
+// The attention entry points (attention.hip) log under modes 1 and 2 the names alone; in plan-only mode, per planned launch, the name and
+// `name grid=x,y,z block smem gx qsplit part_offset ws_floats` (attn_plan.h: nk_attn_plan_line; part_offset -1: no partials; ws_floats 0: no
+// workspace): at most three launches, six entries a call, lines of under 100 characters.
+// In plan-only mode (3) the tile engine and the attention entry points log name and plan and return before they touch the GPU: no zero-fill,
+// no workspace, no launch, no pointer read -- which kernel a problem gets, and how, can be asked on a machine without one.  Host-only and thread-local: nothing is launched by the
 // hooks, so they work during graph capture; with the log off a launch pays the one flag test below.
 #define NK_LAUNCH_LOG_MAX 64
 #define NK_LAUNCH_LOG_TEXT 192

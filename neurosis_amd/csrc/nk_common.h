@@ -27,7 +27,7 @@ typedef __attribute__((ext_vector_type(2))) unsigned int uint2_t;
 
 void nk_set_error(const char* file, int line, const char* what);
 int nk_check_launch(const char* what);
-// launch log (test hook, errors.hip): 0 = off, 1 = logging, 3 = plan-only (the tile engine logs its plan and launches nothing)
+// launch log (test hook, errors.hip): 0 = off, 1 = logging, 3 = plan-only (the tile engine and the attention entry points log their plan and launch nothing)
 int nk_launch_log_mode(void);
 void nk_launch_log_add(const char* name, const char* text);      // `name` (a literal, or nullptr) and then a copy of `text`, one entry each
 // Opt a kernel in to `bytes` of dynamic LDS ON THE CURRENT DEVICE, once per (kernel, device): the attribute is per device, so a process-wide

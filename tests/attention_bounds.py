@@ -1,5 +1,5 @@
-"""Float64 references, error bounds, input generators, a restatement of the dispatch and a small emulation of the kernels' rounding points
-for the attention kernels of csrc/attention.hip, attn512.h and attn512_bwd.h.  Shared by test_attention_fp64_gpu.py (the kernels against
+"""Float64 references, error bounds, input generators, the path each case takes (asked of the library's planner) and a small emulation of the
+kernels' rounding points for the attention kernels of csrc/attention.hip, attn512.h and attn512_bwd.h.  Shared by test_attention_fp64_gpu.py (the kernels against
 float64) and test_attention_bounds_cpu.py (the bounds against the emulated arithmetic, with and without planted faults).
 
 Rounding points, read from the kernels (bf16 = round to nearest even, unit roundoff UB = 2^-8; fp32 unit roundoff U = 2^-24):
@@ -68,28 +68,8 @@ FAMILIES = {
 
 
 # ================================================================================================================================
-# the dispatch of nk_attention_fwd / nk_attention_bwd (attention.hip) and ops.attention512_fwd, restated
+# properties of the kernels' loops (the dispatch is asked of the library: case_path, at the end of this file)
 # ================================================================================================================================
-def attn_qsplit(B, H, Lq, Lk):
-    if Lk > 128 or Lq < 512:
-        return 1
-    s = 1
-    while s < 16 and B * H * s < 512 and Lq // (s * 2) >= 128:
-        s *= 2
-    return s
-
-
-def attn_small_qsplit(B, H, Lq):
-    s = 1
-    while s < 64 and B * H * s * 2 <= 512 and Lq // (s * 2) >= 64:
-        s *= 2
-    return s
-
-
-def attn_dp(D):
-    return 64 if D <= 64 else (96 if D <= 96 else 160)
-
-
 def empty_split(Lq, qsplit):
     """True if the last query split of the dK / dV kernels owns no 32-query tile"""
     nt_all = (Lq + 31) // 32
@@ -97,28 +77,11 @@ def empty_split(Lq, qsplit):
     return qsplit > 1 and (qsplit - 1) * per >= nt_all
 
 
-def dispatch(B, H, Lq, Lk, D, *, causal=False, attn64=True, small=True, backward=True, lse=True):
-    """(forward path, backward path, query splits of the dK / dV partials, nwhole of the forward, empty split)"""
-    if D == 512:
-        fwd = "attn512_fwd" if lse else "attn512_fwd_nolse"
-        if not backward:
-            return fwd, None, 1, None, False
-        return fwd, ("attn512_flash" if Lq <= 2048 else "attn512_recompute"), 1, None, False
-    if D == 64 and attn64:
-        fwd = "attn64_fwd_causal" if causal else "attn64_fwd"
-        nwhole = 0 if causal else Lk // 64
-    else:
-        fwd = f"generic_fwd_dp{attn_dp(D)}"
-        nwhole = Lk // 64 if (D == attn_dp(D) == 64 and not causal) else 0
-    if not backward:
-        return fwd, None, 1, nwhole, False
-    assert not causal
-    if D == 64 and attn64 and Lk <= 96 and small:
-        s = attn_small_qsplit(B, H, Lq)
-        return fwd, "attn64_small" + ("_qsplit" if s > 1 else ""), s, nwhole, empty_split(Lq, s)
-    s = attn_qsplit(B, H, Lq, Lk)
-    bwd = "attn64_dq_dkdv" if (D == 64 and attn64) else f"generic_bwd_dp{attn_dp(D)}"
-    return fwd, bwd + ("_qsplit" if s > 1 else ""), s, nwhole, empty_split(Lq, s)
+def nwhole(fwd, Lk, D, causal):
+    """key tiles the forward takes without a tail mask: the head-dim-64 instances only, none under the causal mask; None at head dim 512"""
+    if fwd.startswith("attn512"):
+        return None
+    return Lk // 64 if (D == 64 and not causal) else 0
 
 
 # ================================================================================================================================
@@ -480,7 +443,34 @@ EDGE_CASES = [(f"edge-d{D}-{Lq}x{Lk}", env, 3, 3, Lq, Lk, D, False, "cross", Tru
 EDGE_CASES += [(f"edge-d512-{L}", {}, 3, 1, L, L, 512, False, "dense", True) for L in (1, 31, 33, 129)]
 
 
+LABEL = {"attn64_fwd_kernel": "attn64_fwd", "attn_fwd_kernel": "generic_fwd_dp", "attn512_fwd_kernel": "attn512_fwd", "attn64_bwd_small_kernel": "attn64_small",
+         "attn64_bwd_dq_kernel": "attn64_dq_dkdv", "attn_bwd_dq_kernel": "generic_bwd_dp", "attn512_delta_kernel": "attn512_flash"}
+
+
+def _generic_dp(launch):
+    """the DP instance of a generic kernel, from the LDS bytes of its query-block ring [2 stages][K, V][64][2 DP + 16] (csrc/attn_plan.h)"""
+    dp = (launch["smem"] // 256 - 16) // 2
+    assert dp in (64, 96, 160) and launch["smem"] == 256 * (2 * dp + 16), launch
+    return dp
+
+
 def case_path(case):
+    """(forward path, backward path, query splits of the dK / dV partials, nwhole of the forward, empty split): kernels and splits are what
+    the library plans for the case under its environment (plan-only mode: tests/attn_plan_rows.py), mapped to the labels the tests use"""
+    from neurosis_amd import lib, ops
+    from tests import attn_plan_rows as R
+
     _, env, B, H, Lq, Lk, D, causal, _, bwd = case
-    return dispatch(B, H, Lq, Lk, D, causal=causal, attn64=env.get("NK_ATTN64", "1") != "0", small=env.get("NK_ATTN64_SMALL", "1") != "0",
-                    backward=bool(bwd), lse=bwd is not None or D != 512)
+    dims = [B, H, Lq, Lk, D, int(causal)]
+    label = lambda l: LABEL[l["name"]] + (str(_generic_dp(l)) if l["name"].startswith("attn_") else "")
+    fwd = label(R.planned(lib, dims, env, "fwd")["launches"][0])
+    fwd += "_causal" if causal and fwd == "attn64_fwd" else ("_nolse" if D == 512 and bwd is None else "")
+    nw = nwhole(fwd, Lk, D, causal)
+    if not bwd:
+        return fwd, None, 1, nw, False
+    if D == 512 and Lq > ops.ATTN512_FLASH_MAX_L:       # ops.attention512_fwd: beyond that, the chunked recompute through the tile engine
+        return fwd, "attn512_recompute", 1, nw, False
+    plan = R.planned(lib, dims, env, "bwd")
+    s = max(plan["qsplit"], 1)
+    assert (s > 1) == (plan["launches"][-1]["name"] == "attn_dkv_reduce_kernel"), plan
+    return fwd, label(plan["launches"][0]) + ("_qsplit" if s > 1 else ""), s, nw, empty_split(Lq, s)

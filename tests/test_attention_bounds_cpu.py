@@ -1,6 +1,6 @@
 """The attention error bounds of tests/attention_bounds.py against a torch emulation of each kernel family's rounding points (CPU):
-the emulated arithmetic stays inside the bounds, and each planted fault leaves them.  Also: the GPU test's case table, mapped through a
-restatement of nk_attention_fwd / nk_attention_bwd's dispatch, reaches every kernel path."""
+the emulated arithmetic stays inside the bounds, and each planted fault leaves them.  Also: the GPU test's case table, mapped through the
+plan nk_attention_fwd / nk_attention_bwd make for each case (plan-only mode: no GPU), reaches every kernel path."""
 import pytest
 import torch
 
