@@ -374,9 +374,15 @@ int nk_timestep_embedding(const float* t, void* out, int B, int dim, float max_p
  * modules/diffusion/denoiser.py:41-53, modules/losses/functions.py:91-94).
  * prepare: z_t = x + sigma*eps (fp32 NCHW); net_in = bf16 channels-last z_t*c_in, channels padded to Cpad.
  * loss:    D = net_out*c_out + z_t*c_skip; loss[b] = w[b]*mean((D-target)^2);
- *          dnet (optional) = upstream * dloss[b]/dnet_out, bf16 channels-last padded. */
+ *          dnet (optional) = upstream * dloss[b]/dnet_out, bf16 channels-last padded.
+ * prepare_cat: prepare for a concat-conditioned UNet (OpenAIWrapper.forward, modules/diffusion/wrappers.py:33: inpainting / edit /
+ *          upscale models).  extra: fp32 NCHW [B][Ce][HW]; net_in[b][p][c] = bf16(z_t*c_in) for c < C, bf16(extra[b][c-C][p]) for
+ *          C <= c < C+Ce (NOT scaled by c_in: the denoiser scales the latents, the wrapper concatenates afterwards), 0 up to Cpad.
+ *          Cpad % 8 == 0, 0 <= Cpad - (C+Ce) < 8; extra may be NULL when Ce == 0.  z_t and the latent channels are bit-equal to prepare's. */
 int nk_edm_prepare(const float* x, const float* eps, const float* sigma, const float* c_in, float* zt, void* net_in,
                    int B, int C, int HW, int Cpad, void* stream);
+int nk_edm_prepare_cat(const float* x, const float* eps, const float* sigma, const float* c_in, const float* extra, float* zt,
+                       void* net_in, int B, int C, int Ce, int HW, int Cpad, void* stream);
 int nk_edm_loss(const void* net_out, const float* zt, const float* target, const float* c_out, const float* c_skip,
                 const float* w, float* loss, void* dnet, int B, int C, int HW, int Cpad, float upstream, void* stream);
 
@@ -385,12 +391,17 @@ int nk_edm_loss(const void* net_out, const float* zt, const float* target, const
  * (VanillaCFG.prepare_inputs, modules/guidance.py:26-37).
  * prepare:    net_in[r*B+b] = bf16(c_in[b] * x[b]) for r < rep        (Denoiser.forward input scaling, denoiser.py:41-49,
  *             + the guider's torch.cat([x] * 2))
+ * prepare_cat: the same for a concat-conditioned UNet: channels C..C+Ce-1 of replica 0 = bf16(extra_u[b]), of replica 1 =
+ *             bf16(extra_c[b]) (fp32 NCHW [B][Ce][HW], unscaled; rep == 1 reads extra_c only), 0 up to Cpad;
+ *             Cpad % 8 == 0, 0 <= Cpad - (C+Ce) < 8
  * denoise:    D = c_skip[b]*x + c_out[b]*(F_u + scale*(F_c - F_u))    (denoiser.py:49-53 + VanillaCFG.__call__ guidance.py:21-24;
  *             rep == 1: F = net_out, scale ignored)
  * euler_step: d = (x - D)/sigma_hat[b]; x_next = x + (sigma_next[b] - sigma_hat[b])*d   (EDMSampler.sampler_step with the
  *             Euler correction, sampling/sampling.py:166-181,313-316, to_d sampling/utils.py:49-51).  x_next may alias x;
  *             `denoised` is optional (NULL to skip). */
 int nk_sample_prepare(const float* x, const float* c_in, void* net_in, int B, int C, int HW, int Cpad, int rep, void* stream);
+int nk_sample_prepare_cat(const float* x, const float* c_in, const float* extra_u, const float* extra_c, void* net_in, int B, int C,
+                          int Ce, int HW, int Cpad, int rep, void* stream);
 int nk_sample_denoise(const void* net_out, const float* x, const float* c_skip, const float* c_out, float scale,
                       float* denoised, int B, int C, int HW, int Cpad, int rep, void* stream);
 int nk_sample_euler_step(const void* net_out, const float* x, const float* c_skip, const float* c_out, const float* sigma_hat,

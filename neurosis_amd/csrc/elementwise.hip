@@ -981,6 +981,13 @@ extern "C" int nk_softmax_rows_bwd(const void* p, void* dp, long M, int L, float
 
 // ---- EDM noising + preconditioning (loss.py:117-140, denoiser.py:41-49) -------------------------
 // z_t = x + sigma*eps (fp32, NCHW) ; net_in = bf16 channels-last (z_t * c_in), channels padded to Cpad
+// One latent element, shared by both prepare kernels so that the compiler contracts the two expressions the same way in each:
+// stores z_t, returns the (fp32) network input.
+__device__ __forceinline__ float edm_noise_scale(float x, float eps, float sg, float ci, float* __restrict__ zt) {
+  const float z = x + sg * eps;
+  *zt = z;
+  return z * ci;
+}
 __global__ void edm_prepare_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                    const float* __restrict__ sigma, const float* __restrict__ c_in,
                                    float* __restrict__ zt, bf16_t* __restrict__ net_in, int B, int C, int HW, int Cpad) {
@@ -993,11 +1000,39 @@ __global__ void edm_prepare_kernel(const float* __restrict__ x, const float* __r
       float v = 0.f;
       if (c < C) {
         long o = ((long)b * C + c) * HW + p;
-        float z = x[o] + sg * eps[o];
-        zt[o] = z;
-        v = z * ci;
+        v = edm_noise_scale(x[o], eps[o], sg, ci, zt + o);
       }
       net_in[i * Cpad + c] = f2bf(v);
+    }
+  }
+}
+// The same with channel-concat conditioning (OpenAIWrapper.forward, modules/diffusion/wrappers.py:33: the denoiser scales the latents,
+// the wrapper joins `extra` behind them UNSCALED): net_in[b][p][c] = bf16(z_t*c_in) for c < C, bf16(extra[b][c-C][p]) for
+// C <= c < C+Ce, 0 up to Cpad.  extra: fp32 NCHW [B][Ce][HW].  One thread per pixel, NCHW reads coalesced across pixels, the
+// token side one 16-byte vector per 8 channels (Cpad % 8 == 0).
+__global__ __launch_bounds__(EW_THREADS) void edm_prepare_cat_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                                     const float* __restrict__ sigma, const float* __restrict__ c_in,
+                                                                     const float* __restrict__ extra, float* __restrict__ zt,
+                                                                     bf16_t* __restrict__ net_in, int B, int C, int Ce, int HW, int Cpad) {
+  const long total = (long)B * HW;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / HW);
+    const int p = (int)(i - (long)b * HW);
+    const float sg = sigma[b], ci = c_in[b];
+    for (int c0 = 0; c0 < Cpad; c0 += 8) {
+      float f[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = c0 + e;
+        f[e] = 0.f;
+        if (c < C) {
+          const long o = ((long)b * C + c) * HW + p;
+          f[e] = edm_noise_scale(x[o], eps[o], sg, ci, zt + o);
+        } else if (c < C + Ce) {
+          f[e] = extra[((long)b * Ce + (c - C)) * HW + p];
+        }
+      }
+      *(uint4_t*)(net_in + i * Cpad + c0) = pack8(f);
     }
   }
 }
@@ -1007,6 +1042,14 @@ extern "C" int nk_edm_prepare(const float* x, const float* eps, const float* sig
   hipLaunchKernelGGL(edm_prepare_kernel, dim3(ew_blocks((long)B * HW)), dim3(EW_THREADS), 0, (hipStream_t)stream, x,
                      eps, sigma, c_in, zt, (bf16_t*)net_in, B, C, HW, Cpad);
   return nk_check_launch("edm_prepare");
+}
+extern "C" int nk_edm_prepare_cat(const float* x, const float* eps, const float* sigma, const float* c_in, const float* extra,
+                                  float* zt, void* net_in, int B, int C, int Ce, int HW, int Cpad, void* stream) {
+  NK_CHECK_ARG(x && eps && sigma && c_in && zt && net_in && B > 0 && C > 0 && HW > 0 && Ce >= 0 && (extra || Ce == 0));
+  NK_CHECK_ARG(Cpad >= C + Ce && (Cpad & 7) == 0 && Cpad - (C + Ce) < 8);
+  hipLaunchKernelGGL(edm_prepare_cat_kernel, dim3(ew_blocks((long)B * HW)), dim3(EW_THREADS), 0, (hipStream_t)stream, x,
+                     eps, sigma, c_in, extra, zt, (bf16_t*)net_in, B, C, Ce, HW, Cpad);
+  return nk_check_launch("edm_prepare_cat");
 }
 
 // ---- EDM loss forward + its gradient w.r.t. the network output (loss.py:142-157, functions.py:91-94)

@@ -6,7 +6,7 @@
 // UNet's first conv gathers from and its last conv writes).  rep = 2 is classifier-free guidance with the batch laid out
 // [unconditional | conditional] as VanillaCFG.prepare_inputs does (modules/guidance.py:26-37).
 //
-// All three kernels are latency-sized (an SDXL 1024^2 latent is 256 KB per sample): one thread per pixel, the token side
+// All kernels here are latency-sized (an SDXL 1024^2 latent is 256 KB per sample): one thread per pixel, the token side
 // moved as one 16-byte vector per pixel when Cpad == 8, the NCHW side coalesced across pixels.
 #include "nk_common.h"
 #include "../../include/neurosis_hip.h"
@@ -19,8 +19,13 @@ static inline int smp_blocks(long n) {
 
 // net_in[r*B + b][p][c] = bf16(c_in[b] * x[b][c][p]) for every replica r (padding channels = 0).
 // Denoiser.forward's `inputs * c_in` (modules/diffusion/denoiser.py:41-49) fused with the guider's torch.cat([x] * 2).
+// CAT: channel-concat conditioning (OpenAIWrapper.forward, modules/diffusion/wrappers.py:33) rides behind the latents, UNSCALED:
+// channels C..C+Ce-1 of replica 0 come from extra_u, of replica 1 from extra_c (rep == 1: extra_c), fp32 NCHW [B][Ce][HW].
+// nk_sample_prepare is the CAT = false instantiation.
+template <bool CAT>
 __global__ __launch_bounds__(SMP_THREADS) void sample_prepare_kernel(const float* __restrict__ x, const float* __restrict__ c_in,
-                                                                     bf16_t* __restrict__ net_in, int B, int C, int HW, int Cpad,
+                                                                     const float* __restrict__ extra_u, const float* __restrict__ extra_c,
+                                                                     bf16_t* __restrict__ net_in, int B, int C, int Ce, int HW, int Cpad,
                                                                      int rep) {
   const long total = (long)B * HW;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -34,8 +39,20 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_prepare_kernel(const float
         const int c = c0 + e;
         f[e] = c < C ? x[((long)b * C + c) * HW + p] * ci : 0.f;
       }
-      const uint4_t v = pack8(f);
-      for (int r = 0; r < rep; ++r) *(uint4_t*)(net_in + (((long)r * B + b) * HW + p) * Cpad + c0) = v;
+      if (!CAT) {
+        const uint4_t v = pack8(f);
+        for (int r = 0; r < rep; ++r) *(uint4_t*)(net_in + (((long)r * B + b) * HW + p) * Cpad + c0) = v;
+      } else {
+        for (int r = 0; r < rep; ++r) {
+          const float* __restrict__ extra = (rep == 2 && r == 0) ? extra_u : extra_c;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int c = c0 + e;
+            if (c >= C && c < C + Ce) f[e] = extra[((long)b * Ce + (c - C)) * HW + p];
+          }
+          *(uint4_t*)(net_in + (((long)r * B + b) * HW + p) * Cpad + c0) = pack8(f);
+        }
+      }
     }
   }
 }
@@ -118,9 +135,18 @@ static bool smp_shape_ok(int B, int C, int HW, int Cpad, int rep) {
 extern "C" int nk_sample_prepare(const float* x, const float* c_in, void* net_in, int B, int C, int HW, int Cpad, int rep,
                                  void* stream) {
   NK_CHECK_ARG(x && c_in && net_in && smp_shape_ok(B, C, HW, Cpad, rep));
-  hipLaunchKernelGGL(sample_prepare_kernel, dim3(smp_blocks((long)B * HW)), dim3(SMP_THREADS), 0, (hipStream_t)stream, x, c_in,
-                     (bf16_t*)net_in, B, C, HW, Cpad, rep);
+  hipLaunchKernelGGL(sample_prepare_kernel<false>, dim3(smp_blocks((long)B * HW)), dim3(SMP_THREADS), 0, (hipStream_t)stream, x, c_in,
+                     (const float*)nullptr, (const float*)nullptr, (bf16_t*)net_in, B, C, 0, HW, Cpad, rep);
   return nk_check_launch("sample_prepare");
+}
+
+extern "C" int nk_sample_prepare_cat(const float* x, const float* c_in, const float* extra_u, const float* extra_c, void* net_in, int B,
+                                     int C, int Ce, int HW, int Cpad, int rep, void* stream) {
+  NK_CHECK_ARG(x && c_in && net_in && Ce >= 0 && C > 0 && smp_shape_ok(B, C + Ce, HW, Cpad, rep));
+  NK_CHECK_ARG(Ce == 0 || (extra_c && (rep == 1 || extra_u)));
+  hipLaunchKernelGGL(sample_prepare_kernel<true>, dim3(smp_blocks((long)B * HW)), dim3(SMP_THREADS), 0, (hipStream_t)stream, x, c_in,
+                     extra_u, extra_c, (bf16_t*)net_in, B, C, Ce, HW, Cpad, rep);
+  return nk_check_launch("sample_prepare_cat");
 }
 
 extern "C" int nk_sample_denoise(const void* net_out, const float* x, const float* c_skip, const float* c_out, float scale,

@@ -1,7 +1,8 @@
 """StandardDiffusionLoss: mirror of neurosis.modules.diffusion.loss (loss.py:20-157).
 
 When the network is an OpenAIWrapper around this package's UNetModel, the l2 loss runs fused for both objectives:
-noising + input scaling (nk_edm_prepare), the UNet as one explicit forward/backward chain of HIP kernels,
+noising + input scaling (nk_edm_prepare; nk_edm_prepare_cat when the conditioning carries a "concat" entry), the UNet as one
+explicit forward/backward chain of HIP kernels,
 and output scaling + per-sample weighted MSE + its gradient (nk_edm_loss) -- one autograd node for the whole
 loss.  "edm": z_t = x + sigma eps, target x, D = c_skip z_t + c_out F.  "rf" (rectified flow): z_t = (1 - sigma) x + sigma eps,
 target eps, the raw network output F (the same two kernels: the prepare kernel is handed (1 - sigma) x, the loss kernel
@@ -70,7 +71,8 @@ class StandardDiffusionLoss(DiffusionLoss):
     @staticmethod
     def fused_edm(unet: UNetModel, denoiser: Denoiser, weighting, inputs: Tensor, sigmas: Tensor, noise: Tensor, cond: dict, objective: str = "edm"):
         """loss[B] (fp32) for the edm or rf objective with the l2 loss; differentiable w.r.t. the UNet parameters.
-        inputs / noise: fp32 NCHW latents; sigmas: [B] fp32 on the same device."""
+        inputs / noise: fp32 NCHW latents; sigmas: [B] fp32 on the same device.  cond["concat"] (fp32 NCHW, no gradient) becomes the
+        network's input channels behind the latents; for "rf" too it is left as it is (only the latents are scaled by 1 - sigma)."""
         B, Cc, H, W = inputs.shape
         dev = inputs.device
         c_skip, c_out, c_in, c_noise = denoiser.coefficients(sigmas)
@@ -86,7 +88,12 @@ class StandardDiffusionLoss(DiffusionLoss):
             target = eps
             c_out, c_skip = torch.ones_like(c_out), torch.zeros_like(c_skip)
         context, y = cond.get("crossattn", None), cond.get("vector", None)
-        cpad = (Cc + 7) // 8 * 8
+        # channel-concat conditioning (inpainting / edit / upscale models): joined behind the latents by the prepare kernel, unscaled
+        extra = OpenAIWrapper.concat_of(cond)
+        Ce = 0 if extra is None else extra.shape[1]
+        if extra is not None:
+            extra = extra.detach().float().contiguous()
+        cpad = (Cc + Ce + 7) // 8 * 8
         params = [p for p in unet.parameters() if p.requires_grad]
         # a trained conditioner (configs/sdxl/sdxl-te.example.yaml): the UNet's backward also returns the gradients of its conditioning
         need_dctx = context is not None and context.requires_grad and torch.is_grad_enabled()
@@ -95,7 +102,11 @@ class StandardDiffusionLoss(DiffusionLoss):
         def run(context=None, y=None):
             zt = torch.empty_like(x)
             net_in = torch.empty(B * H * W, cpad, dtype=BF16, device=dev)
-            call("nk_edm_prepare", x.data_ptr(), eps.data_ptr(), sig.data_ptr(), c_in.data_ptr(), zt.data_ptr(), net_in.data_ptr(), B, Cc, H * W, cpad, ops._stream())
+            if extra is None:
+                call("nk_edm_prepare", x.data_ptr(), eps.data_ptr(), sig.data_ptr(), c_in.data_ptr(), zt.data_ptr(), net_in.data_ptr(), B, Cc, H * W, cpad, ops._stream())
+            else:
+                call("nk_edm_prepare_cat", x.data_ptr(), eps.data_ptr(), sig.data_ptr(), c_in.data_ptr(), extra.data_ptr(), zt.data_ptr(), net_in.data_ptr(),
+                     B, Cc, Ce, H * W, cpad, ops._stream())
             out, unet_bwd = unet.fwd_graphed(Img(net_in, B, H, W), c_noise, None if context is None else as_tokens(context), None if y is None else as_tokens(y),
                                              need_dctx, need_dy)
             loss = torch.empty(B, dtype=torch.float32, device=dev)

@@ -6,7 +6,7 @@ network moved into the nk_sample_* kernels (csrc/sampling.hip):
 
     reference, per step (CFG):  cat([x]*2), cat([s]*2), cat(uc, c) | x*c_in | UNet | F*c_out + x*c_skip | chunk, u + s(c-u) |
                                 (x - D)/sigma | x + dt*d                               ~12 launches over the latents, 2B-sized
-    here:                       nk_sample_prepare | UNet (bf16 tokens in, bf16 tokens out) | nk_sample_euler_step
+    here:                       nk_sample_prepare[_cat] | UNet (bf16 tokens in, bf16 tokens out) | nk_sample_euler_step
 
 The latents stay fp32 NCHW at the API; the network side never leaves channels-last bf16 tokens, so the NCHW<->NHWC
 transposes of the generic path disappear as well.
@@ -104,9 +104,21 @@ class FusedDenoiser:
         unet = self.network.diffusion_model
         c_skip, c_out, c_in, c_noise = (t.contiguous() for t in self.denoiser.coefficients(sigma))
         c_skip, c_out, c_in = c_skip.float(), c_out.float(), c_in.float()
-        cpad = (C + 7) // 8 * 8
+        # channel-concat conditioning (inpainting / edit / upscale models) rides behind the latents, unscaled: the unconditional half
+        # carries uc["concat"], the conditional half cond["concat"]
+        extra_c = OpenAIWrapper.concat_of(cond)
+        Ce = 0 if extra_c is None else extra_c.shape[1]
+        cpad = (C + Ce + 7) // 8 * 8
         net_in = torch.empty(rep * B * H * W, cpad, dtype=BF16, device=x.device)
-        call("nk_sample_prepare", x.data_ptr(), c_in.data_ptr(), net_in.data_ptr(), B, C, H * W, cpad, rep, ops._stream())
+        if extra_c is None:
+            call("nk_sample_prepare", x.data_ptr(), c_in.data_ptr(), net_in.data_ptr(), B, C, H * W, cpad, rep, ops._stream())
+        else:
+            extra_c = extra_c.float().contiguous()
+            extra_u = uc["concat"].float().contiguous() if rep == 2 else None
+            if extra_u is not None and extra_u.shape != extra_c.shape:
+                raise ValueError(f"concat conditioning: unconditional {tuple(extra_u.shape)} vs conditional {tuple(extra_c.shape)}")
+            call("nk_sample_prepare_cat", x.data_ptr(), c_in.data_ptr(), ops._p(extra_u), extra_c.data_ptr(), net_in.data_ptr(), B, C, Ce, H * W, cpad, rep,
+                 ops._stream())
 
         def stacked(key):
             value = cond.get(key)

@@ -22,12 +22,32 @@ class IdentityWrapper(nn.Module):
 class OpenAIWrapper(IdentityWrapper):
     """cond keys: "concat" (extra input channels), "crossattn" (context tokens), "vector" (pooled / size embedding)."""
 
+    @staticmethod
+    def concat_of(cond: dict):
+        """the channel-concat conditioning of `cond`, or None when there is none (an empty tensor means none, as in forward)"""
+        extra = cond.get("concat")
+        return None if extra is None or (torch.is_tensor(extra) and extra.numel() == 0) else extra
+
     def fused_unet(self, inputs: Tensor, cond: dict, extra_inputs: dict):
-        """The bare UNetModel when this call can take the fused HIP training path (device latents, no channel-concat
-        conditioning, no extra network inputs: nk_edm_prepare feeds the UNet's first conv directly), else None."""
+        """The bare UNetModel when this call can take the fused HIP path (device latents, no extra network inputs: nk_edm_prepare /
+        nk_sample_prepare feed the UNet's first conv directly), else None.  Channel-concat conditioning (inpainting, edit, upscale
+        models) stays on the path when it is a 4-D tensor on the latents' device with their B, H, W that needs no gradient: the
+        _cat kernels write it behind the latents.  Its channels must fill the UNet's in_channels: anything else is a ValueError here
+        instead of a shape error inside the first conv.  A 5-D (video) entry or one that requires grad takes the generic route."""
         unet = self.diffusion_model
-        plain = not extra_inputs and cond.get("concat") is None
-        return unet if isinstance(unet, UNetModel) and inputs.is_cuda and plain else None
+        if not isinstance(unet, UNetModel) or not inputs.is_cuda or extra_inputs:
+            return None
+        extra = self.concat_of(cond)
+        if extra is None:
+            return unet
+        if not torch.is_tensor(extra) or extra.dim() != 4 or inputs.dim() != 4 or extra.requires_grad or extra.device != inputs.device:
+            return None
+        if extra.shape[0] != inputs.shape[0] or extra.shape[2:] != inputs.shape[2:]:
+            return None
+        if inputs.shape[1] + extra.shape[1] != unet.in_channels:
+            raise ValueError(f"OpenAIWrapper: {inputs.shape[1]} latent + {extra.shape[1]} concat channels = {inputs.shape[1] + extra.shape[1]}, "
+                             f"but the UNet has in_channels = {unet.in_channels}")
+        return unet
 
     def forward(self, x: Tensor, t: Tensor, c: dict, **kwargs) -> Tensor:
         # other keys in `c` are ignored, as in the reference

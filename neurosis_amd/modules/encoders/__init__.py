@@ -1,4 +1,5 @@
 from .embedding import AbstractEmbModel, GeneralConditioner, PrecomputedEmbedder
 from .metadata import ConcatTimestepEmbedderND
+from .misc import IdentityEncoder
 
-__all__ = ["AbstractEmbModel", "GeneralConditioner", "PrecomputedEmbedder", "ConcatTimestepEmbedderND"]
+__all__ = ["AbstractEmbModel", "GeneralConditioner", "PrecomputedEmbedder", "ConcatTimestepEmbedderND", "IdentityEncoder"]

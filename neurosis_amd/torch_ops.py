@@ -676,6 +676,39 @@ def _(x, eps, sigma, c_in, cpad):
     return torch.empty_like(x), x.new_empty(x.shape[0] * x.shape[2] * x.shape[3], cpad, dtype=BF16)
 
 
+@_op("edm_prepare_cat")
+def edm_prepare_cat(x: Tensor, eps: Tensor, sigma: Tensor, c_in: Tensor, extra: Tensor, cpad: int) -> Tuple[Tensor, Tensor]:
+    """edm_prepare for a concat-conditioned UNet (OpenAIWrapper.forward, wrappers.py:33): the network input carries bf16(extra) -- fp32
+    NCHW [B, Ce, H, W], NOT scaled by c_in -- in channels C..C+Ce-1 behind bf16(z_t * c_in); cpad = C + Ce rounded up to 8"""
+    B, Cc, H, W = x.shape
+    zt = torch.empty_like(x)
+    net_in = torch.empty(B * H * W, cpad, dtype=BF16, device=x.device)
+    ops.call("nk_edm_prepare_cat", x.data_ptr(), eps.data_ptr(), sigma.data_ptr(), c_in.data_ptr(), extra.data_ptr(), zt.data_ptr(), net_in.data_ptr(),
+             B, Cc, extra.shape[1], H * W, cpad, ops._stream())
+    return zt, net_in
+
+
+@edm_prepare_cat.register_fake
+def _(x, eps, sigma, c_in, extra, cpad):
+    return torch.empty_like(x), x.new_empty(x.shape[0] * x.shape[2] * x.shape[3], cpad, dtype=BF16)
+
+
+@_op("sample_prepare_cat")
+def sample_prepare_cat(x: Tensor, c_in: Tensor, extra_u: Optional[Tensor], extra_c: Tensor, cpad: int, rep: int) -> Tensor:
+    """The sampler's network input for a concat-conditioned UNet: bf16 tokens [rep * B * H * W, cpad], channels < C = c_in * x in every
+    replica, channels C..C+Ce-1 = extra_u in replica 0 and extra_c in replica 1 (rep == 1: extra_c; extra_u may be None), unscaled"""
+    B, Cc, H, W = x.shape
+    net_in = torch.empty(rep * B * H * W, cpad, dtype=BF16, device=x.device)
+    ops.call("nk_sample_prepare_cat", x.data_ptr(), c_in.data_ptr(), ops._p(extra_u), extra_c.data_ptr(), net_in.data_ptr(), B, Cc, extra_c.shape[1], H * W,
+             cpad, rep, ops._stream())
+    return net_in
+
+
+@sample_prepare_cat.register_fake
+def _(x, c_in, extra_u, extra_c, cpad, rep):
+    return x.new_empty(rep * x.shape[0] * x.shape[2] * x.shape[3], cpad, dtype=BF16)
+
+
 @_op("edm_loss_fwd")
 def edm_loss_fwd(net_out: Tensor, zt: Tensor, target: Tensor, c_out: Tensor, c_skip: Tensor, w: Tensor) -> Tensor:
     """loss[b] = w[b] * mean((net_out * c_out + z_t * c_skip - target)^2): net_out bf16 tokens [B*H*W, Cpad], z_t / target fp32 NCHW"""
@@ -859,7 +892,7 @@ dropout.register_autograd(lambda ctx, dy: (torch.ops.neurosis_hip.dropout(dy.con
                                                                      setattr(ctx, "site", inputs[3]), setattr(ctx, "has_residual", inputs[4] is not None)))
 
 
-OPS = ("groupnorm_mod_fwd", "groupnorm_mod_bwd", "groupnorm_mod", "upsample2x_nearest", "avgpool2x", "avgpool2x_bwd", "dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
+OPS = ("groupnorm_mod_fwd", "groupnorm_mod_bwd", "groupnorm_mod", "upsample2x_nearest", "avgpool2x", "avgpool2x_bwd", "dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_prepare_cat", "sample_prepare_cat", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
        "flat_allreduce_start", "flat_allreduce_wait", "conv2d_fwd_stats", "linear_dgrad_geglu", "linear_fwd_geglu", "linear_fwd", "linear_dgrad", "linear_wgrad", "colsum", "linear", "layernorm_fwd", "layernorm_bwd", "layernorm", "groupnorm_silu_fwd",
        "groupnorm_silu_bwd", "groupnorm_silu", "geglu_fwd", "geglu_bwd", "geglu", "attention_fwd", "attention_bwd", "attention", "conv2d_fwd",
        "conv2d_dgrad", "conv2d_wgrad", "conv2d", "timestep_embedding", "nchw_to_nlc", "nlc_to_nchw")
