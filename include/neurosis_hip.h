@@ -188,6 +188,11 @@ int nk_attention_bwd(const NkAttnDesc* d, const void* q, const void* k, const vo
  * nk_attention_bwd without the workspace; dq / dk / dv 16-byte aligned.  (nk_attention_bwd refuses causal descriptors.) */
 int nk_attention_bwd_causal(const NkAttnDesc* d, const void* q, const void* k, const void* v, const void* o,
                             const float* lse, const void* d_o, void* dq, void* dk, void* dv, void* stream);
+/* softmax(scale q k^T + rel[h][j - i + Lq - 1]) v, forward only and without lse: the bidirectional self-attention of the T5 encoders with
+ * its additive relative position bias (models/text_encoder/t5.py:38-53: input_ids only, so no padding mask; T5 passes scale = 1).  rel is
+ * fp32 [H][Lq + Lk - 1], one row per head, indexed by key minus query position; added in fp32 before the running max.  Lq == Lk <= 1024,
+ * D % 8 == 0, D <= 160, !causal; q / k / v / o as for nk_attention_fwd. */
+int nk_attention_relbias_fwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, void* o, const float* rel, void* stream);
 /* in-place row softmax on bf16 [M][L]: unfused single-head attention = nk_linear_fwd (q k^T) -> nk_softmax_rows -> nk_linear_dgrad (p v).
  * Serves head dims the flash kernels do not take, and the chunked recomputing backward of the VAE mid block (d = 512) beyond 2 048 tokens per
  * sample (ops.attention512_fwd; up to there nk_attention_bwd's flash kernels run); d = 512 forward and backward are nk_attention_fwd / _bwd. */
@@ -230,6 +235,9 @@ int nk_groupnorm_mod_bwd(const void* dy, const void* x, const float* gamma, cons
 int nk_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                      int M, int C, float eps, void* stream);
 long nk_layernorm_ws_floats(int M, int C);
+/* T5LayerNorm (RMS norm: no mean subtraction, no bias), forward only: y[m][c] = x[m][c] * rsqrt(mean_c(x[m]^2) + eps) * gamma[c] on bf16
+ * [M][C], fp32 gamma, C % 8 == 0, C <= 4096.  The fp32 reduction has a fixed order: a row's bits do not depend on M. */
+int nk_rmsnorm_fwd(const void* x, const float* gamma, void* y, int M, int C, float eps, void* stream);
 int nk_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                      const void* dx_add, void* dx, float* dgamma, float* dbeta, float* ws, int M, int C, int accumulate, void* stream);
 /* The one-pass form in its two halves (round 5: what the transformer blocks use): _rows writes dx and nk_layernorm_part_rows(M) partial rows
@@ -352,6 +360,10 @@ int nk_lpips_layer_bwd(const void* f0, const void* f1, const float* w, const flo
  * text tower, models/text_encoder/clip.py:333-343); mode 1: "quick_gelu" x * sigmoid(1.702 x) (HF CLIPTextModel of
  * openai/clip-vit-large-patch14, models/text_encoder/clip.py:49-56). */
 int nk_gelu_fwd(const void* x, void* y, long n, int mode, void* stream);
+/* ... forward only: mode 2, "gelu_new" 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))); mode 3, ReLU (the ungated FeedForwards of the T5
+ * encoders, models/text_encoder/t5.py:38-53 over transformers' T5DenseActDense).  y = gelu_new(u[:, :I]) * u[:, I:] for u [M][2 I] bf16, the
+ * stacked projection [wi_0; wi_1] of T5 v1.1 / ByT5 (T5DenseGatedActDense); fp32 arithmetic, I % 8 == 0, y [M][I] dense. */
+int nk_gated_gelu_tanh_fwd(const void* u, void* y, long M, int I, void* stream);
 /* dx = dy * gelu'(x), same modes as nk_gelu_fwd; bf16 in and out, fp32 arithmetic (trainable text towers) */
 int nk_gelu_bwd(const void* dy, const void* x, void* dx, long n, int mode, void* stream);
 /* Token + position embedding backward of the text towers (x[b * L + l] = table[ids[b][l]] + pos[l]): dx [B * L][C] bf16 (row stride ldx);

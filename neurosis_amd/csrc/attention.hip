@@ -37,6 +37,7 @@ struct AttnParams {
   int qsplit;           // dK/dV kernel: workgroups per key block along the query range (partials in dkv_part)
   float* dkv_part;      // [qsplit][2][B][Lk][H*D] fp32 partial dK / dV when qsplit > 1
   int gx;               // > 0: the launch is a 1-D grid of gx * H * B workgroups and attn_wg() maps it XCD-aware; 0: the 3-D grid (x, head, batch)
+  const float* rel;     // attn_fwd_kernel<.., RELBIAS>: [H][Lq + Lk - 1] fp32, added to the scaled score of (query i, key j) at [h][j - i + Lq - 1]
 };
 
 // Which (x block, head, batch item) this workgroup is.  Workgroups go to the eight XCDs round-robin in launch order.  With the plain 3-D grid
@@ -134,16 +135,25 @@ struct TileLoader {
 // Occupancy target 3 waves per SIMD (<= 168 VGPRs): left alone hipcc takes 192 registers (2 waves per SIMD) and these
 // VALU-heavy loops stall half their cycles with nobody to cover -- measured forward 314 -> 247 us at L = 4096 (696 TFLOP/s),
 // 66 -> 48 us at L = 1024; 4 waves per SIMD spills and is slower again (308 us).
-template <int DP, int NW = 4>   // NW waves x 32 rows per workgroup (2: twice the workgroups for short sequences)
+// RELBIAS (nk_attention_relbias_fwd: the T5 encoders' self-attention): softmax(scale q k^T + rel[h][j - i + Lq - 1]) v.  The bias depends
+// only on j - i, so the head's whole table (Lq + Lk - 1 floats, 4 KiB at L = 512) sits in LDS behind the K / V ring; the score becomes
+// scale * s + bias in fp32 where the MASKED branch edits the raw scores, in front of the running max, and the softmax below runs on it with
+// scale 1.  No log-sum-exp leaves (no backward follows).  The other instances compile as before: every use is `if constexpr`.
+template <int DP, int NW = 4, bool RELBIAS = false>   // NW waves x 32 rows per workgroup (2: twice the workgroups for short sequences)
 __global__ __launch_bounds__(NW * 64, 3) void attn_fwd_kernel(const AttnParams p) {
   constexpr int RS = DP * 2 + 16, KS = DP / 16, DT = DP / 32, TILE = 64 * RS;
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages][K,V][64][RS]
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages][K,V][64][RS] (RELBIAS: + [Lq + Lk - 1] floats)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h5 = lane >> 5, ql = lane & 31;
   int bx, hd, b;
   attn_wg(p, bx, hd, b);
   const int q0 = bx * (NW * 32) + wave * 32;
-  const float c = p.scale * LOG2E;
+  const float c = RELBIAS ? LOG2E : p.scale * LOG2E;
+  const float* relt = (const float*)(smem + 4 * TILE);
+  if constexpr (RELBIAS) {      // (visible to every wave after the barrier that publishes tile 0)
+    const int nrel = p.Lq + p.Lk - 1;
+    for (int i = tid; i < nrel; i += NW * 64) ((float*)(smem + 4 * TILE))[i] = p.rel[(long)hd * nrel + i];
+  }
 
   const bf16_t* Qb = p.Q + (long)b * p.bq + (long)hd * p.D;
   const bf16_t* Kb = p.K + (long)b * p.bk + (long)hd * p.D;
@@ -245,6 +255,18 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_fwd_kernel(const AttnParams p
     // keys beyond Lk exist only in the last tile (wave-uniform branch); the causal variant (text transformers, L = 77)
     // masks every tile it visits
     const int kbase = t * 64;
+    if constexpr (RELBIAS) {
+      // this lane's query i (clamped: rows past Lq are computed and never stored) and its keys j (clamped: keys past Lk are masked below):
+      // j - i + Lq - 1 stays inside [0, Lq + Lk - 2].  A register index r reads 32 consecutive words per half wave: no bank conflict.
+      const float* rq = relt + (p.Lq - 1 - min(q0 + ql, p.Lq - 1));
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = min(kbase + hf * 32 + acc_row(r, h5), p.Lk - 1);
+          s[hf][r] = fmaf(s[hf][r], p.scale, rq[key]);
+        }
+    }
     if constexpr (MASKED) {
       const int last = p.causal ? min(p.Lk - 1, q0 + ql) : p.Lk - 1;   // highest visible key of this lane's query
 #pragma unroll
@@ -351,7 +373,9 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_fwd_kernel(const AttnParams p
           *(uint2_t*)(Ob + d) = o;
         }
       }
-    if (h5 == 0) p.LSE[((long)b * p.H + hd) * p.Lq + q] = m * p.scale + logf(l);
+    if constexpr (!RELBIAS) {
+      if (h5 == 0) p.LSE[((long)b * p.H + hd) * p.Lq + q] = m * p.scale + logf(l);
+    }
   }
 }
 
@@ -1740,7 +1764,7 @@ static AttnParams attn_params(const NkAttnDesc* d, const NkAttnPlan& pl, void* c
   p.Q = (const bf16_t*)ptr[AP_Q]; p.K = (const bf16_t*)ptr[AP_K]; p.V = (const bf16_t*)ptr[AP_V];
   p.O = (bf16_t*)ptr[AP_O]; p.Oc = (const bf16_t*)ptr[AP_O];      // written by the forward, read by the backward
   p.dO = (const bf16_t*)ptr[AP_DO]; p.dQ = (bf16_t*)ptr[AP_DQ]; p.dK = (bf16_t*)ptr[AP_DK]; p.dV = (bf16_t*)ptr[AP_DV];
-  p.LSE = (float*)ptr[AP_LSE]; p.delta = (float*)ptr[AP_WS];
+  p.LSE = (float*)ptr[AP_LSE]; p.delta = (float*)ptr[AP_WS]; p.rel = (const float*)ptr[AP_REL];
   p.B = d->B; p.H = d->H; p.Lq = d->Lq; p.Lk = d->Lk; p.D = d->D;
   p.sq = d->sq; p.sk = d->sk; p.sv = d->sv; p.so = d->so;
   p.bq = d->bq; p.bk = d->bk; p.bv = d->bv; p.bo = d->bo;
@@ -1780,6 +1804,9 @@ static int attn_run(const NkAttnPlan& pl, AttnParams p, hipStream_t stream) {
       ATTN_KERNEL(AK_BWD_DKDV_DP64, attn_bwd_dkdv_kernel<64, ATTN_NW>)
       ATTN_KERNEL(AK_BWD_DKDV_DP96, attn_bwd_dkdv_kernel<96, ATTN_NW>)
       ATTN_KERNEL(AK_BWD_DKDV_DP160, attn_bwd_dkdv_kernel<160, ATTN_NW>)
+      ATTN_KERNEL(AK_FWD_RELBIAS_DP64, attn_fwd_kernel<64, ATTN_NW, true>)
+      ATTN_KERNEL(AK_FWD_RELBIAS_DP96, attn_fwd_kernel<96, ATTN_NW, true>)
+      ATTN_KERNEL(AK_FWD_RELBIAS_DP160, attn_fwd_kernel<160, ATTN_NW, true>)
       ATTN_KERNEL(AK_DKV_REDUCE, attn_dkv_reduce_kernel)
       ATTN_KERNEL(AK_DELTA512, attn512_delta_kernel)
       ATTN_KERNEL(AK_BWD512_DQ, attn512_bwd_kernel<0>)
@@ -1819,6 +1846,14 @@ extern "C" int nk_attention_fwd(const NkAttnDesc* d, const void* q, const void* 
                                 void* stream) {
   void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, o, lse};
   return attn_pass(d, ATTN_PASS_FWD, ptr, stream);
+}
+
+// softmax(scale q k^T + rel[h][j - i + Lq - 1]) v: the T5 encoders' bidirectional self-attention with its relative position bias (scale = 1
+// there).  Forward only, no log-sum-exp; Lq == Lk <= ATTN_RELBIAS_MAX_L, the generic forward's head dims.
+extern "C" int nk_attention_relbias_fwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, void* o, const float* rel,
+                                        void* stream) {
+  void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, o, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (void*)rel};
+  return attn_pass(d, ATTN_PASS_FWD_RELBIAS, ptr, stream);
 }
 
 extern "C" long nk_attention_bwd_ws_floats(const NkAttnDesc* d) { return attn_ws(d, d->D == 64).total; }

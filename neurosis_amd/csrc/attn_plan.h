@@ -2,7 +2,7 @@
 //
 // Host-only: no kernel, no HIP call, no getenv, nothing but the descriptor (neurosis_hip.h), the constants below and libc, so a plan can be
 // computed (and is tested: tests/test_attn_plan_cpu.py) on a machine without a GPU, and a plain C++ program can include this file.  The entry
-// points (attention.hip: nk_attention_fwd, nk_attention_bwd, nk_attention_bwd_causal) check the descriptor, ask for the plan, check what the
+// points (attention.hip: nk_attention_fwd, nk_attention_relbias_fwd, nk_attention_bwd, nk_attention_bwd_causal) check the descriptor, ask for the plan, check what the
 // plan says about the pointers, fill AttnParams once and walk the plan's launches; nk_attention_bwd_ws_floats answers from the same layout,
 // so the workspace a caller sizes and the offsets the kernels are given cannot disagree.  Every selection rule of the family lives here, in
 // the order nk_attn_plan applies them, with the measurements behind its thresholds; the switches arrive as an AttnEnv (attention.hip:
@@ -21,6 +21,8 @@
 #define ATTN64_RING_SMEM (3 * 2 * 64 * 128)                               // attn64_fwd_kernel, attn64_bwd_dq_kernel: [3 stages][K, V][64][128 B]
 #define ATTN64_DKDV_SMEM (3 * (2 * 32 * 128 + 256))                       // attn64_bwd_dkdv_kernel: three stages of a Q' and a dO tile + 256 B of -delta / -lse2
 constexpr int attn_ring_smem(int dp) { return 2 * 2 * 64 * (dp * 2 + 16); }         // attn_fwd_kernel, attn_bwd_dq_kernel: [2 stages][K, V][64][RS]
+#define ATTN_RELBIAS_MAX_L 1024                                           // nk_attention_relbias_fwd: tokens of the self-attention (an 8 KiB table at the limit)
+constexpr int attn_relbias_smem(int dp, int L) { return attn_ring_smem(dp) + (((2 * L - 1) * 4 + 15) & ~15); }      // attn_fwd_kernel<.., RELBIAS>: the ring + one head's table
 constexpr int attn_dkdv_smem(int dp) { return 2 * (2 * 32 * (dp * 2 + 16) + 256); } // attn_bwd_dkdv_kernel
 #define SMALL_DSROW 72                               // bytes per row of the dS^T image [96 keys][32 queries] (64 + 8: conflict-free 8-byte writes)
 #define ATTN64_SMALL_SMEM (96 * 128 + 3 * (3 * 32 * 128 + 256 + 1024) + 2 * 96 * SMALL_DSROW)      // attn64_bwd_small_kernel: [K image][3 stages][2 dS^T buffers]
@@ -45,16 +47,17 @@ struct AttnEnv {
   int attn64;    // NK_ATTN64: 0 = the generic kernels for head dim 64 as well (A/B switch of round 4)
   int small;     // NK_ATTN64_SMALL: 0 = cross-attention backward through the two-kernel path (A/B switch of round 4)
 };
-enum AttnPass { ATTN_PASS_FWD = 0, ATTN_PASS_BWD = 1, ATTN_PASS_BWD_CAUSAL = 2 };
+enum AttnPass { ATTN_PASS_FWD = 0, ATTN_PASS_BWD = 1, ATTN_PASS_BWD_CAUSAL = 2, ATTN_PASS_FWD_RELBIAS = 3 };
 // the kernels and template instances the dispatch can select
 enum AttnKernel {
   AK_FWD64, AK_FWD_DP64, AK_FWD_DP96, AK_FWD_DP160, AK_FWD512,
   AK_BWD64_SMALL, AK_BWD64_SMALL_CAUSAL, AK_BWD64_DQ, AK_BWD64_DKDV,
   AK_BWD_DQ_DP64, AK_BWD_DQ_DP96, AK_BWD_DQ_DP160, AK_BWD_DKDV_DP64, AK_BWD_DKDV_DP96, AK_BWD_DKDV_DP160,
-  AK_DKV_REDUCE, AK_DELTA512, AK_BWD512_DQ, AK_BWD512_DKDV
+  AK_DKV_REDUCE, AK_DELTA512, AK_BWD512_DQ, AK_BWD512_DKDV,
+  AK_FWD_RELBIAS_DP64, AK_FWD_RELBIAS_DP96, AK_FWD_RELBIAS_DP160
 };
 // the caller's pointers, as bits of NkAttnPlan::need / ::align16 and as indices of the array attn_params() takes
-enum AttnPtr { AP_Q = 0, AP_K, AP_V, AP_O, AP_LSE, AP_DO, AP_DQ, AP_DK, AP_DV, AP_WS, AP_N };
+enum AttnPtr { AP_Q = 0, AP_K, AP_V, AP_O, AP_LSE, AP_DO, AP_DQ, AP_DK, AP_DV, AP_WS, AP_REL, AP_N };
 
 struct NkAttnLaunch {
   int kernel;             // AttnKernel
@@ -173,6 +176,18 @@ static NkAttnPlan nk_attn_plan(const NkAttnDesc* d, int pass, const AttnEnv& env
       attn_launch(pl, dp == 64 ? AK_FWD_DP64 : dp == 96 ? AK_FWD_DP96 : AK_FWD_DP160, "attn_fwd_kernel", attn_blocks(d->Lq), H, B, ATTN_NW * 64,
                   attn_ring_smem(dp), xcd);
     }
+    return pl;
+  }
+
+  if (pass == ATTN_PASS_FWD_RELBIAS) {
+    // The T5 encoders' self-attention: the generic forward in its RELBIAS instantiation, whatever the head dim (the head-dim-64 kernel of
+    // round 4 has no bias variant), with one head's table [Lq + Lk - 1] behind the K / V ring in LDS.  The output leaves in 8-byte stores.
+    pl.need = ATTN_BITS_QKVO | attn_bits(AP_REL);
+    if (d->causal) { pl.err = "!d->causal"; return pl; }
+    if (d->D > 160) { pl.err = "d->D <= 160"; return pl; }
+    if (!(d->Lq == d->Lk && d->Lk <= ATTN_RELBIAS_MAX_L)) { pl.err = "d->Lq == d->Lk && d->Lk <= ATTN_RELBIAS_MAX_L (relative-bias attention: self-attention over at most 1024 tokens)"; return pl; }
+    attn_launch(pl, dp == 64 ? AK_FWD_RELBIAS_DP64 : dp == 96 ? AK_FWD_RELBIAS_DP96 : AK_FWD_RELBIAS_DP160, "attn_fwd_kernel<relbias>", attn_blocks(d->Lq), H, B,
+                ATTN_NW * 64, attn_relbias_smem(dp, d->Lk), xcd);
     return pl;
   }
 

@@ -148,7 +148,13 @@ extern "C" int nk_silu_bwd(const void* dy, const void* x, void* dx, long n, void
 }
 
 // ---- GELU of the CLIP text transformers ---------------------------------------------------------
-// mode 0: exact erf form (open_clip's nn.GELU); mode 1: quick_gelu x * sigmoid(1.702 x) (openai/clip-vit-large-patch14)
+// mode 0: exact erf form (open_clip's nn.GELU); mode 1: quick_gelu x * sigmoid(1.702 x) (openai/clip-vit-large-patch14);
+// mode 2: "gelu_new", the tanh form 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) of T5 v1.1 / ByT5; mode 3: ReLU (T5 v1.0)
+// 0.5 (1 + tanh z) = 1 / (1 + exp(-2 z)): one exponential, and no cancellation where tanh z is near -1
+__device__ __forceinline__ float gelu_tanh(float x) {
+  const float z2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);      // 2 sqrt(2 / pi) (x + 0.044715 x^3)
+  return x / (1.0f + __expf(-z2));
+}
 template <int MODE>
 __global__ void gelu_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long n8) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
@@ -156,17 +162,46 @@ __global__ void gelu_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict
     unpack8(*(const uint4_t*)(x + i * 8), f);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      f[e] = MODE == 0 ? 0.5f * f[e] * (1.0f + erff(f[e] * 0.70710678118654752f)) : f[e] / (1.0f + __expf(-1.702f * f[e]));
+      f[e] = MODE == 0 ? 0.5f * f[e] * (1.0f + erff(f[e] * 0.70710678118654752f)) : MODE == 1 ? f[e] / (1.0f + __expf(-1.702f * f[e]))
+           : MODE == 2 ? gelu_tanh(f[e]) : fmaxf(f[e], 0.f);
     *(uint4_t*)(y + i * 8) = pack8(f);
   }
 }
 extern "C" int nk_gelu_fwd(const void* x, void* y, long n, int mode, void* stream) {
-  NK_CHECK_ARG(x && y && n > 0 && (n & 7) == 0 && (mode == 0 || mode == 1));
+  NK_CHECK_ARG(x && y && n > 0 && (n & 7) == 0 && mode >= 0 && mode <= 3);
   if (mode == 0)
     hipLaunchKernelGGL(gelu_fwd_kernel<0>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
-  else
+  else if (mode == 1)
     hipLaunchKernelGGL(gelu_fwd_kernel<1>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
+  else if (mode == 2)
+    hipLaunchKernelGGL(gelu_fwd_kernel<2>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
+  else
+    hipLaunchKernelGGL(gelu_fwd_kernel<3>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
   return nk_check_launch("gelu_fwd");
+}
+
+// ---- gated activation of the T5 v1.1 / ByT5 FeedForward: y = gelu_new(u[:, :I]) * u[:, I:] ----------------------------------------------
+// u [M][2 I] = one stacked projection [wi_0; wi_1] of the normed tokens, so the FeedForward is two GEMMs and this pass.  (The GEGLU of the
+// UNet, geglu_fwd_kernel above, gates the other way round and with the erf form.)
+__global__ void gated_gelu_tanh_kernel(const bf16_t* __restrict__ u, bf16_t* __restrict__ y, long M, int I) {
+  const int cpr = I >> 3;
+  const long total = M * cpr;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / cpr;
+    const int ch = (int)(i - row * cpr);
+    float a[8], g[8];
+    unpack8(*(const uint4_t*)(u + row * 2 * I + ch * 8), a);
+    unpack8(*(const uint4_t*)(u + row * 2 * I + I + ch * 8), g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = gelu_tanh(a[e]) * g[e];
+    *(uint4_t*)(y + row * I + ch * 8) = pack8(a);
+  }
+}
+extern "C" int nk_gated_gelu_tanh_fwd(const void* u, void* y, long M, int I, void* stream) {
+  NK_CHECK_ARG(u && y && M > 0 && I > 0 && (I & 7) == 0);
+  NK_CHECK_ARG(((uintptr_t)u & 15) == 0 && ((uintptr_t)y & 15) == 0);     // 16-byte accesses
+  hipLaunchKernelGGL(gated_gelu_tanh_kernel, dim3(ew_blocks(M * (I >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)u, (bf16_t*)y, M, I);
+  return nk_check_launch("gated_gelu_tanh_kernel");
 }
 
 // GELU backward (trainable text towers): dx = dy * gelu'(x), fp32 arithmetic on bf16 data, the same modes as the forward

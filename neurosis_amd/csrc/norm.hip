@@ -987,6 +987,65 @@ extern "C" int nk_layernorm_fwd(const void* x, const float* gamma, const float* 
   return nk_check_launch("ln_fwd_kernel");
 }
 
+// ------------------------------------------------------------------------------------------------
+// RMSNorm (T5LayerNorm: no mean subtraction, no bias) over the last dim of [M][C], forward only: y = x * rsqrt(mean(x^2) + eps) * gamma.
+// One wavefront per row as in ln_fwd_kernel.  The sum of squares is a per-lane sum over the lane's chunks in chunk order, then the xor
+// butterfly: a fixed order that depends on C alone, so a row's bits do not depend on M or on which wave got the row.
+// ------------------------------------------------------------------------------------------------
+#define RMS_MAXCH 8   // 16-byte chunks per lane: C <= 64*8*8 = 4096 (T5-v1.1-XXL)
+template <int NCH>
+__global__ __launch_bounds__(256) void rms_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma, bf16_t* __restrict__ y, int M, int C,
+                                                      float eps) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  const int cpr = C >> 3;
+  const float invC = 1.0f / (float)C;
+  for (int row = wave; row < M; row += nwaves) {
+    uint4_t raw[NCH];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int ch = lane + 64 * j;
+      if (ch < cpr) {
+        float f[8];
+        raw[j] = *(const uint4_t*)(x + (long)row * C + ch * 8);
+        unpack8(raw[j], f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s = fmaf(f[e], f[e], s);
+      }
+    }
+    const float rs = rsqrtf(wave_sum(s) * invC + eps);
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int ch = lane + 64 * j;
+      if (ch < cpr) {
+        const float4_t g0 = *(const float4_t*)(gamma + ch * 8), g1 = *(const float4_t*)(gamma + ch * 8 + 4);
+        float f[8], o[8];
+        unpack8(raw[j], f);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          o[e] = f[e] * rs * g0[e];
+          o[4 + e] = f[4 + e] * rs * g1[e];
+        }
+        *(uint4_t*)(y + (long)row * C + ch * 8) = pack8(o);
+      }
+    }
+  }
+}
+
+extern "C" int nk_rmsnorm_fwd(const void* x, const float* gamma, void* y, int M, int C, float eps, void* stream) {
+  NK_CHECK_ARG(M > 0 && C > 0 && (C & 7) == 0 && (C >> 3) <= 64 * RMS_MAXCH);
+  NK_CHECK_ARG(x && gamma && y);
+  NK_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0);     // 16-byte accesses
+  int blocks = min((M + 3) / 4, 4096);
+  const int nch = ((C >> 3) + 63) / 64;
+#define NK_RMS_FWD(NCH_) hipLaunchKernelGGL(rms_fwd_kernel<NCH_>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, gamma, (bf16_t*)y, M, C, eps)
+  if (nch <= 2) NK_RMS_FWD(2); else if (nch <= 4) NK_RMS_FWD(4); else NK_RMS_FWD(8);
+#undef NK_RMS_FWD
+  return nk_check_launch("rms_fwd_kernel");
+}
+
 extern "C" long nk_layernorm_ws_floats(int M, int C) {
   const long a = (long)ln_param_split(M), b = LNR_MAX_BLOCKS;
   return (a > b ? a : b) * 2 * C + 64;

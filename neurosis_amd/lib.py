@@ -63,6 +63,7 @@ SIGNATURES: dict[str, list] = {
     "nk_attention_fwd": [adp, vp, vp, vp, vp, vp, vp],
     "nk_attention_bwd": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "nk_attention_bwd_causal": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "nk_attention_relbias_fwd": [adp, vp, vp, vp, vp, vp, vp],
     "nk_softmax_rows": [vp, i64, i32, vp],
     "nk_softmax_rows_bwd": [vp, vp, i64, i32, f32, vp],
     "nk_groupnorm_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
@@ -74,6 +75,7 @@ SIGNATURES: dict[str, list] = {
     "nk_groupnorm_mod_apply": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "nk_groupnorm_mod_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "nk_layernorm_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp],
+    "nk_rmsnorm_fwd": [vp, vp, vp, i32, i32, f32, vp],
     "nk_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "nk_layernorm_bwd_dx": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
     "nk_layernorm_bwd_rows": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
@@ -85,6 +87,7 @@ SIGNATURES: dict[str, list] = {
     "nk_geglu_bwd_s": [vp, vp, vp, i64, i32, vp],
     "nk_silu_fwd": [vp, vp, i64, vp],
     "nk_gelu_fwd": [vp, vp, i64, i32, vp],
+    "nk_gated_gelu_tanh_fwd": [vp, vp, i64, i32, vp],
     "nk_gelu_bwd": [vp, vp, vp, i64, i32, vp],
     "nk_embedding_bwd": [vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "nk_gather_rows_bwd": [vp, i64, vp, vp, i32, i32, i32, vp],

@@ -808,6 +808,42 @@ def layernorm_fwd(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5):
     return y, bwd
 
 
+def rmsnorm(x: Tensor, weight: Tensor, eps: float = 1e-6) -> Tensor:
+    """T5LayerNorm over the last dim of a dense bf16 token matrix: x * rsqrt(mean(x^2) + eps) * weight (fp32 weight); forward only."""
+    _check2d(x, "x")
+    if not x.is_contiguous():
+        raise ValueError("rmsnorm: x must be dense")
+    M, Cc = x.shape
+    if weight.dtype != torch.float32 or weight.numel() != Cc or not weight.is_contiguous():
+        raise ValueError(f"rmsnorm: weight must be a dense fp32 vector of {Cc} elements, got {weight.dtype} {tuple(weight.shape)}")
+    y = torch.empty_like(x)
+    call("nk_rmsnorm_fwd", x.data_ptr(), weight.data_ptr(), y.data_ptr(), M, Cc, float(eps), _stream())
+    return y
+
+
+GATED_ACT_KINDS = ("gated-gelu", "gelu_new", "relu")
+
+
+def gated_act(u: Tensor, kind: str) -> Tensor:
+    """The activation of a T5 FeedForward on the dense bf16 output u of its input projection, forward only.  "gated-gelu" (T5 v1.1, ByT5):
+    u [M, 2 I] = [wi_0 x | wi_1 x] -> gelu_new(u[:, :I]) * u[:, I:], [M, I]; "gelu_new" and "relu" (T5 v1.0) are ungated, [M, I] -> [M, I]."""
+    _check2d(u, "u")
+    if not u.is_contiguous():
+        raise ValueError("gated_act: u must be dense")
+    if kind == "gated-gelu":
+        M, I2 = u.shape
+        if I2 % 16:
+            raise ValueError(f"gated_act: u must be [M, 2 I] with I % 8 == 0, got {tuple(u.shape)}")
+        y = torch.empty(M, I2 // 2, dtype=BF16, device=u.device)
+        call("nk_gated_gelu_tanh_fwd", u.data_ptr(), y.data_ptr(), M, I2 // 2, _stream())
+        return y
+    if kind in ("gelu_new", "relu"):
+        y = torch.empty_like(u)
+        call("nk_gelu_fwd", u.data_ptr(), y.data_ptr(), u.numel(), 2 if kind == "gelu_new" else 3, _stream())
+        return y
+    raise ValueError(f"gated_act: kind must be one of {GATED_ACT_KINDS}, got {kind!r}")
+
+
 def geglu_fwd(u: Tensor):
     _check2d(u, "u")
     M, I2 = u.shape
@@ -1230,6 +1266,33 @@ def attention_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head:
     if return_lse:              # [B, heads, Lq] fp32, natural log of the row sums of exp(scale q k^T) (the chunked recompute backward rebuilds P from it)
         return o, bwd, lse
     return o, bwd
+
+
+ATTN_RELBIAS_MAX_L = 1024      # csrc/attn_plan.h
+
+
+def attention_relbias_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head: int, rel: Tensor, scale: float = 1.0) -> Tensor:
+    """softmax(scale q k^T + rel[h][j - i + L - 1]) v, forward only: the T5 encoders' bidirectional self-attention with its relative position
+    bias (T5 does not scale: scale = 1).  q / k / v [B*L, H*D] token matrices (column slices of a fused projection allowed); rel fp32
+    [heads, 2 L - 1], indexed by key minus query position.  Returns the dense bf16 [B*L, H*D] output."""
+    for n, t in (("q", q), ("k", k), ("v", v)):
+        _check2d(t, n)
+    L = q.shape[0] // B
+    if k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
+        raise ValueError("attention_relbias_fwd: self-attention (q, k and v over the same tokens)")
+    if L > ATTN_RELBIAS_MAX_L:
+        raise NotImplementedError(f"attention_relbias_fwd: at most {ATTN_RELBIAS_MAX_L} tokens per sequence (the head's bias table lives in LDS), got L = {L}")
+    if rel.dtype != torch.float32 or tuple(rel.shape) != (heads, 2 * L - 1) or not rel.is_contiguous() or rel.device != q.device:
+        raise ValueError(f"attention_relbias_fwd: rel must be a dense fp32 [{heads}, {2 * L - 1}] tensor on {q.device}, got {rel.dtype} {tuple(rel.shape)}")
+    o = torch.empty(B * L, heads * dim_head, dtype=BF16, device=q.device)
+    d = NkAttnDesc()
+    d.B, d.H, d.Lq, d.Lk, d.D = B, heads, L, L, dim_head
+    d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
+    d.bq, d.bk, d.bv, d.bo = L * q.stride(0), L * k.stride(0), L * v.stride(0), L * o.stride(0)
+    d.scale = float(scale)
+    d.causal = 0
+    call("nk_attention_relbias_fwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), rel.data_ptr(), _stream())
+    return o
 
 
 def attention_causal_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head: int = 64):
