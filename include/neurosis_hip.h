@@ -379,6 +379,27 @@ int nk_gather_rows_bwd(const void* dsel, long ldsel, const long long* idx, void*
  * (bigG's text_projection sees only the B end-of-text rows); fixed-order sums */
 int nk_wgrad_few_rows(const void* x, long ldx, const void* dy, long lddy, float* dw, long lddw, int M, int K, int N, int accumulate, void* stream);
 
+/* Vector-quantizer bottleneck (modules/autoencoding/regularizers/quantize.py: VectorQuantizer.forward :222-272, EMAVectorQuantizer.forward
+ * :362-409), csrc/vq.hip.  All fp32, no float atomics: every result is bit-reproducible.  1 <= D <= NK_VQ_MAX_D, 1 <= n_e <=
+ * NK_VQ_MAX_CODES, N < 2^31, refused with a message otherwise.  z [N][D] with row stride ldz (elements), codebook [n_e][D] dense.
+ * search:     idx[i] = argmin_j d_j, d_j = fma(-2, z_i . e_j, n_j): n_j = sum_k e_jk^2 and the dot product are fp32 fma chains in k order from
+ *             0 (the dot product on v_mfma_f32_16x16x4_f32, whose result is that chain); |z_i|^2 is left out (constant along a row).  Among
+ *             bitwise-equal scores the lowest j wins; a NaN score is never chosen unless the whole row is NaN (then 0).  The [N][n_e] matrix is
+ *             never written.  ws: nk_vq_search_ws_floats(N, n_e) floats (the norms; with few rows the code tiles are also cut across workgroups
+ *             and each cut's (min, index) per row is merged from there in cut order -- the same index whatever the cut).
+ * code_stats: count[j] = #{i : idx[i] = j} (int64), sum[j][:] = the rows z_i of code j added in rising i (a chain of count[j] additions);
+ *             codes nobody chose give exact zeros.  Feeds the codebook gradient, the EMA update, perplexity and cluster usage.
+ * quantize:   zq = codebook[idx] as fp32 [N / HW][D][HW] (row i = b * HW + p; HW = 1: the [N][D] matrix) and sumsq[0] = sum (zq - z)^2 by a
+ *             fixed-order reduction (longest chain D + ceil(ceil(N / 256) / 256) + 16).  ws: nk_vq_quantize_ws_floats(N) floats. */
+#define NK_VQ_MAX_D 256
+#define NK_VQ_MAX_CODES 65536
+long nk_vq_search_ws_floats(long N, int n_e);
+int nk_vq_search(const float* z, long ldz, const float* codebook, float* ws, long long* idx, long N, int D, int n_e, void* stream);
+int nk_vq_code_stats(const long long* idx, const float* z, long ldz, long long* count, float* sum, long N, int D, int n_e, void* stream);
+long nk_vq_quantize_ws_floats(long N);
+int nk_vq_quantize(const long long* idx, const float* codebook, const float* z, long ldz, float* zq, float* sumsq, float* ws, long N, int D,
+                   int n_e, int HW, void* stream);
+
 /* timestep_embedding (modules/diffusion/util.py:152-177): out[B][dim] bf16 = [cos | sin](t * freq) */
 int nk_timestep_embedding(const float* t, void* out, int B, int dim, float max_period, void* stream);
 

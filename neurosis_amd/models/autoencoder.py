@@ -77,6 +77,8 @@ class DiagonalGaussianRegularizer(nn.Module):
     `regularize` also returns the backward of the map moments -> (z, kl_loss): the tensors are latent-sized
     ([B, 2*z, H/8, W/8] fp32), plain torch arithmetic on the device."""
 
+    loss_key = "kl_loss"      # the entry of the log that `regularization_weights` weighs (the quantizers' is "loss/vq")
+
     def __init__(self, sample: bool = True) -> None:
         super().__init__()
         self.sample = sample
@@ -187,7 +189,11 @@ class AutoencodingEngine(nn.Module):
 
     def get_autoencoder_params(self, decoder_only: bool = False) -> list:
         params = ([self.logvar] if self.learn_logvar else []) + list(self.decoder.parameters())
-        return params if decoder_only else params + list(self.encoder.parameters())
+        if decoder_only:
+            return params
+        # the regularizer's own parameters (a VectorQuantizer's codebook) go last: nothing for the Gaussian one, whose layout is unchanged
+        reg = getattr(self.regularization, "get_trainable_parameters", None)
+        return params + list(self.encoder.parameters()) + (list(reg()) if reg is not None else [])
 
     def get_last_layer(self):
         return self.decoder.get_last_layer()
@@ -257,7 +263,7 @@ class AutoencodingEngine(nn.Module):
             loss = loss + w * reg_log[key]
         reg_log = {**reg_log, **log}
         dz = ops.tokens_to_nchw(b_dec(d_out), B, zc, z.shape[2], z.shape[3], dtype=torch.float32)
-        d_moments = b_reg(dz, float(self.regularization_weights.get("kl_loss", 0.0)))
+        d_moments = b_reg(dz, float(self.regularization_weights.get(getattr(self.regularization, "loss_key", "kl_loss"), 0.0)))
         b_enc(ops.nchw_to_tokens(d_moments.contiguous(), moments_img.C))
         ops.join_wgrad_stream()
         return loss, z, xrec, reg_log

@@ -1441,6 +1441,74 @@ def _attention_recompute_bwd(q: Tensor, k: Tensor, v: Tensor, B: int, lse: Optio
 
 
 # ------------------------------------------------------------------------------------------------
+# vector quantizer (csrc/vq.hip)
+# ------------------------------------------------------------------------------------------------
+VQ_MAX_D, VQ_MAX_CODES = 256, 65536
+
+
+def _vq_rows(t: Tensor, name: str, op: str) -> Tensor:
+    """fp32 [N, D] device matrix with unit inner stride (a column slice of a wider matrix is taken as it is)"""
+    if not t.is_cuda:
+        raise NotImplementedError(f"{op}: {name} is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f"{op}: {name} must be a 2-D fp32 tensor, got {tuple(t.shape)} {t.dtype}")
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def _vq_idx(idx: Tensor, N: int, op: str) -> Tensor:
+    if not idx.is_cuda:
+        raise NotImplementedError(f"{op}: idx is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    if idx.dtype != torch.int64 or idx.numel() != N:
+        raise ValueError(f"{op}: idx must hold {N} int64 indices, got {tuple(idx.shape)} {idx.dtype}")
+    return idx.reshape(-1).contiguous()
+
+
+def vq_search(z: Tensor, codebook: Tensor) -> Tensor:
+    """idx [N] int64 = argmin_j (|e_j|^2 - 2 z_i . e_j) over the codebook [n_e, D] for every row of z [N, D] (nk_vq_search: exact fp32 on the
+    matrix pipe, lowest index among equal scores, NaN scores never chosen; the [N, n_e] distance matrix is never written)."""
+    z, codebook = _vq_rows(z, "z", "vq_search"), _vq_rows(codebook, "codebook", "vq_search").contiguous()
+    N, D = z.shape
+    n_e = codebook.shape[0]
+    if codebook.shape[1] != D:
+        raise ValueError(f"vq_search: z [N, {D}] against a codebook of width {codebook.shape[1]}")
+    idx = torch.empty(N, dtype=torch.int64, device=z.device)
+    ws = _ws(max(query("nk_vq_search_ws_floats", N, n_e), 1), z.device)
+    call("nk_vq_search", z.data_ptr(), z.stride(0), codebook.data_ptr(), ws.data_ptr(), idx.data_ptr(), N, D, n_e, _stream())
+    return idx
+
+
+def vq_code_stats(idx: Tensor, z: Tensor, n_e: int):
+    """(count [n_e] int64, sum [n_e, D] fp32): how many rows of z chose each code and the sum of those rows, added in row order
+    (nk_vq_code_stats: deterministic, no atomics; codes nobody chose are exact zeros)."""
+    z = _vq_rows(z, "z", "vq_code_stats")
+    N, D = z.shape
+    idx = _vq_idx(idx, N, "vq_code_stats")
+    count = torch.zeros(n_e, dtype=torch.int64, device=z.device)
+    total = torch.zeros(n_e, D, dtype=torch.float32, device=z.device)
+    call("nk_vq_code_stats", idx.data_ptr(), z.data_ptr(), z.stride(0), count.data_ptr(), total.data_ptr(), N, D, int(n_e), _stream())
+    return count, total
+
+
+def vq_quantize(idx: Tensor, codebook: Tensor, z: Tensor, hw: int = 1, out: Optional[Tensor] = None):
+    """(z_q, sumsq): z_q = codebook[idx] written as fp32 [N // hw, D, hw] (row i of z = b * hw + p: NCHW with hw = H * W; hw = 1 gives
+    the [N, D] matrix), sumsq = sum (z_q - z)^2 as a device scalar from a fixed-order reduction (nk_vq_quantize)."""
+    z, codebook = _vq_rows(z, "z", "vq_quantize"), _vq_rows(codebook, "codebook", "vq_quantize").contiguous()
+    N, D = z.shape
+    idx = _vq_idx(idx, N, "vq_quantize")
+    if codebook.shape[1] != D or hw < 1 or N % hw:
+        raise ValueError(f"vq_quantize: z {tuple(z.shape)}, codebook {tuple(codebook.shape)}, hw = {hw}")
+    if out is None:
+        out = torch.empty((N, D) if hw == 1 else (N // hw, D, hw), dtype=torch.float32, device=z.device)
+    elif out.numel() != N * D or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("vq_quantize: out must be a dense fp32 device tensor of N * D elements")
+    sumsq = torch.empty((), dtype=torch.float32, device=z.device)
+    ws = _ws(query("nk_vq_quantize_ws_floats", N), z.device)
+    call("nk_vq_quantize", idx.data_ptr(), codebook.data_ptr(), z.data_ptr(), z.stride(0), out.data_ptr(), sumsq.data_ptr(), ws.data_ptr(), N, D,
+         codebook.shape[0], int(hw), _stream())
+    return out, sumsq
+
+
+# ------------------------------------------------------------------------------------------------
 # misc
 # ------------------------------------------------------------------------------------------------
 def timestep_embedding(t: Tensor, dim: int, max_period: float = 10000.0) -> Tensor:

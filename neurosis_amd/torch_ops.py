@@ -892,7 +892,68 @@ dropout.register_autograd(lambda ctx, dy: (torch.ops.neurosis_hip.dropout(dy.con
                                                                      setattr(ctx, "site", inputs[3]), setattr(ctx, "has_residual", inputs[4] is not None)))
 
 
-OPS = ("groupnorm_mod_fwd", "groupnorm_mod_bwd", "groupnorm_mod", "upsample2x_nearest", "avgpool2x", "avgpool2x_bwd", "dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_prepare_cat", "sample_prepare_cat", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
+# ---------------------------------------------------------------------------------------------------------------
+# vector quantizer (csrc/vq.hip): code search, per-code statistics, straight-through gather with the VQ loss
+# ---------------------------------------------------------------------------------------------------------------
+@_op("vq_search")
+def vq_search(z: Tensor, codebook: Tensor) -> Tensor:
+    """idx [N] int64: the nearest code of every row of z [N, D] fp32 in codebook [n_e, D] fp32 (exact fp32, lowest index among equal scores).
+    Not differentiable: the indices are integers."""
+    return ops.vq_search(z, codebook)
+
+
+@vq_search.register_fake
+def _(z, codebook):
+    return z.new_empty(z.shape[0], dtype=torch.int64)
+
+
+@_op("vq_code_stats")
+def vq_code_stats(idx: Tensor, z: Tensor, n_e: int) -> Tuple[Tensor, Tensor]:
+    """(count [n_e] int64, sum [n_e, D] fp32) of the rows of z by the code they chose; deterministic"""
+    return ops.vq_code_stats(idx, z, n_e)
+
+
+@vq_code_stats.register_fake
+def _(idx, z, n_e):
+    return z.new_empty(n_e, dtype=torch.int64), z.new_empty(n_e, z.shape[1], dtype=torch.float32)
+
+
+@_op("vq_quantize")
+def vq_quantize(z: Tensor, codebook: Tensor, idx: Tensor, beta: float = 0.25) -> Tuple[Tensor, Tensor]:
+    """(z_q, loss) of VectorQuantizer for z [N, D] fp32 and the indices of vq_search: z_q = codebook[idx], straight-through (its gradient
+    goes to z unchanged), loss = beta * mean((sg[z_q] - z)^2) + mean((z_q - sg[z])^2)."""
+    z_q, sumsq = ops.vq_quantize(idx, codebook, z)
+    mse = sumsq / z.numel()
+    return z_q, beta * mse + mse
+
+
+@vq_quantize.register_fake
+def _(z, codebook, idx, beta=0.25):
+    return torch.empty_like(z, memory_format=torch.contiguous_format), z.new_empty(())
+
+
+def _vq_quantize_setup(ctx, inputs, output):
+    z, codebook, idx, beta = inputs
+    ctx.save_for_backward(z, codebook, idx, output[0])
+    ctx.beta = beta
+
+
+def _vq_quantize_bwd(ctx, d_zq, d_loss):
+    z, codebook, idx, z_q = ctx.saved_tensors
+    k = d_loss * (2.0 / z.numel())
+    dz = dE = None
+    if ctx.needs_input_grad[0]:
+        dz = d_zq + (k * ctx.beta) * (z - z_q)
+    if ctx.needs_input_grad[1]:
+        count, total = torch.ops.neurosis_hip.vq_code_stats(idx, z, codebook.shape[0])
+        dE = k * (count.to(torch.float32).unsqueeze(1) * codebook - total)
+    return dz, dE, None, None
+
+
+vq_quantize.register_autograd(_vq_quantize_bwd, setup_context=_vq_quantize_setup)
+
+
+OPS = ("vq_search", "vq_code_stats", "vq_quantize", "groupnorm_mod_fwd", "groupnorm_mod_bwd", "groupnorm_mod", "upsample2x_nearest", "avgpool2x", "avgpool2x_bwd", "dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_prepare_cat", "sample_prepare_cat", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
        "flat_allreduce_start", "flat_allreduce_wait", "conv2d_fwd_stats", "linear_dgrad_geglu", "linear_fwd_geglu", "linear_fwd", "linear_dgrad", "linear_wgrad", "colsum", "linear", "layernorm_fwd", "layernorm_bwd", "layernorm", "groupnorm_silu_fwd",
        "groupnorm_silu_bwd", "groupnorm_silu", "geglu_fwd", "geglu_bwd", "geglu", "attention_fwd", "attention_bwd", "attention", "conv2d_fwd",
        "conv2d_dgrad", "conv2d_wgrad", "conv2d", "timestep_embedding", "nchw_to_nlc", "nlc_to_nchw")
