@@ -204,14 +204,18 @@ int nk_softmax_rows(void* s, long M, int L, void* stream);
  * mean/rstd: [N][G] fp32 (saved for backward).  ws: uninitialised fp32 workspace of nk_groupnorm_ws_floats elements
  * (statistics are reduced through per-block partials, not atomics: deterministic, no memset).
  * Backward adds into dgamma/dbeta (fp32) and optionally adds dx_add into dx.
+ * Sizes, the workspace layout (part [N][nsplit][nz][2G] | gsum [N][2G] | chan [N][nsplit][2][C]) and the launches of every entry point of
+ * this family, of LayerNorm / RMSNorm and of the column sums come from one host-only planner, csrc/norm_plan.h: the *_ws_floats queries
+ * answer from the plan the entry points run (0 for a shape they refuse), and in plan-only mode (nk_debug_launch_log(3)) the entry points
+ * log `name grid=x,y,z block smem [region=offset+extent ...] ws=ws_floats` per launch and return before touching a pointer or the device.
  * ---------------------------------------------------------------------------------------------- */
-long nk_groupnorm_ws_floats(int N, int HW, int C, int G); /* fp32 elements of `ws` (per-block partial sums) */
+long nk_groupnorm_ws_floats(int N, int HW, int C, int G); /* fp32 elements of `ws`: the same for the forward, the sums and the backward */
 int nk_groupnorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                      float* ws, int N, int HW, int C, int G, float eps, int silu, void* stream);
 /* The forward in separable passes (what nk_groupnorm_fwd runs back to back): sums [N][2G] (entry 2g = sum, 2g+1 = sum of squares over
  * HW * C/G elements) from x, or from a convolution's per-tile partials; and the normalisation given the sums. */
 int nk_groupnorm_sums(const void* x, float* sums, float* ws, int N, int HW, int C, int G, void* stream);
-long nk_groupnorm_sums_ws_floats(int N, int nparts, int G);
+long nk_groupnorm_sums_ws_floats(int N, int nparts, int G); /* level 1's [N][64][2G] partial rows (used beyond 128 rows per image); the same for every nparts */
 int nk_groupnorm_sums_from_parts(const float* part, float* sums, float* ws, int N, int nparts, int G, void* stream);
 int nk_groupnorm_apply(const void* x, const float* sums, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                        int N, int HW, int C, int G, float eps, int silu, void* stream);
@@ -234,7 +238,7 @@ int nk_groupnorm_mod_bwd(const void* dy, const void* x, const float* gamma, cons
 /* nn.LayerNorm(C) over rows of [M][C] (attention.py:468-470).  mean/rstd: [M] fp32. */
 int nk_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                      int M, int C, float eps, void* stream);
-long nk_layernorm_ws_floats(int M, int C);
+long nk_layernorm_ws_floats(int M, int C); /* `ws` of nk_layernorm_bwd and _bwd_params: partial rows [rows][2][C], room for the larger of their two splits; for every C % 8 == 0 (_bwd_params takes widths beyond 2048) */
 /* T5LayerNorm (RMS norm: no mean subtraction, no bias), forward only: y[m][c] = x[m][c] * rsqrt(mean_c(x[m]^2) + eps) * gamma[c] on bf16
  * [M][C], fp32 gamma, C % 8 == 0, C <= 4096.  The fp32 reduction has a fixed order: a row's bits do not depend on M. */
 int nk_rmsnorm_fwd(const void* x, const float* gamma, void* y, int M, int C, float eps, void* stream);

@@ -2,6 +2,8 @@
 // All bf16 traffic is 16 B per lane; fp32 traffic 16 B per lane where the layout allows.
 #include "../../include/neurosis_hip.h"
 #include "nk_common.h"
+#include "nk_reduce.h"
+#include "norm_plan.h"
 
 #define EW_THREADS 256
 static inline int ew_blocks(long work_items) {
@@ -759,14 +761,6 @@ extern "C" int nk_cast_bf16_to_f32(const void* src, float* dst, long n, void* st
 // A block is 16 row lanes x 16 chunk lanes (a chunk = 8 channels = 16 B): every row lane reads 256 contiguous bytes, a
 // thread keeps four rows' loads in flight, and with 64 rows per split even M = 4096 gives hundreds of blocks (the
 // earlier one-row-at-a-time layout ran at 1-2 TB/s: 12 ms of GPU time per step for bias gradients alone).
-#define CS_ROWS 64
-// rows per workgroup: 64 up to 65 536 rows (the UNet's token counts), then as many as keeps the second stage at <= 1 024 partial rows
-// (the autoencoder's 2 M-row feature maps gave it 32 768 rows to walk: 80 us per bias gradient)
-static int colsum_rows(long M) {
-  long rows = CS_ROWS;
-  while ((M + rows - 1) / rows > 1024) rows *= 2;
-  return (int)rows;
-}
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const bf16_t* __restrict__ dy, float* __restrict__ part, long M, int N,
                                                              long ld, int rows_per_block) {
   __shared__ float ps[16][16 * 8 + 4];  // [row lane][chunk lane * 8 + e], combined in a fixed order (bitwise reproducible)
@@ -813,43 +807,34 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const bf16_t* __res
 }
 __global__ __launch_bounds__(1024) void colsum_reduce_kernel(const float* __restrict__ part, float* __restrict__ out,
                                                              int nsplit, int N, int accumulate) {
-  __shared__ float sa[16][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + tx;
-  part += (long)blockIdx.y * nsplit * N;               // batched form: blockIdx.y = row block
+  // 64 columns x 16 row groups in the order of nk_reduce_rows; batched form: blockIdx.y = row block
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  part += (long)blockIdx.y * nsplit * N;
   out += (long)blockIdx.y * N;
-  float a = 0.f;
-  if (c < N)
-#pragma unroll 4
-    for (int r = ty; r < nsplit; r += 16) a += part[(long)r * N + c];
-  sa[ty][tx] = a;
-  __syncthreads();
-  if (ty == 0 && c < N) {
-#pragma unroll
-    for (int j = 1; j < 16; ++j) a += sa[j][tx];
-    out[c] = accumulate ? out[c] + a : a;
-  }
+  nk_reduce_rows<16, 64, 1, 0, 4>(
+      c < N, nsplit, [&](int r, float* a) { a[0] += part[(long)r * N + c]; }, [&](const float* a) { out[c] = accumulate ? out[c] + a[0] : a[0]; });
 }
-static int colsum_split(long M) { const int rows = colsum_rows(M); return (int)((M + rows - 1) / rows); }
-extern "C" long nk_colsum_ws_floats(long M, int N) { return (long)colsum_split(M) * N + 64; }
+// sizes, split and launches: norm_plan.h (nk_colsum_plan)
+extern "C" long nk_colsum_ws_floats(long M, int N) { return nk_colsum_plan(M, N, 1).ws_floats; }
 extern "C" int nk_colsum_batched(const void* dy, float* out, float* ws, long M, int N, long ld, int nbatch, int accumulate, void* stream_) {
   // out[b][N] (+)= column sums of rows [b*M, (b+1)*M) of dy, b < nbatch, in ONE pair of launches (ws: nbatch x nk_colsum_ws_floats(M, N))
   hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(dy && out && ws && M > 0 && N > 0 && (N & 7) == 0 && (ld & 7) == 0 && nbatch >= 1 && nbatch <= 65535);
-  const int nsplit = colsum_split(M);
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(nsplit, (N + 127) / 128, nbatch), dim3(256), 0, stream, (const bf16_t*)dy, ws, M, N, ld, colsum_rows(M));
-  if (int e = nk_check_launch("colsum_partial")) return e;
-  hipLaunchKernelGGL(colsum_reduce_kernel, dim3((N + 63) / 64, nbatch), dim3(1024), 0, stream, ws, out, nsplit, N, accumulate);
-  return nk_check_launch("colsum_reduce");
+  const NkColsumPlan p = nk_colsum_plan(M, N, nbatch);
+  NORM_PLAN_OR_RETURN(p);
+  NK_CHECK_ARG(dy && out && ws && (ld & 7) == 0);
+  // while the launch log is on, each launch's plan line follows its name, as behind a tile-engine launch: what plan-only mode logs is
+  // what a logged launch logs (tests/test_gemm_exact_gpu.py compares the two)
+  char line[192];
+  for (int i = 0; i < 2; ++i) {
+    if (i == 0) NORM_LAUNCH(p.launch[0], colsum_partial_kernel, (const bf16_t*)dy, ws + p.part.off, M, N, ld, p.rows_per_block);
+    else NORM_LAUNCH(p.launch[1], colsum_reduce_kernel, ws + p.part.off, out, p.nsplit, N, accumulate);
+    if (int e = nk_check_launch(p.launch[i].name)) return e;
+    if (nk_launch_log_mode()) { nk_norm_plan_line(p, i, line, sizeof(line)); nk_launch_log_add(nullptr, line); }
+  }
+  return NK_OK;
 }
-extern "C" int nk_colsum(const void* dy, float* out, float* ws, long M, int N, long ld, int accumulate, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(dy && out && ws && M > 0 && N > 0 && (N & 7) == 0 && (ld & 7) == 0);
-  const int nsplit = colsum_split(M);
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(nsplit, (N + 127) / 128), dim3(256), 0, stream, (const bf16_t*)dy, ws, M, N, ld, colsum_rows(M));
-  if (int e = nk_check_launch("colsum_partial")) return e;
-  hipLaunchKernelGGL(colsum_reduce_kernel, dim3((N + 63) / 64), dim3(1024), 0, stream, ws, out, nsplit, N, accumulate);
-  return nk_check_launch("colsum_reduce");
+extern "C" int nk_colsum(const void* dy, float* out, float* ws, long M, int N, long ld, int accumulate, void* stream) {
+  return nk_colsum_batched(dy, out, ws, M, N, ld, 1, accumulate, stream);
 }
 
 // ---- sinusoidal timestep embedding (modules/diffusion/util.py:152-177): [cos | sin] -------------

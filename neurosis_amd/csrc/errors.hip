@@ -13,8 +13,11 @@ void nk_set_error(const char* file, int line, const char* what) {
 // the plan of its launch behind the name: `name grid=x,y,z block smem splitk ksplit_len acc zero krot gm chunk` (gemm_plan.h: nk_plan_line).
 // The attention entry points (attention.hip) log under modes 1 and 2 the names alone; in plan-only mode, per planned launch, the name and
 // `name grid=x,y,z block smem gx qsplit part_offset ws_floats` (attn_plan.h: nk_attn_plan_line; part_offset -1: no partials; ws_floats 0: no
-// workspace): at most three launches, six entries a call, lines of under 100 characters.
-// In plan-only mode (3) the tile engine and the attention entry points log name and plan and return before they touch the GPU: no zero-fill,
+// workspace): at most three launches, six entries a call, lines of under 100 characters.  The norm and column-sum entry points (norm.hip,
+// elementwise.hip) do the same with `name grid=x,y,z block smem [region=offset+extent ...] ws=ws_floats` (norm_plan.h: nk_norm_plan_line): at
+// most five launches a call.  The column sums also log their line behind the name in mode 1, like the tile engine (tests/test_gemm_exact_gpu.py
+// compares a planned call with a launched one).
+// In plan-only mode (3) the tile engine, the attention and the norm / column-sum entry points log name and plan and return before they touch the GPU: no zero-fill,
 // no workspace, no launch, no pointer read -- which kernel a problem gets, and how, can be asked on a machine without one.  Host-only and thread-local: nothing is launched by the
 // hooks, so they work during graph capture; with the log off a launch pays the one flag test below.
 #define NK_LAUNCH_LOG_MAX 64

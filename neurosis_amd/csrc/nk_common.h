@@ -27,7 +27,7 @@ typedef __attribute__((ext_vector_type(2))) unsigned int uint2_t;
 
 void nk_set_error(const char* file, int line, const char* what);
 int nk_check_launch(const char* what);
-// launch log (test hook, errors.hip): 0 = off, 1 = logging, 3 = plan-only (the tile engine and the attention entry points log their plan and launch nothing)
+// launch log (test hook, errors.hip): 0 = off, 1 = logging, 3 = plan-only (the tile engine, the attention and the norm / column-sum entry points log their plan and launch nothing)
 int nk_launch_log_mode(void);
 void nk_launch_log_add(const char* name, const char* text);      // `name` (a literal, or nullptr) and then a copy of `text`, one entry each
 // Opt a kernel in to `bytes` of dynamic LDS ON THE CURRENT DEVICE, once per (kernel, device): the attribute is per device, so a process-wide
@@ -127,3 +127,14 @@ __device__ __forceinline__ float dgelu_erf(float x) {
   normal_cdf_pdf(x, cdf, pdf);
   return cdf + x * pdf;
 }
+
+// ---- for the entry points that run a plan of norm_plan.h (norm.hip, elementwise.hip) ----------------------------------------------------------
+// a refused shape is an argument error; in plan-only mode (nk_debug_launch_log(3)) the plan is the answer: name and plan line per launch,
+// and nothing looks at a pointer or touches the device
+#define NORM_PLAN_OR_RETURN(p)                                                                        \
+  do {                                                                                                \
+    if ((p).err) { nk_set_error(__FILE__, __LINE__, (p).err); return NK_ERR_ARG; }                    \
+    if (nk_launch_log_mode() == 3) { nk_norm_plan_log(p, nk_launch_log_add); return NK_OK; }          \
+  } while (0)
+// launch `kernel` with the geometry of planned launch L on `stream`
+#define NORM_LAUNCH(L, kernel, ...) hipLaunchKernelGGL(kernel, dim3((L).grid[0], (L).grid[1], (L).grid[2]), dim3((L).block), (L).smem, stream, __VA_ARGS__)

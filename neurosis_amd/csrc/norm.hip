@@ -7,9 +7,9 @@
 // nn.LayerNorm (modules/attention.py:468-470).
 #include "../../include/neurosis_hip.h"
 #include "nk_common.h"
-
-#define GN_THREADS 256
-#define GN_MAXC 4096
+#include "nk_reduce.h"
+#include "norm_plan.h"
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
 // GroupNorm forward, pass 1: per-(n, group) sum and sum of squares
@@ -74,22 +74,13 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const bf16_t* __re
 }
 
 // sums the per-block partials of one image in a fixed order: out[n][2G] = sum_p part[n][p][2G]
-// block = G2 (<= 128) columns x (1024 / 128) row groups; each row group sums a strided subset, then a serial combine
+// block = G2 (<= 128) columns x (1024 / 128) row groups, in the order of nk_reduce_rows
 __global__ __launch_bounds__(1024) void gn_reduce_partials_kernel(const float* __restrict__ part, float* __restrict__ out,
                                                                  int nparts, int G2) {
-  __shared__ float sm[8][128];
-  const int n = blockIdx.x;
-  const int tx = threadIdx.x & 127, ty = threadIdx.x >> 7;   // 128 x 8
-  float a = 0.f;
-  if (tx < G2)
-    for (int p = ty; p < nparts; p += 8) a += part[((long)n * nparts + p) * G2 + tx];
-  sm[ty][tx] = a;
-  __syncthreads();
-  if (ty == 0 && tx < G2) {
-#pragma unroll
-    for (int j = 1; j < 8; ++j) a += sm[j][tx];
-    out[(long)n * G2 + tx] = a;
-  }
+  const int n = blockIdx.x, tx = threadIdx.x & 127;
+  nk_reduce_rows<8, 128, 1, 0, 0>(
+      tx < G2, nparts, [&](int p, float* a) { a[0] += part[((long)n * nparts + p) * G2 + tx]; },
+      [&](const float* a) { out[(long)n * G2 + tx] = a[0]; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -266,29 +257,20 @@ __global__ __launch_bounds__(GN_THREADS, 4) void gn_bwd_stats_kernel(const bf16_
 }
 
 // dgamma[c] += sum_rows part[row][0][c] ; dbeta[c] += sum_rows part[row][1][c]
-// block = 64 channels x 16 row groups (1024 threads); single writer per channel, so no atomics
+// block = 64 channels x 16 row groups (1024 threads); single writer per channel, so no atomics (nk_reduce_rows has the order)
 __global__ __launch_bounds__(1024) void colpart_reduce_kernel(const float* __restrict__ part, float* __restrict__ dgamma,
                                                               float* __restrict__ dbeta, int nrows, int C, int accumulate) {
-  __shared__ float sa[16][64], sb[16][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + tx;
-  float a = 0.f, b = 0.f;
-  if (c < C) {
-#pragma unroll 4
-    for (int r = ty; r < nrows; r += 16) {
-      a += part[(long)r * 2 * C + c];
-      b += part[(long)r * 2 * C + C + c];
-    }
-  }
-  sa[ty][tx] = a;
-  sb[ty][tx] = b;
-  __syncthreads();
-  if (ty == 0 && c < C) {
-#pragma unroll
-    for (int j = 1; j < 16; ++j) { a += sa[j][tx]; b += sb[j][tx]; }
-    dgamma[c] = accumulate ? dgamma[c] + a : a;
-    dbeta[c] = accumulate ? dbeta[c] + b : b;
-  }
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  nk_reduce_rows<16, 64, 2, 0, 4>(
+      c < C, nrows,
+      [&](int r, float* a) {
+        a[0] += part[(long)r * 2 * C + c];
+        a[1] += part[(long)r * 2 * C + C + c];
+      },
+      [&](const float* a) {
+        dgamma[c] = accumulate ? dgamma[c] + a[0] : a[0];
+        dbeta[c] = accumulate ? dbeta[c] + a[1] : a[1];
+      });
 }
 
 // The modulated GroupNorm's parameter gradients from the same per-(image, split) channel partials (row r belongs to image r / nsplit):
@@ -296,52 +278,35 @@ __global__ __launch_bounds__(1024) void colpart_reduce_kernel(const float* __res
 __global__ __launch_bounds__(1024) void colpart_reduce_mod_kernel(const float* __restrict__ part, const bf16_t* __restrict__ mod,
                                                                   float* __restrict__ dgamma, float* __restrict__ dbeta, int nrows, int nsplit,
                                                                   int C, int accumulate) {
-  __shared__ float sa[16][64], sb[16][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + tx;
-  float a = 0.f, b = 0.f;
-  if (c < C) {
-#pragma unroll 4
-    for (int r = ty; r < nrows; r += 16) {
-      const float s1 = 1.0f + bf2f(mod[(long)(r / nsplit) * 2 * C + c]);
-      a += s1 * part[(long)r * 2 * C + c];
-      b += s1 * part[(long)r * 2 * C + C + c];
-    }
-  }
-  sa[ty][tx] = a;
-  sb[ty][tx] = b;
-  __syncthreads();
-  if (ty == 0 && c < C) {
-#pragma unroll
-    for (int j = 1; j < 16; ++j) { a += sa[j][tx]; b += sb[j][tx]; }
-    dgamma[c] = accumulate ? dgamma[c] + a : a;
-    dbeta[c] = accumulate ? dbeta[c] + b : b;
-  }
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  nk_reduce_rows<16, 64, 2, 0, 4>(
+      c < C, nrows,
+      [&](int r, float* a) {
+        const float s1 = 1.0f + bf2f(mod[(long)(r / nsplit) * 2 * C + c]);
+        a[0] += s1 * part[(long)r * 2 * C + c];
+        a[1] += s1 * part[(long)r * 2 * C + C + c];
+      },
+      [&](const float* a) {
+        dgamma[c] = accumulate ? dgamma[c] + a[0] : a[0];
+        dbeta[c] = accumulate ? dbeta[c] + a[1] : a[1];
+      });
 }
 
 // ... and the gradient of the modulation itself, dmod[n] = [d_scale | d_shift]: with a_nc = sum_hw dz, b_nc = sum_hw dz*xhat (the image's
 // nsplit partial rows, summed in a fixed order)  d_shift = a_nc,  d_scale = gamma_c b_nc + beta_c a_nc.  grid (C / 64, N).
 __global__ __launch_bounds__(1024) void gn_dmod_kernel(const float* __restrict__ part, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, bf16_t* __restrict__ dmod, int nsplit, int C) {
-  __shared__ float sa[16][64], sb[16][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + tx, n = blockIdx.y;
-  float a = 0.f, b = 0.f;
-  if (c < C) {
-    for (int r = ty; r < nsplit; r += 16) {
-      b += part[((long)n * nsplit + r) * 2 * C + c];
-      a += part[((long)n * nsplit + r) * 2 * C + C + c];
-    }
-  }
-  sa[ty][tx] = a;
-  sb[ty][tx] = b;
-  __syncthreads();
-  if (ty == 0 && c < C) {
-#pragma unroll
-    for (int j = 1; j < 16; ++j) { a += sa[j][tx]; b += sb[j][tx]; }
-    dmod[(long)n * 2 * C + c] = f2bf(gamma[c] * b + beta[c] * a);
-    dmod[(long)n * 2 * C + C + c] = f2bf(a);
-  }
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63), n = blockIdx.y;
+  nk_reduce_rows<16, 64, 2, 0, 0>(
+      c < C, nsplit,
+      [&](int r, float* ab) {      // ab[0] = a (the dbeta half of the row), ab[1] = b
+        ab[1] += part[((long)n * nsplit + r) * 2 * C + c];
+        ab[0] += part[((long)n * nsplit + r) * 2 * C + C + c];
+      },
+      [&](const float* ab) {
+        dmod[(long)n * 2 * C + c] = f2bf(gamma[c] * ab[1] + beta[c] * ab[0]);
+        dmod[(long)n * 2 * C + C + c] = f2bf(ab[0]);
+      });
 }
 
 // GroupNorm backward, pass 2: dx = rstd * (dz*gamma - (s1 + xhat*s2)/cnt) (+ dx_add)
@@ -422,58 +387,96 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_apply_kernel(const bf16_t* 
   }
 }
 
-// channel slabs so that one thread owns one 16-byte chunk column: (C/8)/nz <= 256
-static int gn_nz(int C) {
-  int cpr = C >> 3, nz = (cpr + GN_THREADS - 1) / GN_THREADS;
-  while (cpr % nz) ++nz;
-  return nz;
-}
-
-static int gn_rows_per(int N, int HW, int* nsplit) {
-  // aim for ~2048 blocks in total
-  int want = (1024 + N - 1) / N;
-  int rows_per = (HW + want - 1) / want;
-  if (rows_per < 32) rows_per = 32;
-  *nsplit = (HW + rows_per - 1) / rows_per;
-  return rows_per;
-}
-
-extern "C" long nk_groupnorm_ws_floats(int N, int HW, int C, int G) {
-  // fp32 elements of workspace nk_groupnorm_fwd / nk_groupnorm_bwd need (per-block partial sums)
-  int nsplit;
-  gn_rows_per(N, HW, &nsplit);
-  long parts = (long)N * nsplit * gn_nz(C) * 2 * G;   // group partials
-  long chan = (long)N * nsplit * 2 * C;                // channel partials (backward)
-  return parts + chan + (long)N * 2 * G + 64;
-}
-
-extern "C" int nk_groupnorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
-                                float* rstd, float* ws, int N, int HW, int C, int G, float eps, int silu,
-                                void* stream_) {
+// ---- GroupNorm, host side: one forward and one backward runner -- plan (norm_plan.h: nk_gn_plan has the sizes, the workspace layout and the
+// launches), check the pointers, run the plan's launches in order.  The plain and the modulated entry points differ in what they pass. ----
+static int gn_forward(int pass, bool modulated, const void* x, float* sums, const float* gamma, const float* beta, const void* mod, void* y, float* mean,
+                      float* rstd, float* ws, int N, int HW, int C, int G, float eps, int silu, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
-  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
-  NK_CHECK_ARG(x && gamma && beta && y && mean && rstd && ws);
-  int nsplit;
-  int rows_per = gn_rows_per(N, HW, &nsplit);
-  const int nz = gn_nz(C);
-  float* part = ws;
-  float* stats = ws + (long)N * nsplit * nz * 2 * G;
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(nsplit, N, nz), dim3(GN_THREADS), 0, stream, (const bf16_t*)x, part, HW, C,
-                     G, rows_per);
-  if (int e = nk_check_launch("gn_stats_kernel")) return e;
-  hipLaunchKernelGGL(gn_reduce_partials_kernel, dim3(N), dim3(1024), 0, stream, part, stats, nsplit * nz, 2 * G);
-  if (int e = nk_check_launch("gn_reduce_partials_kernel")) return e;
-  hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(nsplit, N), dim3(GN_THREADS), 2 * C * sizeof(float), stream,
-                     (const bf16_t*)x, stats, gamma, beta, (const bf16_t*)nullptr, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, rows_per);
-  return nk_check_launch("gn_apply_kernel");
+  const NkGnPlan p = nk_gn_plan(N, HW, C, G, pass, modulated);
+  NORM_PLAN_OR_RETURN(p);
+  NK_CHECK_ARG(x && (pass == GN_APPLY || ws) && (pass == GN_FWD || sums) && (pass == GN_SUMS || (gamma && beta && y && mean && rstd)) && (!modulated || mod));
+  if (pass == GN_FWD) sums = ws + p.gsum.off;      // the one-call form keeps the sums in its workspace
+  for (int i = 0; i < p.n; ++i) {
+    const NkNormLaunch& L = p.launch[i];
+    if (L.kernel == NK_GN_STATS) NORM_LAUNCH(L, gn_stats_kernel, (const bf16_t*)x, ws + p.part.off, HW, C, G, p.rows_per);
+    else if (L.kernel == NK_GN_REDUCE) NORM_LAUNCH(L, gn_reduce_partials_kernel, ws + p.part.off, sums, p.nparts, 2 * G);
+    else if (modulated) NORM_LAUNCH(L, gn_apply_kernel<true>, (const bf16_t*)x, sums, gamma, beta, (const bf16_t*)mod, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, p.rows_per);
+    else NORM_LAUNCH(L, gn_apply_kernel<false>, (const bf16_t*)x, sums, gamma, beta, (const bf16_t*)nullptr, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, p.rows_per);
+    if (int e = nk_check_launch(L.name)) return e;
+  }
+  return NK_OK;
 }
 
+static int gn_backward(bool modulated, const void* dy_, const void* x_, const float* gamma, const float* beta, const void* mod_, const float* mean, const float* rstd,
+                       const void* dx_add, void* dx, float* dgamma, float* dbeta, void* dmod, float* ws, int N, int HW, int C, int G, int silu, int accumulate,
+                       void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const NkGnPlan p = nk_gn_plan(N, HW, C, G, GN_BWD, modulated);
+  NORM_PLAN_OR_RETURN(p);
+  NK_CHECK_ARG(dy_ && x_ && gamma && beta && mean && rstd && dx && dgamma && dbeta && ws && (!modulated || (mod_ && dmod)));
+  const bf16_t *dy = (const bf16_t*)dy_, *x = (const bf16_t*)x_, *mod = (const bf16_t*)mod_;
+  float *part = ws + p.part.off, *gsum = ws + p.gsum.off, *chan = ws + p.chan.off;
+  for (int i = 0; i < p.n; ++i) {
+    const NkNormLaunch& L = p.launch[i];
+    switch (L.kernel) {
+      case NK_GN_BWD_STATS:
+        if (modulated) NORM_LAUNCH(L, gn_bwd_stats_kernel<true>, dy, x, gamma, beta, mod, mean, rstd, part, chan, HW, C, G, silu, p.rows_per);
+        else NORM_LAUNCH(L, gn_bwd_stats_kernel<false>, dy, x, gamma, beta, mod, mean, rstd, part, chan, HW, C, G, silu, p.rows_per);
+        break;
+      case NK_GN_REDUCE: NORM_LAUNCH(L, gn_reduce_partials_kernel, part, gsum, p.nparts, 2 * G); break;
+      case NK_GN_COLPART: NORM_LAUNCH(L, colpart_reduce_kernel, chan, dgamma, dbeta, p.chan_rows, C, accumulate); break;
+      case NK_GN_COLPART_MOD: NORM_LAUNCH(L, colpart_reduce_mod_kernel, chan, mod, dgamma, dbeta, p.chan_rows, p.nsplit, C, accumulate); break;
+      case NK_GN_DMOD: NORM_LAUNCH(L, gn_dmod_kernel, chan, gamma, beta, (bf16_t*)dmod, p.nsplit, C); break;
+      case NK_GN_BWD_APPLY:
+        if (modulated) NORM_LAUNCH(L, gn_bwd_apply_kernel<true>, dy, x, gamma, beta, mod, mean, rstd, gsum, (const bf16_t*)dx_add, (bf16_t*)dx, HW, C, G, silu, p.rows_per);
+        else NORM_LAUNCH(L, gn_bwd_apply_kernel<false>, dy, x, gamma, beta, mod, mean, rstd, gsum, (const bf16_t*)dx_add, (bf16_t*)dx, HW, C, G, silu, p.rows_per);
+        break;
+    }
+    if (int e = nk_check_launch(L.name)) return e;
+  }
+  return NK_OK;
+}
+
+// fp32 elements of workspace nk_groupnorm_fwd / _sums / _bwd and their modulated forms need; 0 for a shape they refuse
+extern "C" long nk_groupnorm_ws_floats(int N, int HW, int C, int G) { return nk_gn_plan(N, HW, C, G, GN_BWD, false).ws_floats; }
+
+extern "C" int nk_groupnorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, float* ws, int N, int HW, int C, int G, float eps,
+                                int silu, void* stream) {
+  return gn_forward(GN_FWD, false, x, nullptr, gamma, beta, nullptr, y, mean, rstd, ws, N, HW, C, G, eps, silu, stream);
+}
 // ---- GroupNorm in separable passes: the sums, and the normalisation given the sums.  A convolution's statistics epilogue
 // (conv_halo.h) produces the sums' per-tile partials itself, and its GroupNorm prologue consumes the sums: the passes below are
 // what remains for tensors that come from elsewhere.  sums[n][2g] = sum, sums[n][2g+1] = sum of squares over H*W*(C/G) elements. ----
+extern "C" int nk_groupnorm_sums(const void* x, float* sums, float* ws, int N, int HW, int C, int G, void* stream) {
+  return gn_forward(GN_SUMS, false, x, sums, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws, N, HW, C, G, 0.f, 0, stream);
+}
+extern "C" int nk_groupnorm_apply(const void* x, const float* sums, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int N, int HW, int C, int G,
+                                  float eps, int silu, void* stream) {
+  return gn_forward(GN_APPLY, false, x, (float*)sums, gamma, beta, nullptr, y, mean, rstd, nullptr, N, HW, C, G, eps, silu, stream);
+}
+extern "C" int nk_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean, const float* rstd, const void* dx_add, void* dx,
+                                float* dgamma, float* dbeta, float* ws, int N, int HW, int C, int G, int silu, int accumulate, void* stream) {
+  return gn_backward(false, dy, x, gamma, beta, nullptr, mean, rstd, dx_add, dx, dgamma, dbeta, nullptr, ws, N, HW, C, G, silu, accumulate, stream);
+}
+// ---- the modulated forms (scale-shift norm): same passes, same workspace (nk_groupnorm_ws_floats), mod = bf16 [N][2C] scale | shift ----
+extern "C" int nk_groupnorm_mod_fwd(const void* x, const float* gamma, const float* beta, const void* mod, void* y, float* mean, float* rstd, float* ws, int N, int HW,
+                                    int C, int G, float eps, int silu, void* stream) {
+  return gn_forward(GN_FWD, true, x, nullptr, gamma, beta, mod, y, mean, rstd, ws, N, HW, C, G, eps, silu, stream);
+}
+extern "C" int nk_groupnorm_mod_apply(const void* x, const float* sums, const float* gamma, const float* beta, const void* mod, void* y, float* mean, float* rstd, int N,
+                                      int HW, int C, int G, float eps, int silu, void* stream) {
+  return gn_forward(GN_APPLY, true, x, (float*)sums, gamma, beta, mod, y, mean, rstd, nullptr, N, HW, C, G, eps, silu, stream);
+}
+extern "C" int nk_groupnorm_mod_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const void* mod, const float* mean, const float* rstd,
+                                    const void* dx_add, void* dx, float* dgamma, float* dbeta, void* dmod, float* ws, int N, int HW, int C, int G, int silu,
+                                    int accumulate, void* stream) {
+  return gn_backward(true, dy, x, gamma, beta, mod, mean, rstd, dx_add, dx, dgamma, dbeta, dmod, ws, N, HW, C, G, silu, accumulate, stream);
+}
+
+// ---- sums from a producer's partial rows: one fixed-order level, or two for many rows ----
 __global__ __launch_bounds__(256) void gn_reduce_partials_l1_kernel(const float* __restrict__ part, float* __restrict__ out, int nparts, int G2, int nchunks) {
-  // level 1 of a two-level fixed-order sum for many partial rows: block (chunk, n) sums rows chunk, chunk + nchunks, ... of image n
+  // level 1 of a two-level fixed-order sum for many partial rows: block (chunk, n) sums rows chunk, chunk + nchunks, ... of image n.
+  // Its four row groups combine PAIRWISE, (a + s1) + (s2 + s3): not the ascending fold of nk_reduce_rows, so it keeps its own body.
   __shared__ float sm[4][64];
   const int n = blockIdx.y, chunk = blockIdx.x;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -485,145 +488,29 @@ __global__ __launch_bounds__(256) void gn_reduce_partials_l1_kernel(const float*
   if (ty == 0 && tx < G2) out[((long)n * nchunks + chunk) * G2 + tx] = (a + sm[1][tx]) + (sm[2][tx] + sm[3][tx]);
 }
 
-extern "C" long nk_groupnorm_sums_ws_floats(int N, int nparts, int G) {
-  (void)nparts;
-  return (long)N * 64 * 2 * G + 64;
-}
+extern "C" long nk_groupnorm_sums_ws_floats(int N, int nparts, int G) { return nk_gn_sums_plan(N, nparts, G).ws_floats; }
 extern "C" int nk_groupnorm_sums_from_parts(const float* part, float* sums, float* ws, int N, int nparts, int G, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(part && sums && N > 0 && nparts > 0 && G > 0 && G <= 32);
-  if (nparts > 128) {
-    NK_CHECK_ARG(ws != nullptr);
-    const int nchunks = 64;
-    hipLaunchKernelGGL(gn_reduce_partials_l1_kernel, dim3(nchunks, N), dim3(256), 0, stream, part, ws, nparts, 2 * G, nchunks);
-    if (int e = nk_check_launch("gn_reduce_partials_l1_kernel")) return e;
-    part = ws;
-    nparts = nchunks;
+  const NkGnSumsPlan p = nk_gn_sums_plan(N, nparts, G);
+  NORM_PLAN_OR_RETURN(p);
+  NK_CHECK_ARG(part && sums && (p.levels == 1 || ws));
+  for (int i = 0; i < p.n; ++i) {
+    const NkNormLaunch& L = p.launch[i];
+    if (L.kernel == NK_GN_REDUCE_L1) {
+      NORM_LAUNCH(L, gn_reduce_partials_l1_kernel, part, ws + p.l1.off, nparts, 2 * G, p.nchunks);
+      part = ws + p.l1.off;
+      nparts = p.nchunks;
+    } else {
+      NORM_LAUNCH(L, gn_reduce_partials_kernel, part, sums, nparts, 2 * G);
+    }
+    if (int e = nk_check_launch(L.name)) return e;
   }
-  hipLaunchKernelGGL(gn_reduce_partials_kernel, dim3(N), dim3(1024), 0, stream, part, sums, nparts, 2 * G);
-  return nk_check_launch("gn_reduce_partials_kernel");
-}
-
-extern "C" int nk_groupnorm_sums(const void* x, float* sums, float* ws, int N, int HW, int C, int G, void* stream_) {
-  // the statistics pass of nk_groupnorm_fwd alone; ws: nk_groupnorm_ws_floats(N, HW, C, G) floats
-  hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
-  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
-  NK_CHECK_ARG(x && sums && ws);
-  int nsplit;
-  int rows_per = gn_rows_per(N, HW, &nsplit);
-  const int nz = gn_nz(C);
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(nsplit, N, nz), dim3(GN_THREADS), 0, stream, (const bf16_t*)x, ws, HW, C, G, rows_per);
-  if (int e = nk_check_launch("gn_stats_kernel")) return e;
-  hipLaunchKernelGGL(gn_reduce_partials_kernel, dim3(N), dim3(1024), 0, stream, ws, sums, nsplit * nz, 2 * G);
-  return nk_check_launch("gn_reduce_partials_kernel");
-}
-
-extern "C" int nk_groupnorm_apply(const void* x, const float* sums, const float* gamma, const float* beta, void* y, float* mean,
-                                  float* rstd, int N, int HW, int C, int G, float eps, int silu, void* stream_) {
-  // the normalisation pass of nk_groupnorm_fwd given the sums (from nk_groupnorm_sums or a convolution's statistics epilogue)
-  hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
-  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
-  NK_CHECK_ARG(x && sums && gamma && beta && y && mean && rstd);
-  int nsplit;
-  int rows_per = gn_rows_per(N, HW, &nsplit);
-  hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(nsplit, N), dim3(GN_THREADS), 2 * C * sizeof(float), stream, (const bf16_t*)x, sums, gamma, beta,
-                     (const bf16_t*)nullptr, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, rows_per);
-  return nk_check_launch("gn_apply_kernel");
-}
-
-extern "C" int nk_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta,
-                                const float* mean, const float* rstd, const void* dx_add, void* dx, float* dgamma,
-                                float* dbeta, float* ws, int N, int HW, int C, int G, int silu, int accumulate, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
-  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
-  NK_CHECK_ARG(dy && x && gamma && beta && mean && rstd && dx && dgamma && dbeta && ws);
-  int nsplit;
-  int rows_per = gn_rows_per(N, HW, &nsplit);
-  const int nz = gn_nz(C);
-  float* part = ws;
-  float* gsum = part + (long)N * nsplit * nz * 2 * G;
-  float* chan = gsum + (long)N * 2 * G;
-  hipLaunchKernelGGL(gn_bwd_stats_kernel<false>, dim3(nsplit, N, nz), dim3(GN_THREADS), 2 * C * sizeof(float), stream,
-                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, (const bf16_t*)nullptr, mean, rstd, part, chan, HW, C, G, silu, rows_per);
-  if (int e = nk_check_launch("gn_bwd_stats_kernel")) return e;
-  hipLaunchKernelGGL(gn_reduce_partials_kernel, dim3(N), dim3(1024), 0, stream, part, gsum, nsplit * nz, 2 * G);
-  if (int e = nk_check_launch("gn_reduce_partials_kernel")) return e;
-  hipLaunchKernelGGL(colpart_reduce_kernel, dim3((C + 63) / 64), dim3(1024), 0, stream, chan, dgamma, dbeta, N * nsplit, C, accumulate);
-  if (int e = nk_check_launch("colpart_reduce_kernel")) return e;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel<false>, dim3(nsplit, N), dim3(GN_THREADS), 4 * C * sizeof(float), stream,
-                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, (const bf16_t*)nullptr, mean, rstd, gsum, (const bf16_t*)dx_add,
-                     (bf16_t*)dx, HW, C, G, silu, rows_per);
-  return nk_check_launch("gn_bwd_apply_kernel");
-}
-
-// ---- the modulated forms (scale-shift norm): same passes, same workspace (nk_groupnorm_ws_floats), mod = bf16 [N][2C] scale | shift ----
-static int gn_mod_apply_launch(const void* x, const float* sums, const float* gamma, const float* beta, const void* mod, void* y, float* mean,
-                               float* rstd, int N, int HW, int C, int G, float eps, int silu, hipStream_t stream) {
-  int nsplit;
-  int rows_per = gn_rows_per(N, HW, &nsplit);
-  hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(nsplit, N), dim3(GN_THREADS), 2 * C * sizeof(float), stream, (const bf16_t*)x, sums, gamma, beta,
-                     (const bf16_t*)mod, (bf16_t*)y, mean, rstd, HW, C, G, eps, silu, rows_per);
-  return nk_check_launch("gn_apply_kernel<mod>");
-}
-
-extern "C" int nk_groupnorm_mod_fwd(const void* x, const float* gamma, const float* beta, const void* mod, void* y, float* mean, float* rstd,
-                                    float* ws, int N, int HW, int C, int G, float eps, int silu, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
-  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
-  NK_CHECK_ARG(x && gamma && beta && mod && y && mean && rstd && ws);
-  int nsplit;
-  gn_rows_per(N, HW, &nsplit);
-  float* stats = ws + (long)N * nsplit * gn_nz(C) * 2 * G;
-  if (int e = nk_groupnorm_sums(x, stats, ws, N, HW, C, G, stream_)) return e;
-  return gn_mod_apply_launch(x, stats, gamma, beta, mod, y, mean, rstd, N, HW, C, G, eps, silu, stream);
-}
-
-extern "C" int nk_groupnorm_mod_apply(const void* x, const float* sums, const float* gamma, const float* beta, const void* mod, void* y,
-                                      float* mean, float* rstd, int N, int HW, int C, int G, float eps, int silu, void* stream_) {
-  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
-  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
-  NK_CHECK_ARG(x && sums && gamma && beta && mod && y && mean && rstd);
-  return gn_mod_apply_launch(x, sums, gamma, beta, mod, y, mean, rstd, N, HW, C, G, eps, silu, (hipStream_t)stream_);
-}
-
-extern "C" int nk_groupnorm_mod_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const void* mod, const float* mean,
-                                    const float* rstd, const void* dx_add, void* dx, float* dgamma, float* dbeta, void* dmod, float* ws,
-                                    int N, int HW, int C, int G, int silu, int accumulate, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(N > 0 && HW > 0 && C > 0 && G > 0 && G <= 64);
-  NK_CHECK_ARG((C & 7) == 0 && C % G == 0 && C <= GN_MAXC);
-  NK_CHECK_ARG(dy && x && gamma && beta && mod && mean && rstd && dx && dgamma && dbeta && dmod && ws);
-  int nsplit;
-  int rows_per = gn_rows_per(N, HW, &nsplit);
-  const int nz = gn_nz(C);
-  float* part = ws;
-  float* gsum = part + (long)N * nsplit * nz * 2 * G;
-  float* chan = gsum + (long)N * 2 * G;
-  hipLaunchKernelGGL(gn_bwd_stats_kernel<true>, dim3(nsplit, N, nz), dim3(GN_THREADS), 2 * C * sizeof(float), stream,
-                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, (const bf16_t*)mod, mean, rstd, part, chan, HW, C, G, silu, rows_per);
-  if (int e = nk_check_launch("gn_bwd_stats_kernel<mod>")) return e;
-  hipLaunchKernelGGL(gn_reduce_partials_kernel, dim3(N), dim3(1024), 0, stream, part, gsum, nsplit * nz, 2 * G);
-  if (int e = nk_check_launch("gn_reduce_partials_kernel")) return e;
-  hipLaunchKernelGGL(colpart_reduce_mod_kernel, dim3((C + 63) / 64), dim3(1024), 0, stream, chan, (const bf16_t*)mod, dgamma, dbeta, N * nsplit,
-                     nsplit, C, accumulate);
-  if (int e = nk_check_launch("colpart_reduce_mod_kernel")) return e;
-  hipLaunchKernelGGL(gn_dmod_kernel, dim3((C + 63) / 64, N), dim3(1024), 0, stream, chan, gamma, beta, (bf16_t*)dmod, nsplit, C);
-  if (int e = nk_check_launch("gn_dmod_kernel")) return e;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel<true>, dim3(nsplit, N), dim3(GN_THREADS), 4 * C * sizeof(float), stream,
-                     (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, (const bf16_t*)mod, mean, rstd, gsum, (const bf16_t*)dx_add,
-                     (bf16_t*)dx, HW, C, G, silu, rows_per);
-  return nk_check_launch("gn_bwd_apply_kernel<mod>");
+  return NK_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm over the last dim of [M][C]; one wavefront per row, rows strided over the grid.
 // ------------------------------------------------------------------------------------------------
-#define LN_MAXCH 4   // 16-byte chunks per lane: C <= 64*8*4 = 2048
-
 // NCH = 16-byte chunks per lane actually needed (2: C <= 1024, 3: <= 1536, 4: <= 2048): the per-lane arrays are sized by
 // it, which is what decides the register count and with it how many rows a CU keeps in flight.
 template <int NCH>
@@ -750,7 +637,6 @@ __global__ __launch_bounds__(256, 4) void ln_bwd_dx_kernel(const bf16_t* __restr
 // LayerNorm backward, parameter gradients: part[split][0][c] = sum_rows dy*xhat, part[split][1][c] = sum_rows dy over the
 // split's 64 rows.  Block = 16 row lanes x 16 chunk lanes (256 contiguous bytes per row lane, four rows in flight per
 // thread); splits are combined by colpart_reduce_kernel (single writer per channel, deterministic).
-#define LNP_ROWS 64
 __global__ __launch_bounds__(256) void ln_bwd_param_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
                                                            float* __restrict__ part, int M, int C) {
@@ -803,8 +689,6 @@ __global__ __launch_bounds__(256) void ln_bwd_param_kernel(const bf16_t* __restr
   }
 }
 
-static int ln_param_split(int M) { return (M + LNP_ROWS - 1) / LNP_ROWS; }
-
 // LayerNorm backward in ONE pass over x and dy (round 5; replaces the round-2 one-row-per-wave fused kernel, whose per-wave LDS fold cost
 // more than the row it had processed).  A wave walks SEVERAL rows (row = wave, wave + nwaves, ...: 4 at M = 4096, 8 at M = 16384), the next
 // row's x / dy / residual-gradient loads are issued before the current row's reductions (two rows in flight per wave: these 10-40 MB
@@ -813,8 +697,6 @@ static int ln_param_split(int M) { return (M + LNP_ROWS - 1) / LNP_ROWS; }
 // ((w0 + w2) + (w1 + w3): bit-reproducible) into ONE partial row per block: <= 512 rows, 1.3-2.6 MB, against the 21 MB the separate
 // parameter kernel re-read.  colpart_reduce_kernel / colpart_reduce_batch_kernel sum the partial rows (single writer per channel).
 // Algorithmic traffic 6 B/elem (+2 with dx_add); the three-kernel form moved 10 (+2) and took three launches.
-#define LNR_WAVES 4      // (8 waves x 2 rows: 10.2 vs 11.1 us alone at 4096 x 1280, 20.5 vs 18.0 at 16384 x 640, and the smaller A/B gain in the step)
-#define LNR_MAX_BLOCKS 512
 template <int NCH>
 __global__ __launch_bounds__(LNR_WAVES * 64) void ln_bwd_rows_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                                        const float* __restrict__ gamma, const float* __restrict__ mean,
@@ -925,66 +807,28 @@ __global__ __launch_bounds__(LNR_WAVES * 64) void ln_bwd_rows_kernel(const bf16_
   float* out = part + (long)blockIdx.x * 2 * C;
   for (int c = threadIdx.x; c < 2 * C; c += LNR_WAVES * 64) out[c] = red[c] + red[2 * C + c];
 }
-// one block per 16 rows (four per wave), at most 512 blocks (two per CU; 8 rows per wave at M = 16384)
-static int ln_rows_blocks(int M) {
-  int b = (M + 4 * LNR_WAVES - 1) / (4 * LNR_WAVES);
-  return b < 1 ? 1 : (b > LNR_MAX_BLOCKS ? LNR_MAX_BLOCKS : b);
-}
-
 // Several column-partial reductions in ONE launch (blockIdx.y = entry): the three LayerNorms of a transformer block hand their partial
 // rows to the weight-gradient queue, which reduces them behind the block's batched weight gradients (ops.WgradQueue).
 __global__ __launch_bounds__(1024) void colpart_reduce_batch_kernel(const NkColpartBatch b) {
   // block = 32 channels x 32 row groups: 120 workgroups for three 1280-wide LayerNorms, eight rows per thread at 256 partial rows, all of them
   // in flight at once (the 64 x 16 layout of colpart_reduce_kernel measured 10.4 us per launch in the step: 60 workgroups, 16 dependent rounds)
-  __shared__ float sa[32][33], sb[32][33];
   const int z = blockIdx.y;
-  const int C = b.C[z], nrows = b.nrows[z];
+  const int C = b.C[z];
   if ((int)blockIdx.x * 32 >= C) return;
   const float* __restrict__ part = b.part[z];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + tx;
-  float a = 0.f, v = 0.f;
-  if (c < C) {
-#pragma unroll 8
-    for (int r = ty; r < nrows; r += 32) {
-      a += part[(long)r * 2 * C + c];
-      v += part[(long)r * 2 * C + C + c];
-    }
-  }
-  sa[ty][tx] = a;
-  sb[ty][tx] = v;
-  __syncthreads();
-  if (ty == 0 && c < C) {
-#pragma unroll
-    for (int j = 1; j < 32; ++j) { a += sa[j][tx]; v += sb[j][tx]; }
-    float* dgamma = b.dgamma[z];
-    float* dbeta = b.dbeta[z];
-    dgamma[c] = b.accumulate[z] ? dgamma[c] + a : a;
-    dbeta[c] = b.accumulate[z] ? dbeta[c] + v : v;
-  }
-}
-
-extern "C" int nk_colpart_reduce_batch(const NkColpartBatch* b, void* stream_) {
-  NK_CHECK_ARG(b && b->n > 0 && b->n <= NK_COLPART_MAX);
-  int maxC = 0;
-  for (int z = 0; z < b->n; ++z) {
-    NK_CHECK_ARG(b->part[z] && b->dgamma[z] && b->dbeta[z] && b->nrows[z] > 0 && b->C[z] > 0);
-    maxC = b->C[z] > maxC ? b->C[z] : maxC;
-  }
-  hipLaunchKernelGGL(colpart_reduce_batch_kernel, dim3((maxC + 31) / 32, b->n), dim3(1024), 0, (hipStream_t)stream_, *b);
-  return nk_check_launch("colpart_reduce_batch_kernel");
-}
-
-extern "C" int nk_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
-                                float* rstd, int M, int C, float eps, void* stream) {
-  NK_CHECK_ARG(M > 0 && C > 0 && (C & 7) == 0 && (C >> 3) <= 64 * LN_MAXCH);
-  NK_CHECK_ARG(x && gamma && beta && y && mean && rstd);
-  int blocks = min((M + 3) / 4, 4096);
-  const int nch = ((C >> 3) + 63) / 64;
-#define NK_LN_FWD(NCH_) hipLaunchKernelGGL(ln_fwd_kernel<NCH_>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, gamma, beta, (bf16_t*)y, mean, rstd, M, C, eps)
-  if (nch <= 2) NK_LN_FWD(2); else if (nch == 3) NK_LN_FWD(3); else NK_LN_FWD(4);
-#undef NK_LN_FWD
-  return nk_check_launch("ln_fwd_kernel");
+  const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+  nk_reduce_rows<32, 32, 2, 1, 8>(
+      c < C, b.nrows[z],
+      [&](int r, float* a) {
+        a[0] += part[(long)r * 2 * C + c];
+        a[1] += part[(long)r * 2 * C + C + c];
+      },
+      [&](const float* a) {
+        float* dgamma = b.dgamma[z];
+        float* dbeta = b.dbeta[z];
+        dgamma[c] = b.accumulate[z] ? dgamma[c] + a[0] : a[0];
+        dbeta[c] = b.accumulate[z] ? dbeta[c] + a[1] : a[1];
+      });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -992,7 +836,6 @@ extern "C" int nk_layernorm_fwd(const void* x, const float* gamma, const float* 
 // One wavefront per row as in ln_fwd_kernel.  The sum of squares is a per-lane sum over the lane's chunks in chunk order, then the xor
 // butterfly: a fixed order that depends on C alone, so a row's bits do not depend on M or on which wave got the row.
 // ------------------------------------------------------------------------------------------------
-#define RMS_MAXCH 8   // 16-byte chunks per lane: C <= 64*8*8 = 4096 (T5-v1.1-XXL)
 template <int NCH>
 __global__ __launch_bounds__(256) void rms_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma, bf16_t* __restrict__ y, int M, int C,
                                                       float eps) {
@@ -1034,87 +877,92 @@ __global__ __launch_bounds__(256) void rms_fwd_kernel(const bf16_t* __restrict__
   }
 }
 
+// ---- LayerNorm / RMSNorm / column partials, host side: one runner -- plan (norm_plan.h: nk_rownorm_plan), check the pointers the kind needs,
+// run the plan's launches in order.  nch_dispatch: f(integral_constant<NCH>) for the chunks-per-lane instance the plan chose. ----
+template <int... NCH, class F>
+static void nch_dispatch(int nch, F f) {
+  ((nch == NCH ? f(std::integral_constant<int, NCH>{}) : void()), ...);
+}
+
+struct RowNormArgs {
+  const void *dy, *x, *dx_add;
+  const float *gamma, *beta, *mean, *rstd;      // mean / rstd: written by the forward, read by the backward
+  void* out;                                    // y or dx
+  float *dgamma, *dbeta, *part;
+};
+// ptrs: the entry point's own "every pointer it needs is there" (evaluated by the caller, examined only behind plan-only mode)
+static int rownorm_run(int kind, bool ptrs, const RowNormArgs& a, int M, int C, float eps, int accumulate, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const NkRowNormPlan p = nk_rownorm_plan(M, C, kind);
+  NORM_PLAN_OR_RETURN(p);
+  NK_CHECK_ARG(ptrs && "a required pointer argument is null");
+  if (kind == RMS_FWD) NK_CHECK_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.out & 15) == 0 && ((uintptr_t)a.gamma & 15) == 0);     // 16-byte accesses
+  const bf16_t *dy = (const bf16_t*)a.dy, *x = (const bf16_t*)a.x, *dx_add = (const bf16_t*)a.dx_add;
+  bf16_t* out = (bf16_t*)a.out;
+  float* part = a.part + p.part.off;
+  for (int i = 0; i < p.n; ++i) {
+    const NkNormLaunch& L = p.launch[i];
+    switch (L.kernel) {
+      case NK_LN_FWD:
+        nch_dispatch<2, 3, 4>(p.nch, [&](auto n) { NORM_LAUNCH(L, ln_fwd_kernel<decltype(n)::value>, x, a.gamma, a.beta, out, (float*)a.mean, (float*)a.rstd, M, C, eps); });
+        break;
+      case NK_RMS_FWD: nch_dispatch<2, 4, 8>(p.nch, [&](auto n) { NORM_LAUNCH(L, rms_fwd_kernel<decltype(n)::value>, x, a.gamma, out, M, C, eps); }); break;
+      case NK_LN_BWD_DX:
+        // input gradient: one wavefront per row.  (Fewer, longer-lived workgroups -- a grid capped at 256 / 512 / 1024 blocks with the rows
+        // strided over them -- make no difference beside the weight-gradient stream: 180.4 / 180.3 / 180.2 vs 180.1 ms per step.)
+        nch_dispatch<2, 3, 4>(p.nch, [&](auto n) { NORM_LAUNCH(L, ln_bwd_dx_kernel<decltype(n)::value>, dy, x, a.gamma, a.mean, a.rstd, dx_add, out, M, C); });
+        break;
+      case NK_LN_BWD_PARAM: NORM_LAUNCH(L, ln_bwd_param_kernel, dy, x, a.mean, a.rstd, part, M, C); break;      // column partials over row splits
+      case NK_LN_BWD_ROWS:
+        nch_dispatch<2, 3, 4>(p.nch, [&](auto n) {
+          nk_optin_lds((const void*)ln_bwd_rows_kernel<decltype(n)::value>, LNR_MAX_SMEM);
+          NORM_LAUNCH(L, ln_bwd_rows_kernel<decltype(n)::value>, dy, x, a.gamma, a.mean, a.rstd, dx_add, out, part, M, C);
+        });
+        break;
+      case NK_LN_COLPART: NORM_LAUNCH(L, colpart_reduce_kernel, part, a.dgamma, a.dbeta, p.nrows, C, accumulate); break;      // the single-writer reduce
+    }
+    if (int e = nk_check_launch(L.name)) return e;
+  }
+  return NK_OK;
+}
+
+// the size for every C that any entry point using it accepts: nk_layernorm_bwd_params takes widths beyond LN_MAXCH
+extern "C" long nk_layernorm_ws_floats(int M, int C) { return nk_rownorm_plan(M, C, LN_BWD_PARAMS).ws_floats; }
+extern "C" long nk_layernorm_part_rows(int M) { return nk_rownorm_plan(M, 8, LN_BWD_ROWS).part_rows; }
+
+extern "C" int nk_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M, int C, float eps, void* stream) {
+  return rownorm_run(LN_FWD, x && gamma && beta && y && mean && rstd, {nullptr, x, nullptr, gamma, beta, mean, rstd, y}, M, C, eps, 0, stream);
+}
 extern "C" int nk_rmsnorm_fwd(const void* x, const float* gamma, void* y, int M, int C, float eps, void* stream) {
-  NK_CHECK_ARG(M > 0 && C > 0 && (C & 7) == 0 && (C >> 3) <= 64 * RMS_MAXCH);
-  NK_CHECK_ARG(x && gamma && y);
-  NK_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0);     // 16-byte accesses
-  int blocks = min((M + 3) / 4, 4096);
-  const int nch = ((C >> 3) + 63) / 64;
-#define NK_RMS_FWD(NCH_) hipLaunchKernelGGL(rms_fwd_kernel<NCH_>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, gamma, (bf16_t*)y, M, C, eps)
-  if (nch <= 2) NK_RMS_FWD(2); else if (nch <= 4) NK_RMS_FWD(4); else NK_RMS_FWD(8);
-#undef NK_RMS_FWD
-  return nk_check_launch("rms_fwd_kernel");
+  return rownorm_run(RMS_FWD, x && gamma && y, {nullptr, x, nullptr, gamma, nullptr, nullptr, nullptr, y}, M, C, eps, 0, stream);
+}
+/* The backward in two parts, so the caller can run the parameter gradients (off the critical path) on another stream ... */
+extern "C" int nk_layernorm_bwd_dx(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dx_add, void* dx, int M, int C,
+                                   void* stream) {
+  return rownorm_run(LN_BWD_DX, dy && x && gamma && mean && rstd && dx, {dy, x, dx_add, gamma, nullptr, mean, rstd, dx}, M, C, 0.f, 0, stream);
+}
+extern "C" int nk_layernorm_bwd_params(const void* dy, const void* x, const float* mean, const float* rstd, float* dgamma, float* dbeta, float* ws, int M, int C,
+                                       int accumulate, void* stream) {
+  return rownorm_run(LN_BWD_PARAMS, dy && x && mean && rstd && dgamma && dbeta && ws, {dy, x, nullptr, nullptr, nullptr, mean, rstd, nullptr, dgamma, dbeta, ws}, M, C, 0.f, accumulate, stream);
+}
+/* ... dx and nk_layernorm_part_rows(M) partial rows [rows][2][C] (dgamma partials, dbeta partials) in one pass; the caller reduces the rows with
+ * nk_colpart_reduce_batch (any stream, any later time: `part` is the only state) ... */
+extern "C" int nk_layernorm_bwd_rows(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dx_add, void* dx, float* part,
+                                     int M, int C, void* stream) {
+  return rownorm_run(LN_BWD_ROWS, dy && x && gamma && mean && rstd && dx && part, {dy, x, dx_add, gamma, nullptr, mean, rstd, dx, nullptr, nullptr, part}, M, C, 0.f, 0, stream);
+}
+/* ... or one pass over x and dy for the input gradient AND the per-block parameter partials, then the single-writer column reduce */
+extern "C" int nk_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dx_add, void* dx, float* dgamma,
+                                float* dbeta, float* ws, int M, int C, int accumulate, void* stream) {
+  return rownorm_run(LN_BWD, dy && x && gamma && mean && rstd && dx && dgamma && dbeta && ws, {dy, x, dx_add, gamma, nullptr, mean, rstd, dx, dgamma, dbeta, ws}, M, C, 0.f, accumulate, stream);
 }
 
-extern "C" long nk_layernorm_ws_floats(int M, int C) {
-  const long a = (long)ln_param_split(M), b = LNR_MAX_BLOCKS;
-  return (a > b ? a : b) * 2 * C + 64;
-}
-
-extern "C" long nk_layernorm_part_rows(int M) { return ln_rows_blocks(M); }
-
-extern "C" int nk_layernorm_bwd_dx(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                   const void* dx_add, void* dx, int M, int C, void* stream_) {
+extern "C" int nk_colpart_reduce_batch(const NkColpartBatch* b, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(M > 0 && C > 0 && (C & 7) == 0 && (C >> 3) <= 64 * LN_MAXCH);
-  NK_CHECK_ARG(dy && x && gamma && mean && rstd && dx);
-  // input gradient: one wavefront per row.  (Fewer, longer-lived workgroups -- a grid capped at 256 / 512 / 1024 blocks with the rows
-  // strided over them -- make no difference beside the weight-gradient stream: 180.4 / 180.3 / 180.2 vs 180.1 ms per step.)
-  const int blocks = min((M + 3) / 4, 4096);
-  const int nch = ((C >> 3) + 63) / 64;
-#define NK_LN_DX(NCH_) hipLaunchKernelGGL(ln_bwd_dx_kernel<NCH_>, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)x, gamma, mean, rstd, (const bf16_t*)dx_add, (bf16_t*)dx, M, C)
-  if (nch <= 2) NK_LN_DX(2); else if (nch == 3) NK_LN_DX(3); else NK_LN_DX(4);
-#undef NK_LN_DX
-  return nk_check_launch("ln_bwd_dx_kernel");
-}
-
-extern "C" int nk_layernorm_bwd_params(const void* dy, const void* x, const float* mean, const float* rstd, float* dgamma,
-                                       float* dbeta, float* ws, int M, int C, int accumulate, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(M > 0 && C > 0 && (C & 7) == 0);
-  NK_CHECK_ARG(dy && x && mean && rstd && dgamma && dbeta && ws);
-  // parameter gradients: column-parallel partial sums over row splits, then a single-writer reduce
-  const int nsplit = ln_param_split(M);
-  hipLaunchKernelGGL(ln_bwd_param_kernel, dim3(nsplit, (C + 127) / 128), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)x,
-                     mean, rstd, ws, M, C);
-  if (int e = nk_check_launch("ln_bwd_param_kernel")) return e;
-  hipLaunchKernelGGL(colpart_reduce_kernel, dim3((C + 63) / 64), dim3(1024), 0, stream, ws, dgamma, dbeta, nsplit, C, accumulate);
-  return nk_check_launch("colpart_reduce_kernel");
-}
-
-static int launch_ln_rows(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dx_add,
-                          void* dx, float* part, int M, int C, hipStream_t stream) {
-  const int blocks = ln_rows_blocks(M);
-  const int nch = ((C >> 3) + 63) / 64;
-  const int smem = 2 * 2 * C * (int)sizeof(float);
-#define NK_LN_ROWS(NCH_)                                                                                                       \
-  do {                                                                                                                          \
-    nk_optin_lds((const void*)ln_bwd_rows_kernel<NCH_>, 2 * 2 * 2048 * 4);                                                      \
-    hipLaunchKernelGGL(ln_bwd_rows_kernel<NCH_>, dim3(blocks), dim3(LNR_WAVES * 64), smem, stream, (const bf16_t*)dy, (const bf16_t*)x, gamma, mean, rstd,   \
-                       (const bf16_t*)dx_add, (bf16_t*)dx, part, M, C);                                                        \
-  } while (0)
-  if (nch <= 2) NK_LN_ROWS(2); else if (nch == 3) NK_LN_ROWS(3); else NK_LN_ROWS(4);
-#undef NK_LN_ROWS
-  return nk_check_launch("ln_bwd_rows_kernel");
-}
-
-/* dx and nk_layernorm_part_rows(M) partial rows [rows][2][C] (dgamma partials, dbeta partials) in one pass; the caller reduces the rows with
- * nk_colpart_reduce_batch (any stream, any later time: `part` is the only state) */
-extern "C" int nk_layernorm_bwd_rows(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                     const void* dx_add, void* dx, float* part, int M, int C, void* stream_) {
-  NK_CHECK_ARG(M > 0 && C > 0 && (C & 7) == 0 && (C >> 3) <= 64 * LN_MAXCH);
-  NK_CHECK_ARG(dy && x && gamma && mean && rstd && dx && part);
-  return launch_ln_rows(dy, x, gamma, mean, rstd, dx_add, dx, part, M, C, (hipStream_t)stream_);
-}
-
-extern "C" int nk_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
-                                const float* rstd, const void* dx_add, void* dx, float* dgamma, float* dbeta, float* ws,
-                                int M, int C, int accumulate, void* stream_) {
-  // one pass over x and dy for the input gradient AND the per-block parameter partials, then the single-writer column reduce
-  hipStream_t stream = (hipStream_t)stream_;
-  NK_CHECK_ARG(M > 0 && C > 0 && (C & 7) == 0 && (C >> 3) <= 64 * LN_MAXCH);
-  NK_CHECK_ARG(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && ws);
-  if (int e = launch_ln_rows(dy, x, gamma, mean, rstd, dx_add, dx, ws, M, C, stream)) return e;
-  hipLaunchKernelGGL(colpart_reduce_kernel, dim3((C + 63) / 64), dim3(1024), 0, stream, ws, dgamma, dbeta, ln_rows_blocks(M), C, accumulate);
-  return nk_check_launch("colpart_reduce_kernel");
+  NK_CHECK_ARG(b != nullptr);
+  const NkNormPlan p = nk_colpart_batch_plan(b->C, b->n);
+  NORM_PLAN_OR_RETURN(p);
+  for (int z = 0; z < b->n; ++z) NK_CHECK_ARG(b->part[z] && b->dgamma[z] && b->dbeta[z] && b->nrows[z] > 0);
+  NORM_LAUNCH(p.launch[0], colpart_reduce_batch_kernel, *b);
+  return nk_check_launch(p.launch[0].name);
 }

@@ -204,15 +204,16 @@ def load() -> C.CDLL:
 
 def launch_log(mode: int) -> None:
     """Test hook: 1 = log the kernel name of every launch of this thread (cleared), 2 = clear, 0 = off; 3 = log on and PLAN-ONLY: the tile
-    engine (nk_gemm_dispatch) and the attention entry points log the launches they plan and return before they touch the GPU -- usable on a
-    machine without one."""
+    engine (nk_gemm_dispatch), the attention and the norm / column-sum entry points log the launches they plan and return before they touch
+    the GPU -- usable on a machine without one."""
     call("nk_debug_launch_log", int(mode))
 
 
 def launched() -> list[str]:
     """Test hook: the kernel names logged since the last clear, in launch order; behind the name of a tile-engine launch follows its plan,
     one line: `name grid=x,y,z block smem splitk ksplit_len acc zero krot gm chunk`; behind each planned attention launch (plan-only mode)
-    `name grid=x,y,z block smem gx qsplit part_offset ws_floats`."""
+    `name grid=x,y,z block smem gx qsplit part_offset ws_floats`; behind each planned norm / column-sum launch
+    `name grid=x,y,z block smem [region=offset+extent ...] ws=ws_floats`."""
     buf = C.create_string_buffer(8192)
     n = query("nk_debug_launch_names", buf, len(buf))
     if n < 0:

@@ -698,66 +698,49 @@ def conv2d_fwd(x: Img, weight: Tensor, bias: Optional[Tensor], stride: int = 1, 
 # ------------------------------------------------------------------------------------------------
 # norms / activations
 # ------------------------------------------------------------------------------------------------
-def groupnorm_fwd(x: Img, weight: Tensor, bias: Tensor, groups: int, eps: float, silu: bool):
-    """GroupNorm (+SiLU).  bwd(dy, dx_add=None) -> dx token matrix."""
+def groupnorm_fwd(x: Img, weight: Tensor, bias: Tensor, groups: int, eps: float, silu: bool, mod: Optional[Tensor] = None):
+    """GroupNorm (+SiLU).  bwd(dy, dx_add=None) -> dx token matrix.
+    With mod, the scale-shift modulated form: y = silu?(GN(x) * (1 + scale) + shift), mod = bf16 [N, 2C] with scale in the first C columns and
+    shift in the last (ResBlock use_scale_shift_norm, openaimodel.py:332-336); bwd(dy, dx_add=None) -> (dx token matrix, dmod [N, 2C])."""
+    what = "groupnorm" if mod is None else "groupnorm_mod"
     if not x.t.is_contiguous():
-        raise ValueError("groupnorm: x must be dense channels-last")
+        raise ValueError(f"{what}: x must be dense channels-last")
     N, HW, Cc = x.N, x.H * x.W, x.C
+    if mod is not None:
+        _check2d(mod, "mod")
+        if tuple(mod.shape) != (N, 2 * Cc) or not mod.is_contiguous():
+            raise ValueError(f"groupnorm_mod: mod must be a dense [{N}, {2 * Cc}] (scale | shift) matrix, got {tuple(mod.shape)}")
+    entry, mp = "nk_" + what, () if mod is None else (mod.data_ptr(),)      # the modulated entry points take mod behind beta
     y = torch.empty_like(x.t)
     mean = torch.empty(N, groups, dtype=torch.float32, device=x.t.device)
     rstd = torch.empty_like(mean)
     nws = query("nk_groupnorm_ws_floats", N, HW, Cc, groups)
     if x.sums is not None and x.sums.shape == (N, 2 * groups):
         # the producer's statistics epilogue already summed x: the normalisation pass alone
-        call("nk_groupnorm_apply", x.t.data_ptr(), x.sums.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(),
+        call(entry + "_apply", x.t.data_ptr(), x.sums.data_ptr(), weight.data_ptr(), bias.data_ptr(), *mp, y.data_ptr(), mean.data_ptr(),
              rstd.data_ptr(), N, HW, Cc, groups, float(eps), int(silu), _stream())
     else:
         ws = _ws(nws, x.t.device)
-        call("nk_groupnorm_fwd", x.t.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+        call(entry + "_fwd", x.t.data_ptr(), weight.data_ptr(), bias.data_ptr(), *mp, y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
              ws.data_ptr(), N, HW, Cc, groups, float(eps), int(silu), _stream())
 
     def bwd(dy: Tensor, dx_add: Optional[Tensor] = None):
         dx = torch.empty_like(x.t)
+        dmod = () if mod is None else (torch.empty_like(mod),)
         ws2 = _ws(nws, dy.device)
-        call("nk_groupnorm_bwd", dy.data_ptr(), x.t.data_ptr(), weight.data_ptr(), bias.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-             _p(dx_add), dx.data_ptr(), grad_flat(weight).data_ptr(), grad_flat(bias).data_ptr(), ws2.data_ptr(), N, HW, Cc, groups,
-             int(silu), int(state_of(weight).grad_accumulate), _stream())
-        return dx
+        call(entry + "_bwd", dy.data_ptr(), x.t.data_ptr(), weight.data_ptr(), bias.data_ptr(), *mp, mean.data_ptr(), rstd.data_ptr(),
+             _p(dx_add), dx.data_ptr(), grad_flat(weight).data_ptr(), grad_flat(bias).data_ptr(), *(t.data_ptr() for t in dmod), ws2.data_ptr(),
+             N, HW, Cc, groups, int(silu), int(state_of(weight).grad_accumulate), _stream())
+        return (dx, *dmod) if dmod else dx
 
     return Img(y, x.N, x.H, x.W), bwd
 
 
 def groupnorm_mod_fwd(x: Img, weight: Tensor, bias: Tensor, mod: Tensor, groups: int, eps: float, silu: bool):
-    """Scale-shift modulated GroupNorm (+SiLU): y = silu?(GN(x) * (1 + scale) + shift), mod = bf16 [N, 2C] with scale in the first C columns
-    and shift in the last (ResBlock use_scale_shift_norm, openaimodel.py:332-336).  bwd(dy, dx_add=None) -> (dx token matrix, dmod [N, 2C])."""
-    if not x.t.is_contiguous():
-        raise ValueError("groupnorm_mod: x must be dense channels-last")
-    N, HW, Cc = x.N, x.H * x.W, x.C
-    _check2d(mod, "mod")
-    if tuple(mod.shape) != (N, 2 * Cc) or not mod.is_contiguous():
-        raise ValueError(f"groupnorm_mod: mod must be a dense [{N}, {2 * Cc}] (scale | shift) matrix, got {tuple(mod.shape)}")
-    y = torch.empty_like(x.t)
-    mean = torch.empty(N, groups, dtype=torch.float32, device=x.t.device)
-    rstd = torch.empty_like(mean)
-    nws = query("nk_groupnorm_ws_floats", N, HW, Cc, groups)
-    if x.sums is not None and x.sums.shape == (N, 2 * groups):
-        call("nk_groupnorm_mod_apply", x.t.data_ptr(), x.sums.data_ptr(), weight.data_ptr(), bias.data_ptr(), mod.data_ptr(), y.data_ptr(),
-             mean.data_ptr(), rstd.data_ptr(), N, HW, Cc, groups, float(eps), int(silu), _stream())
-    else:
-        ws = _ws(nws, x.t.device)
-        call("nk_groupnorm_mod_fwd", x.t.data_ptr(), weight.data_ptr(), bias.data_ptr(), mod.data_ptr(), y.data_ptr(), mean.data_ptr(),
-             rstd.data_ptr(), ws.data_ptr(), N, HW, Cc, groups, float(eps), int(silu), _stream())
-
-    def bwd(dy: Tensor, dx_add: Optional[Tensor] = None):
-        dx = torch.empty_like(x.t)
-        dmod = torch.empty_like(mod)
-        ws2 = _ws(nws, dy.device)
-        call("nk_groupnorm_mod_bwd", dy.data_ptr(), x.t.data_ptr(), weight.data_ptr(), bias.data_ptr(), mod.data_ptr(), mean.data_ptr(),
-             rstd.data_ptr(), _p(dx_add), dx.data_ptr(), grad_flat(weight).data_ptr(), grad_flat(bias).data_ptr(), dmod.data_ptr(),
-             ws2.data_ptr(), N, HW, Cc, groups, int(silu), int(state_of(weight).grad_accumulate), _stream())
-        return dx, dmod
-
-    return Img(y, x.N, x.H, x.W), bwd
+    """groupnorm_fwd with the per-image scale-shift modulation mod (required here): bwd -> (dx, dmod)."""
+    if mod is None:
+        raise ValueError("groupnorm_mod: mod is required")
+    return groupnorm_fwd(x, weight, bias, groups, eps, silu, mod=mod)
 
 
 def layernorm_fwd(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5):

@@ -178,16 +178,37 @@ layernorm.register_autograd(_ln_bwd, setup_context=_ln_setup)
 # ---------------------------------------------------------------------------------------------------------------
 # GroupNorm (+SiLU) on channels-last tokens [N*HW, C]
 # ---------------------------------------------------------------------------------------------------------------
-@_op("groupnorm_silu_fwd")
-def groupnorm_silu_fwd(x: Tensor, gamma: Tensor, beta: Tensor, N: int, groups: int, eps: float, silu: bool) -> Tuple[Tensor, Tensor, Tensor]:
+def _gn_fwd_eager(x, gamma, beta, mod, N, groups, eps, silu):
+    """the eager body of groupnorm_silu_fwd (mod None) and groupnorm_mod_fwd: (y, mean, rstd)"""
     HW, C = x.shape[0] // N, x.shape[1]
     y = torch.empty_like(x)
     mean = torch.empty(N, groups, dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
     ws = ops._ws(ops.query("nk_groupnorm_ws_floats", N, HW, C, groups), x.device)
-    ops.call("nk_groupnorm_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), N, HW, C, groups,
-             float(eps), int(silu), ops._stream())
+    mp = () if mod is None else (mod.data_ptr(),)
+    ops.call("nk_groupnorm_fwd" if mod is None else "nk_groupnorm_mod_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), *mp, y.data_ptr(), mean.data_ptr(),
+             rstd.data_ptr(), ws.data_ptr(), N, HW, C, groups, float(eps), int(silu), ops._stream())
     return y, mean, rstd
+
+
+def _gn_bwd_eager(dy, x, gamma, beta, mod, mean, rstd, N, groups, silu):
+    """the eager body of groupnorm_silu_bwd (mod None) and groupnorm_mod_bwd: (dx, dgamma, dbeta) and, with mod, dmod"""
+    HW, C = x.shape[0] // N, x.shape[1]
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty_like(dg)
+    dmod = () if mod is None else (torch.empty_like(mod),)
+    ws = ops._ws(ops.query("nk_groupnorm_ws_floats", N, HW, C, groups), x.device)
+    mp = () if mod is None else (mod.data_ptr(),)
+    ops.call("nk_groupnorm_bwd" if mod is None else "nk_groupnorm_mod_bwd", dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), *mp, mean.data_ptr(),
+             rstd.data_ptr(), None, dx.data_ptr(), dg.data_ptr(), db.data_ptr(), *(t.data_ptr() for t in dmod), ws.data_ptr(), N, HW, C, groups, int(silu), 0,
+             ops._stream())
+    return (dx, dg, db, *dmod)
+
+
+@_op("groupnorm_silu_fwd")
+def groupnorm_silu_fwd(x: Tensor, gamma: Tensor, beta: Tensor, N: int, groups: int, eps: float, silu: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    return _gn_fwd_eager(x, gamma, beta, None, N, groups, eps, silu)
 
 
 @groupnorm_silu_fwd.register_fake
@@ -197,14 +218,7 @@ def _(x, gamma, beta, N, groups, eps, silu):
 
 @_op("groupnorm_silu_bwd")
 def groupnorm_silu_bwd(dy: Tensor, x: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, rstd: Tensor, N: int, groups: int, silu: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    HW, C = x.shape[0] // N, x.shape[1]
-    dx = torch.empty_like(x)
-    dg = torch.empty(C, dtype=torch.float32, device=x.device)
-    db = torch.empty_like(dg)
-    ws = ops._ws(ops.query("nk_groupnorm_ws_floats", N, HW, C, groups), x.device)
-    ops.call("nk_groupnorm_bwd", dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr(), None, dx.data_ptr(), dg.data_ptr(),
-             db.data_ptr(), ws.data_ptr(), N, HW, C, groups, int(silu), 0, ops._stream())
-    return dx, dg, db
+    return _gn_bwd_eager(dy, x, gamma, beta, None, mean, rstd, N, groups, silu)
 
 
 @groupnorm_silu_bwd.register_fake
@@ -242,14 +256,7 @@ groupnorm_silu.register_autograd(_gn_bwd, setup_context=_gn_setup)
 # ... with the per-image scale-shift modulation of the ADM ResBlock: y = silu?(GN(x) * (1 + mod[:, :C]) + mod[:, C:]), mod bf16 [N, 2C]
 @_op("groupnorm_mod_fwd")
 def groupnorm_mod_fwd(x: Tensor, gamma: Tensor, beta: Tensor, mod: Tensor, N: int, groups: int, eps: float, silu: bool) -> Tuple[Tensor, Tensor, Tensor]:
-    HW, C = x.shape[0] // N, x.shape[1]
-    y = torch.empty_like(x)
-    mean = torch.empty(N, groups, dtype=torch.float32, device=x.device)
-    rstd = torch.empty_like(mean)
-    ws = ops._ws(ops.query("nk_groupnorm_ws_floats", N, HW, C, groups), x.device)
-    ops.call("nk_groupnorm_mod_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mod.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(),
-             N, HW, C, groups, float(eps), int(silu), ops._stream())
-    return y, mean, rstd
+    return _gn_fwd_eager(x, gamma, beta, mod, N, groups, eps, silu)
 
 
 @groupnorm_mod_fwd.register_fake
@@ -260,15 +267,7 @@ def _(x, gamma, beta, mod, N, groups, eps, silu):
 @_op("groupnorm_mod_bwd")
 def groupnorm_mod_bwd(dy: Tensor, x: Tensor, gamma: Tensor, beta: Tensor, mod: Tensor, mean: Tensor, rstd: Tensor, N: int, groups: int,
                       silu: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    HW, C = x.shape[0] // N, x.shape[1]
-    dx = torch.empty_like(x)
-    dg = torch.empty(C, dtype=torch.float32, device=x.device)
-    db = torch.empty_like(dg)
-    dmod = torch.empty_like(mod)
-    ws = ops._ws(ops.query("nk_groupnorm_ws_floats", N, HW, C, groups), x.device)
-    ops.call("nk_groupnorm_mod_bwd", dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mod.data_ptr(), mean.data_ptr(), rstd.data_ptr(), None,
-             dx.data_ptr(), dg.data_ptr(), db.data_ptr(), dmod.data_ptr(), ws.data_ptr(), N, HW, C, groups, int(silu), 0, ops._stream())
-    return dx, dg, db, dmod
+    return _gn_bwd_eager(dy, x, gamma, beta, mod, mean, rstd, N, groups, silu)
 
 
 @groupnorm_mod_bwd.register_fake
