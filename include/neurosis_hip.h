@@ -404,6 +404,20 @@ long nk_vq_quantize_ws_floats(long N);
 int nk_vq_quantize(const long long* idx, const float* codebook, const float* z, long ldz, float* zq, float* sumsq, float* ws, long N, int D,
                    int n_e, int HW, void* stream);
 
+/* Separable banded resampler on dense fp32 planes, csrc/resample.hip: y[p] = Wv . x[p] . Wh^T for p < P, x [P][H][W] -> y [P][OH][OW].
+ * With the tables of F.interpolate(mode="bicubic", antialias=True) it is the resize_input / resize_target step of the autoencoder losses
+ * (modules/autoencoding/losses/vae_lpips_discr.py:104-107, :326-329); called with the transposed tables ([H x OH], [W x OW]) and the sizes
+ * swapped it is that step's adjoint -- one kernel pair for both directions, no atomics, bit-identical from run to run.
+ * A banded matrix with n_out rows is three device arrays: start[n_out] and count[n_out] (int32: row i has its non-zeros in columns
+ * start[i] .. start[i] + count[i] - 1, inside the input) and weights[n_out][taps] fp32, each row padded with zeros; v_* is Wv [OH x H],
+ * h_* is Wh [OW x W].  ws: nk_resample_ws_floats(P, H, W, OH, OW) floats, the intermediate of the two passes (the smaller of
+ * [P][OH][W] and [P][H][OW]); x, y and ws must not overlap.  No size has a divisibility requirement; P * max(H, OH) * max(W, OW) <= 2^38.
+ * The launch allocates nothing, synchronises nothing and reads nothing on the host: it can be captured into a graph. */
+long nk_resample_ws_floats(long P, int H, int W, int OH, int OW);
+int nk_resample_planes(const float* x, float* y, float* ws, const int* v_start, const int* v_count, const float* v_weights, int v_taps,
+                       const int* h_start, const int* h_count, const float* h_weights, int h_taps, long P, int H, int W, int OH, int OW,
+                       void* stream);
+
 /* timestep_embedding (modules/diffusion/util.py:152-177): out[B][dim] bf16 = [cos | sin](t * freq) */
 int nk_timestep_embedding(const float* t, void* out, int B, int dim, float max_period, void* stream);
 

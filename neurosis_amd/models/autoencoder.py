@@ -129,9 +129,10 @@ class AutoencodingEngine(nn.Module):
     def __init__(self, *, encoder: Encoder, decoder: Decoder, loss="l2", regularizer: Optional[nn.Module] = None, input_key: str = "image",
                  regularization_weights: Optional[dict] = None, discriminator: Optional[nn.Module] = None, disc_loss: str = "hinge", disc_start: int = 0,
                  disc_factor: float = 1.0, disc_weight: float = 1.0, rec_weight: float = 1.0, logvar_init: float = 0.0, learn_logvar: bool = False,
-                 perceptual_loss: Optional[nn.Module] = None, perceptual_weight: float = 1.0, **kwargs):
+                 perceptual_loss: Optional[nn.Module] = None, perceptual_weight: float = 1.0, resize: Optional[str] = None, **kwargs):
         super().__init__()
         self.encoder, self.decoder = encoder, decoder
+        self.perceptual_only = False
         self.disc_store: Optional[FlatParamStore] = None
         self.regularization = regularizer if regularizer is not None else DiagonalGaussianRegularizer()
         if hasattr(loss, "engine_settings"):
@@ -155,6 +156,12 @@ class AutoencodingEngine(nn.Module):
             if regularization_weights is None:
                 regularization_weights = cfg["regularization_weights"]
             loss = cfg["rec_loss_type"]
+            resize = resize if resize is not None else cfg.get("resize")
+            # AutoencoderPerceptual: clamped images, per-sample means, no discriminator (_perceptual_loss); its LPIPS is read from the loss
+            # object at each step, so that `delay_setup` / `configure_model()` work as in the reference
+            self.perceptual_only = bool(cfg.get("perceptual_only", False))
+            if self.perceptual_only:
+                self.perceptual_weight = cfg["perceptual_weight"]
         else:
             # adversarial part as keyword arguments (GeneralLPIPSWithDiscriminator's, discriminator_loss.py:23-40)
             self.discriminator = discriminator
@@ -177,6 +184,12 @@ class AutoencodingEngine(nn.Module):
         else:
             raise NotImplementedError("loss must be 'l2' / 'l1' (or nn.MSELoss / nn.L1Loss), or one of the loss classes of "
                                       "neurosis_amd.modules.autoencoding.losses; got " + type(loss).__name__)
+        # decoder output of another size than the input (an autoencoder whose decoder has more or fewer levels than its encoder): "input"
+        # resamples the input to the reconstruction's size, "target" the reconstruction to the input's (resize_input / resize_target of the
+        # loss classes; antialiased bicubic, ops.resize_bicubic_aa); None refuses such a pair
+        if resize not in (None, "input", "target"):
+            raise ValueError(f"resize must be None, 'input' or 'target', got {resize!r}")
+        self.resize = resize
         self.input_key = input_key
         self.regularization_weights = dict(regularization_weights or {})     # e.g. {"kl_loss": 1e-6}; the reference's simple branch uses none
         self.global_step = 0
@@ -230,7 +243,9 @@ class AutoencodingEngine(nn.Module):
     @torch.no_grad()
     def loss_and_backward(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None):
         """forward + backward of  rec_loss(x, decode(regularize(encode(x)))) + sum_k w_k * reg_log[k]  into the parameters'
-        gradients.  Returns (loss, z, xrec, reg_log); xrec fp32 NCHW.  `noise` may be injected (parity tests)."""
+        gradients.  Returns (loss, z, xrec, reg_log); xrec fp32 NCHW, the decoder's own output.  `noise` may be injected (parity tests).
+        When the decoder's output has another size than x, `self.resize` says which of the two the loss resamples (_resized); with equal
+        sizes nothing of that runs."""
         B, C, H, W = x.shape
         x = x.float().contiguous()
         cpad = (C + 7) // 8 * 8
@@ -240,12 +255,19 @@ class AutoencodingEngine(nn.Module):
         z, reg_log, b_reg = self.regularization.regularize(moments, noise)
         zc = z.shape[1]
         out_img, b_dec = self.decoder.fwdb(Img(ops.nchw_to_tokens(z.contiguous(), (zc + 7) // 8 * 8), B, z.shape[2], z.shape[3]))
-        xrec = ops.tokens_to_nchw(out_img.t, B, C, out_img.H, out_img.W, dtype=torch.float32)
+        xrec_out = xrec = ops.tokens_to_nchw(out_img.t, B, C, out_img.H, out_img.W, dtype=torch.float32)
         dev = x.device
+        # the images the loss terms see: x, xrec and the reconstruction's tokens as they are when the sizes agree; otherwise the resized input,
+        # or the resized reconstruction with `pull`, which takes a token gradient w.r.t. it back to the decoder's output resolution
+        x, xrec, out_img, pull = self._loss_view(x, xrec, out_img)
+        H, W = x.shape[2:]
         adversarial = self.discriminator is not None or self.perceptual_loss is not None
         log = {}
-        if adversarial:
-            loss, d_out, log = self._generator_loss(x, xrec, out_img, b_dec)
+        if self.perceptual_only:
+            loss, d_out, log = self._perceptual_loss(x, xrec, out_img)
+        elif adversarial:
+            loss, d_out, log = self._generator_loss(x, xrec, out_img, b_dec, pull)
+            pull = None                                   # (already at the decoder's resolution: the adaptive weight needed it there)
         elif self.rec_loss_type == "l2":
             # mean((xrec - x)^2) over everything = sum_b (1/B) * mean_chw: the edm loss kernel with c_out = 1, c_skip = 0, w = 1/B
             one, zero = torch.ones(B, device=dev), torch.zeros(B, device=dev)
@@ -262,13 +284,66 @@ class AutoencodingEngine(nn.Module):
         for key, w in self.regularization_weights.items():
             loss = loss + w * reg_log[key]
         reg_log = {**reg_log, **log}
+        if pull is not None:
+            d_out = pull(d_out)
         dz = ops.tokens_to_nchw(b_dec(d_out), B, zc, z.shape[2], z.shape[3], dtype=torch.float32)
         d_moments = b_reg(dz, float(self.regularization_weights.get(getattr(self.regularization, "loss_key", "kl_loss"), 0.0)))
         b_enc(ops.nchw_to_tokens(d_moments.contiguous(), moments_img.C))
         ops.join_wgrad_stream()
-        return loss, z, xrec, reg_log
+        return loss, z, xrec_out, reg_log
 
-    def _generator_loss(self, x: torch.Tensor, xrec: torch.Tensor, out_img: Img, b_dec):
+    def _resized(self, x: torch.Tensor, xrec: torch.Tensor):
+        """(x, xrec, backward of the reconstruction's resize or None) at one common size, by `self.resize`"""
+        if x.shape[2:] == xrec.shape[2:]:
+            return x, xrec, None
+        if self.resize is None:
+            raise ValueError(f"the decoder's output is {tuple(xrec.shape[2:])} and the input {tuple(x.shape[2:])}: the loss needs resize='input' (resize_input / "
+                             "scale_input_to_tgt_size of the loss classes: the input is resampled to the reconstruction's size) or resize='target' "
+                             "(resize_target: the reconstruction is resampled to the input's size)")
+        if self.resize == "input":
+            return ops.resize_bicubic_aa(x, tuple(xrec.shape[2:]))[0], xrec, None          # no gradient flows to the input
+        xrec_t, b_resize = ops.resize_bicubic_aa(xrec, tuple(x.shape[2:]))
+        return x, xrec_t, b_resize
+
+    def _loss_view(self, x: torch.Tensor, xrec: torch.Tensor, out_img: Img):
+        x, xrec_t, b_resize = self._resized(x, xrec)
+        if b_resize is None:
+            return x, xrec_t, out_img, None
+        B, C, H, W = xrec_t.shape
+        cpad = out_img.C
+
+        def pull(d_tokens: torch.Tensor) -> torch.Tensor:
+            return ops.nchw_to_tokens(b_resize(ops.tokens_to_nchw(d_tokens, B, C, H, W, dtype=torch.float32)), cpad)
+
+        return x, xrec_t, Img(ops.nchw_to_tokens(xrec_t, cpad), B, H, W), pull
+
+    def _perceptual_loss(self, x: torch.Tensor, xrec: torch.Tensor, out_img: Img):
+        """AutoencoderPerceptual (vae_lpips_discr.py:97-137):  loss = mean_b(recon_weight * rec_b + perceptual_weight * relu(LPIPS_b)),  rec_b the
+        per-sample mean of |x - xrec| or (x - xrec)^2, both images clamped to [-1, 1]; no gradient where xrec was clamped.  (The reference
+        adds a [B] to a [B, 1, 1, 1] tensor, which backpropagates only at B = 1, where it is this formula.)
+        Returns (loss, d loss / d reconstruction tokens, log); every log entry is a device scalar."""
+        B, C, H, W = x.shape
+        inside = (xrec >= -1.0) & (xrec <= 1.0)
+        xc, rc = x.clamp(-1.0, 1.0), xrec.clamp(-1.0, 1.0)
+        diff = rc - xc
+        rec = diff * diff if self.rec_loss_type == "l2" else diff.abs()
+        rec_term = self.rec_weight * rec.mean(dim=(1, 2, 3))                                 # [B]
+        d_rec = (2.0 * diff if self.rec_loss_type == "l2" else torch.sign(diff)) * (self.rec_weight / (B * C * H * W))
+        p_term = torch.zeros(B, device=x.device)
+        lpips = self.loss.perceptual_loss
+        if self.perceptual_weight > 0:
+            if lpips is None:
+                raise RuntimeError("AutoencoderPerceptual(delay_setup=True): call configure_model() on the loss before the first training step")
+            p_loss, b_lpips = lpips.fwdb(xc, Img(ops.nchw_to_tokens(rc, out_img.C), B, H, W))
+            p_term = self.perceptual_weight * torch.relu(p_loss)
+            d_p = ops.tokens_to_nchw(b_lpips(((p_loss > 0) * (self.perceptual_weight / B)).contiguous()), B, C, H, W, dtype=torch.float32)
+            d_rec = d_rec + d_p
+        total = rec_term + p_term
+        loss = total.mean()
+        log = {"loss/total": loss.detach(), "loss/rec": rec_term.mean(), "loss/p": p_term.mean()}
+        return loss, ops.nchw_to_tokens((d_rec * inside).contiguous(), out_img.C), log
+
+    def _generator_loss(self, x: torch.Tensor, xrec: torch.Tensor, out_img: Img, b_dec, pull=None):
         """The autoencoder's side of the adversarial loss with perceptual_weight = 0:
             nll   = sum(rec_weight * rec(x, xrec) / exp(logvar) + logvar) / B                  (get_nll_loss, :219-233)
             g     = -mean(D(xrec))                                                             (:268-270)
@@ -279,6 +354,9 @@ class AutoencodingEngine(nn.Module):
         The reference's forward for this branch does not run as written (it evaluates `weights > 0` with weights = None, and
         sums the un-reduced p_rec_loss tensor into a loss that is then passed to backward()); this is the formula its terms
         spell out -- the one of the taming-transformers / generative-models loss it was reworked from.
+        `x`, `xrec` and `out_img` are the images the terms see (_loss_view); with a resized reconstruction `pull` takes each token gradient
+        back to the decoder's output resolution, which is where the last layer's gradient norms and the returned gradient live (the adjoint
+        is linear: the sum of the two pulled gradients is the pulled sum, so the total passes through it once).
         Returns (loss, d loss / d decoder-output tokens, log)."""
         B, C, H, W = x.shape
         diff = xrec - x
@@ -306,6 +384,8 @@ class AutoencodingEngine(nn.Module):
             flat.copy_(g.reshape(flat.shape)) if not ops.state_of(self.logvar).grad_accumulate else flat.add_(g.reshape(flat.shape))
         active = self.discriminator is not None and self.global_step >= self.disc_start
         log["nll_loss"] = nll.detach()
+        if pull is not None:
+            d_nll_tok = pull(d_nll_tok)
         if not active:
             log.update(g_loss=torch.zeros((), device=x.device), d_weight=torch.zeros((), device=x.device))
             return nll, d_nll_tok, log
@@ -315,6 +395,8 @@ class AutoencodingEngine(nn.Module):
         d_logits = torch.full_like(vals, -1.0 / vals.numel())
         d_g_tok = b_disc(ops.nchw_to_tokens(d_logits, logits.C))       # also writes the discriminator's weight gradients: unused here,
         ops.join_wgrad_stream()                                          # overwritten by its own step
+        if pull is not None:
+            d_g_tok = pull(d_g_tok)
         d_weight = (b_dec.last_layer_grad_norm(d_nll_tok) / (b_dec.last_layer_grad_norm(d_g_tok) + 1e-4)).clamp(0.0, 1e4) * self.discriminator_weight
         factor = d_weight * self.disc_factor
         log.update(g_loss=g_loss.detach(), d_weight=d_weight.detach())
@@ -327,6 +409,8 @@ class AutoencodingEngine(nn.Module):
         B, C, H, W = x.shape
         x = x.float().contiguous()
         _, xrec, _ = self._reconstruct(x, noise)
+        x, xrec, _ = self._resized(x, xrec)          # (the reconstruction is detached here: no backward through the resize)
+        H, W = x.shape[2:]
         cpad = (C + 7) // 8 * 8
         lr_img, b_real = self.discriminator.fwdb(Img(ops.nchw_to_tokens(x, cpad), B, H, W), need_dx=False)
         lf_img, b_fake = self.discriminator.fwdb(Img(ops.nchw_to_tokens(xrec.contiguous(), cpad), B, H, W), need_dx=False)

@@ -4,6 +4,7 @@ SDXL one does.
 
     GeneralLPIPSWithDiscriminator   /root/reference/src/neurosis/modules/autoencoding/losses/discriminator_loss.py:22-88
     AutoencoderLPIPSWithDiscr       /root/reference/src/neurosis/modules/autoencoding/losses/vae_lpips_discr.py:140-200
+    AutoencoderPerceptual           the same file, :25-137
 
 In the reference these modules own the LPIPS network, the PatchGAN discriminator and the output log-variance, and their `forward`
 assembles the loss from torch ops under autograd.  Here they OWN THE SAME SUBMODULES UNDER THE SAME NAMES (so `loss.*` checkpoint
@@ -14,11 +15,17 @@ reconstruction term, the adaptive generator weight from two last-layer weight-gr
 losses with explicit logit gradients, alternating optimizers from `disc_start` on.  Calling the object directly raises: there is
 no autograd graph through the HIP decoder for a stand-alone loss call to differentiate.
 
-Options outside the SD / SDXL autoencoder recipes are refused loudly at construction (3-D inputs, input rescaling, R1
-penalty, non-LPIPS perceptual types) rather than accepted and ignored.
+The resize options (`resize_input` / `resize_target`, `scale_input_to_tgt_size`) cover an autoencoder whose decoder output has another
+size than its input: the engine resamples the input to the reconstruction's size, or the reconstruction to the input's, with the antialiased
+bicubic resize of `ops.resize_bicubic_aa` (the reference's F.interpolate(mode="bicubic", antialias=True)) and, for the reconstruction, its
+explicit adjoint.
+
+Options outside the SD / SDXL autoencoder recipes are refused loudly at construction (3-D inputs, R1 penalty, non-LPIPS perceptual
+types) rather than accepted and ignored.
 """
 from __future__ import annotations
 
+import logging
 from sys import maxsize
 from typing import Any, Iterator, Optional, Union
 
@@ -27,7 +34,16 @@ from torch import nn
 
 from ...losses import LPIPS, NLayerDiscriminator, get_discr_loss_fn, weights_init
 
-__all__ = ["AutoencoderLPIPSWithDiscr", "GeneralLPIPSWithDiscriminator"]
+__all__ = ["AutoencoderLPIPSWithDiscr", "AutoencoderPerceptual", "GeneralLPIPSWithDiscriminator"]
+
+logger = logging.getLogger(__name__)
+
+
+def _resize_mode(resize_input: bool, resize_target: bool) -> Optional[str]:
+    """the engine's `resize`: "input" (the input is resampled to the reconstruction's size), "target" (the reconstruction to the input's)"""
+    if resize_input and resize_target:
+        raise ValueError("Only one of resize_input and resize_target can be True")
+    return "input" if resize_input else "target" if resize_target else None
 
 
 def _rec_type(kind) -> str:
@@ -50,9 +66,10 @@ class _FusedLossConfig(nn.Module):
     discriminator_weight: float
     disc_loss_name: str
     learn_logvar: bool
+    resize: Optional[str] = None
 
     def engine_settings(self) -> dict:
-        return dict(rec_loss_type=self.rec_loss_type, rec_weight=self.rec_weight, perceptual_loss=self.perceptual_loss,
+        return dict(resize=self.resize, rec_loss_type=self.rec_loss_type, rec_weight=self.rec_weight, perceptual_loss=self.perceptual_loss,
                     perceptual_weight=self.perceptual_weight, discriminator=self._discriminator_module(), disc_loss=self.disc_loss_name,
                     disc_start=self.disc_start, disc_factor=self.disc_factor, disc_weight=self.discriminator_weight,
                     logvar=self._logvar_parameter(), learn_logvar=self.learn_logvar, regularization_weights=dict(getattr(self, "regularization_weights", {}) or {}))
@@ -79,11 +96,11 @@ class GeneralLPIPSWithDiscriminator(_FusedLossConfig):
         super().__init__()
         if dims != 2:
             raise NotImplementedError("dims > 2 (video autoencoders) is outside the SD / SDXL path")
-        if scale_input_to_tgt_size:
-            raise NotImplementedError("scale_input_to_tgt_size is not built")
         if disc_loss not in ("hinge", "vanilla"):
             raise ValueError(f"disc_loss must be one of ['hinge', 'vanilla'], got {disc_loss}")
         self.dims, self.scale_input_to_tgt_size = dims, scale_input_to_tgt_size
+        # discriminator_loss.py:240-241 resamples the INPUT to the reconstruction's size: the same as resize_input of the classes below
+        self.resize = _resize_mode(bool(scale_input_to_tgt_size), False)
         # `lpips_kwargs` is this package's addition: the reference constructs LPIPS() with its packaged weights; here the calibrated lin
         # weights are named explicitly (modules/losses/perceptual.py) or pretrained=False is passed for synthetic runs
         self.perceptual_loss = LPIPS(**(lpips_kwargs or {})).eval() if perceptual_weight > 0 else None
@@ -134,8 +151,7 @@ class AutoencoderLPIPSWithDiscr(_FusedLossConfig):
         self.recon_weight = self.rec_weight = float(recon_weight)
         if str(getattr(perceptual_type, "value", perceptual_type)).lower() != "lpips":
             raise NotImplementedError(f"Perceptual loss {perceptual_type} not implemented")
-        if resize_input or resize_target:
-            raise NotImplementedError("resize_input / resize_target are not built")
+        self.resize = _resize_mode(resize_input, resize_target)
         if disc_lambda_r1:
             raise NotImplementedError("the R1 gradient penalty (disc_lambda_r1) needs a double backward through the discriminator: not built")
         self.perceptual_loss = LPIPS(**(lpips_kwargs or {})).eval() if perceptual_weight > 0 else None
@@ -161,3 +177,58 @@ class AutoencoderLPIPSWithDiscr(_FusedLossConfig):
 
     def _discriminator_module(self) -> nn.Module:
         return self.discr
+
+
+class AutoencoderPerceptual(_FusedLossConfig):
+    """vae_lpips_discr.py:25-137: l1 / l2 reconstruction + LPIPS, no discriminator and no second optimizer.  Passed as `loss=` it makes the
+    engine compute, per step,
+
+        loss = mean_b( recon_weight * rec_b + perceptual_weight * relu(LPIPS_b) )
+
+    rec_b the per-sample mean of |x - xrec| (l1) or (x - xrec)^2 (l2), both images clamped to [-1, 1] first (after the resize, if one is
+    configured); the gradient is zero where xrec was clamped.  As written the reference's forward returns the sum of a [B] and a [B, 1, 1, 1]
+    tensor, a [B, 1, 1, B] tensor that backward() only takes at B = 1; this is the formula its terms spell out, and it coincides with the
+    reference at B = 1.  The log carries `{split}/loss/total`, `/rec` and `/p` as device scalars; the three `*_ema` keys cost the reference
+    an `.item()` (a host sync) per step and are not produced (`loss_ema_steps` is kept for the config's sake)."""
+
+    def __init__(self, perceptual_type="lpips", perceptual_weight: float = 1.0, lpips_type: str = "alex", recon_type="l1", recon_weight: float = 1.0,
+                 resize_input: bool = False, resize_target: bool = False, loss_ema_steps: int = 64, extra_log_keys: list[str] = [],
+                 delay_setup: bool = False, compile: bool = False, lpips_kwargs: Optional[dict] = None):
+        super().__init__()
+        self.recon_type = recon_type
+        self.rec_loss_type = _rec_type(recon_type)
+        self.recon_weight = self.rec_weight = float(recon_weight)
+        self.resize = _resize_mode(resize_input, resize_target)
+        self.resize_input_to_target, self.resize_target_to_input = resize_input, resize_target
+        self.perceptual_type = str(getattr(perceptual_type, "value", perceptual_type)).lower()
+        if self.perceptual_type != "lpips":
+            raise NotImplementedError(f"Perceptual loss {perceptual_type} not implemented")
+        self._lpips_type = lpips_type
+        self._lpips_kwargs = dict(lpips_kwargs or {})
+        self.perceptual_loss: Optional[LPIPS] = None
+        self.perceptual_weight = float(perceptual_weight)
+        self.loss_ema_steps = int(loss_ema_steps)
+        self.forward_keys = ["split"]
+        self.extra_log_keys = set(extra_log_keys)
+        self._compile = compile
+        if compile:
+            logger.info("AutoencoderPerceptual(compile=True): ignored, the LPIPS trunk runs on this package's HIP kernels, not through TorchInductor")
+        # no discriminator: the settings the adversarial classes share are fixed
+        self.disc_start, self.disc_factor, self.discriminator_weight, self.disc_loss_name, self.learn_logvar = maxsize, 0.0, 0.0, "hinge", False
+        if delay_setup:
+            logger.info("Delaying LPIPS model loading until configure_model() call")
+        else:
+            self.configure_model()
+
+    def configure_model(self) -> None:
+        if self.perceptual_loss is None:
+            self.perceptual_loss = LPIPS(**{"pnet_type": self._lpips_type, **self._lpips_kwargs}).eval()      # (lpips_kwargs may name the trunk too; it wins)
+
+    def get_trainable_parameters(self) -> Iterator[nn.Parameter]:
+        yield from ()
+
+    def _discriminator_module(self) -> Optional[nn.Module]:
+        return None
+
+    def engine_settings(self) -> dict:
+        return {**super().engine_settings(), "perceptual_only": True}

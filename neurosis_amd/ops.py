@@ -1492,6 +1492,67 @@ def vq_quantize(idx: Tensor, codebook: Tensor, z: Tensor, hw: int = 1, out: Opti
 
 
 # ------------------------------------------------------------------------------------------------
+# antialiased bicubic resize (csrc/resample.hip; host tables in neurosis_amd/resample.py)
+# ------------------------------------------------------------------------------------------------
+def _resize_planes(x: Tensor, out_hw, transposed: bool, op: str) -> Tensor:
+    """x fp32 NCHW -> [N, C, *out_hw] through nk_resample_planes: with the forward tables of (H, W) -> out_hw, or (transposed) with the
+    transposed tables of out_hw -> (H, W), i.e. the adjoint of the resize that produced something of x's size."""
+    from .resample import device_tables
+
+    if not x.is_cuda:
+        raise NotImplementedError(f"{op}: the input is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"{op}: expected an fp32 NCHW tensor, got {tuple(x.shape)} {x.dtype}")
+    N, Cc, H, W = x.shape
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    if OH < 1 or OW < 1 or H < 1 or W < 1:
+        raise ValueError(f"{op}: sizes must be positive, got {(H, W)} -> {(OH, OW)}")
+    x = x.contiguous()
+    if transposed:
+        v, h = device_tables(OH, H, x.device)[1], device_tables(OW, W, x.device)[1]
+    else:
+        v, h = device_tables(H, OH, x.device)[0], device_tables(W, OW, x.device)[0]
+    y = torch.empty(N, Cc, OH, OW, dtype=torch.float32, device=x.device)
+    P = N * Cc
+    if P == 0:
+        return y
+    ws = _ws(max(query("nk_resample_ws_floats", P, H, W, OH, OW), 1), x.device)
+    call("nk_resample_planes", x.data_ptr(), y.data_ptr(), ws.data_ptr(), v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr(), v[3], h[0].data_ptr(),
+         h[1].data_ptr(), h[2].data_ptr(), h[3], P, H, W, OH, OW, _stream())
+    return y
+
+
+def resize_bicubic_aa(x: Tensor, size):
+    """(y, bwd): y = F.interpolate(x, size, mode="bicubic", antialias=True) for fp32 NCHW x, through the banded resampler with float64-built
+    tables; bwd(dy) -> dx is the same kernel with the transposed tables (deterministic, no atomics).  Equal sizes return x itself and an
+    identity bwd (torch's result is the bit-exact identity there)."""
+    if not x.is_cuda:
+        raise NotImplementedError("resize_bicubic_aa: the input is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"resize_bicubic_aa: expected an fp32 NCHW tensor, got {tuple(x.shape)} {x.dtype}")
+    OH, OW = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    N, Cc, H, W = x.shape
+    if (OH, OW) == (H, W):
+        return x, lambda dy: dy
+    y = _resize_planes(x, (OH, OW), False, "resize_bicubic_aa")
+
+    def bwd(dy: Tensor) -> Tensor:
+        if tuple(dy.shape) != (N, Cc, OH, OW):
+            raise ValueError(f"resize_bicubic_aa backward: expected a gradient of shape {(N, Cc, OH, OW)}, got {tuple(dy.shape)}")
+        return _resize_planes(dy, (H, W), True, "resize_bicubic_aa backward")
+
+    return y, bwd
+
+
+def resize_bicubic_aa_bwd(dy: Tensor, size) -> Tensor:
+    """dx [N, C, *size] = R^T dy for the resize R: size -> dy's height and width (the backward of resize_bicubic_aa without its forward)."""
+    IH, IW = int(size[0]), int(size[1])
+    if dy.is_cuda and dy.dim() == 4 and tuple(dy.shape[2:]) == (IH, IW):
+        return dy
+    return _resize_planes(dy, (IH, IW), True, "resize_bicubic_aa_bwd")
+
+
+# ------------------------------------------------------------------------------------------------
 # misc
 # ------------------------------------------------------------------------------------------------
 def timestep_embedding(t: Tensor, dim: int, max_period: float = 10000.0) -> Tensor:

@@ -952,7 +952,48 @@ def _vq_quantize_bwd(ctx, d_zq, d_loss):
 vq_quantize.register_autograd(_vq_quantize_bwd, setup_context=_vq_quantize_setup)
 
 
-OPS = ("vq_search", "vq_code_stats", "vq_quantize", "groupnorm_mod_fwd", "groupnorm_mod_bwd", "groupnorm_mod", "upsample2x_nearest", "avgpool2x", "avgpool2x_bwd", "dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_prepare_cat", "sample_prepare_cat", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
+# ---------------------------------------------------------------------------------------------------------------
+# antialiased bicubic resize (csrc/resample.hip): fp32 NCHW planes, forward and adjoint on one banded kernel
+# ---------------------------------------------------------------------------------------------------------------
+@_op("resize_bicubic_aa")
+def resize_bicubic_aa(x: Tensor, out_h: int, out_w: int) -> Tensor:
+    """F.interpolate(x, (out_h, out_w), mode="bicubic", antialias=True) for fp32 NCHW x; differentiable (its backward is resize_bicubic_aa_bwd)."""
+    y, _ = ops.resize_bicubic_aa(x, (out_h, out_w))
+    return y.clone() if y is x else y          # (an op may not return its input; equal sizes are the identity)
+
+
+@resize_bicubic_aa.register_fake
+def _(x, out_h, out_w):
+    return x.new_empty(x.shape[0], x.shape[1], out_h, out_w)
+
+
+@_op("resize_bicubic_aa_bwd")
+def resize_bicubic_aa_bwd(dy: Tensor, in_h: int, in_w: int) -> Tensor:
+    """dx [N, C, in_h, in_w] = R^T dy for the resize R from (in_h, in_w) to dy's size: the same kernel with the transposed tables."""
+    dx = ops.resize_bicubic_aa_bwd(dy, (in_h, in_w))
+    return dx.clone() if dx is dy else dx
+
+
+@resize_bicubic_aa_bwd.register_fake
+def _(dy, in_h, in_w):
+    return dy.new_empty(dy.shape[0], dy.shape[1], in_h, in_w)
+
+
+def _resize_setup(ctx, inputs, output):
+    ctx.in_hw = tuple(inputs[0].shape[2:])
+
+
+def _resize_bwd(ctx, dy):
+    return torch.ops.neurosis_hip.resize_bicubic_aa_bwd(dy.contiguous(), ctx.in_hw[0], ctx.in_hw[1]), None, None
+
+
+resize_bicubic_aa.register_autograd(_resize_bwd, setup_context=_resize_setup)
+# the adjoint is linear too: its backward is the forward resize
+resize_bicubic_aa_bwd.register_autograd(lambda ctx, dx: (torch.ops.neurosis_hip.resize_bicubic_aa(dx.contiguous(), ctx.out_hw[0], ctx.out_hw[1]), None, None),
+                                        setup_context=lambda ctx, inputs, output: setattr(ctx, "out_hw", tuple(inputs[0].shape[2:])))
+
+
+OPS = ("resize_bicubic_aa", "resize_bicubic_aa_bwd", "vq_search", "vq_code_stats", "vq_quantize", "groupnorm_mod_fwd", "groupnorm_mod_bwd", "groupnorm_mod", "upsample2x_nearest", "avgpool2x", "avgpool2x_bwd", "dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_prepare_cat", "sample_prepare_cat", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
        "flat_allreduce_start", "flat_allreduce_wait", "conv2d_fwd_stats", "linear_dgrad_geglu", "linear_fwd_geglu", "linear_fwd", "linear_dgrad", "linear_wgrad", "colsum", "linear", "layernorm_fwd", "layernorm_bwd", "layernorm", "groupnorm_silu_fwd",
        "groupnorm_silu_bwd", "groupnorm_silu", "geglu_fwd", "geglu_bwd", "geglu", "attention_fwd", "attention_bwd", "attention", "conv2d_fwd",
        "conv2d_dgrad", "conv2d_wgrad", "conv2d", "timestep_embedding", "nchw_to_nlc", "nlc_to_nchw")
