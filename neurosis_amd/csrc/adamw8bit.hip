@@ -181,7 +181,6 @@ extern "C" int nk_adamw8bit_step(const NkAdamW8bitArgs* h, void* stream_) {
   NK_CHECK_ARG(h && h->master && h->grad && h->shadow && h->code1 && h->code2 && h->absmax1 && h->absmax2);
   NK_CHECK_ARG(h->m32 && h->v32 && h->qmap1 && h->qmap2 && h->tensors && h->blk_start);
   NK_CHECK_ARG(h->ntensors > 0 && h->nblocks >= h->ntensors);
-  if (int e = nk_health_poll()) return e;       // an EARLIER step's backward was flagged: refuse to go on silently
   hipStream_t stream = (hipStream_t)stream_;
   NkA8Args a;
   a.master = h->master; a.grad = h->grad; a.shadow = (bf16_t*)h->shadow;
@@ -190,11 +189,8 @@ extern "C" int nk_adamw8bit_step(const NkAdamW8bitArgs* h, void* stream_) {
   a.ntensors = h->ntensors; a.nblocks = h->nblocks;
   a.beta1 = h->beta1; a.beta2 = h->beta2; a.omb1 = h->one_minus_beta1; a.omb2 = h->one_minus_beta2; a.eps = h->eps; a.lr = h->lr;
   a.decay = h->decay; a.bc1 = h->bc1; a.bc2 = h->bc2; a.grad_scale = h->grad_scale;
-  a.health = nk_health_word();
-  if (!a.health) { nk_set_error(__FILE__, __LINE__, "health word allocation failed"); return NK_ERR_LAUNCH; }
+  if (int e = nk_opt_begin(true, &a.health)) return e;      // (one launch per step: every call is the step's first chunk)
   const int per_wg = A8_WAVES * A8_BPW;
-  hipLaunchKernelGGL(adamw8bit_kernel, dim3((a.nblocks + per_wg - 1) / per_wg), dim3(256), 0, stream, a);
-  if (int e = nk_check_launch("adamw8bit_kernel")) return e;
-  nk_health_snapshot(stream);                    // what the backward in front of this update left in the word
-  return NK_OK;
+  NK_OPT_LAUNCH(adamw8bit_kernel, (a.nblocks + per_wg - 1) / per_wg, stream, a);
+  return nk_opt_end(stream);
 }

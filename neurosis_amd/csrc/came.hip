@@ -18,6 +18,12 @@
 // Adafactor's 22 and AdamW's 30.  State: m (full size) and the four factored vectors, or m and v for a vector (4 B/param + a little,
 // against AdamW's 8).  Every reduction goes through per-tile partials combined in a fixed order: no atomics on values, bitwise
 // reproducible step to step.  Every kernel returns at once while the backward-health word is raised.
+//
+// The tile geometry, the strip finish, pass B and the mean slots are optim_common.h's, shared with Adafactor.  The row loop of
+// cm_matrix_stats and the conv / vector passes are NOT written on the shared loops, deliberately: both statistics kernels sit at the edge of
+// what the compiler pairs into packed operations, and on the shared loops (same bits) CAME's update of 2.57 G parameters went from 19.77 to
+// 20.14 ms: matrices +1.4 %, 3x3 convs +1.2 %; with only the KH/KW ladder shared the 3x3 convs still ran +2 %, with the pair EMA / factor
+// helpers shared the 1x1 convs +5 % (profiles/optim_refactor_ab.txt).
 #include "../../include/neurosis_hip.h"
 #include "nk_common.h"
 #include "optim_common.h"
@@ -63,28 +69,17 @@ __device__ __forceinline__ void cm_tensor_denom(const NkCmArgs& a, const NkCameT
   }
 }
 
-__device__ __forceinline__ float cm_mean_slots(const NkCmArgs& a, const NkCameTensor& t, int base) {
-  float s = 0.f;
-  const int n = (t.d0 + AF_TR - 1) / AF_TR;
-  for (int i = 0; i < n; ++i) s += a.mean_row[t.mr0 + base + i];
-  return s / (float)t.d0;
-}
-
 // ---- matrices: the two row / column statistics passes (A: q = g^2 + eps1 -> R, C;  C1: m update, res -> Rr, Cr) -------------------------
 template <bool RES>
 __device__ __forceinline__ void cm_matrix_stats(const NkCmArgs& a, const NkAfItem& it, const NkCameTensor& t, int tid) {
-  __shared__ float red[4];
-  __shared__ float colsh[16][AF_TC + 4];
-  __shared__ float rowsh[AF_TR];
-  __shared__ unsigned flag[2];
-  const int ry = tid >> 4, cx = tid & 15;
-  const int col = it.tc * AF_TC + cx * 4;
-  const bool cok = col < t.d1;
-  const int ntc = (t.d1 + AF_TC - 1) / AF_TC, ntr = (t.d0 + AF_TR - 1) / AF_TR;
+  __shared__ FacStatsLds L;
+  const FacTile T(it, t.d0, t.d1, tid);
+  const int ry = T.ry, cx = T.cx, col = T.col;
+  const bool cok = T.cok;
   const float gs = a.grad_scale;
   float ci[4] = {0.f, 0.f, 0.f, 0.f}, mr = 1.f, den = 1.f;
   if (RES) {
-    mr = cm_mean_slots(a, t, 0);
+    mr = fac_mean_slots(a.mean_row, t.mr0, t.d0);
     if (cok) {
       const float4_t c4 = *(const float4_t*)(a.state + t.c_off + col);
 #pragma unroll
@@ -133,51 +128,12 @@ __device__ __forceinline__ void cm_matrix_stats(const NkCmArgs& a, const NkAfIte
       if (RES && ok) *(float4_t*)(a.state + t.m_off + (long)r * t.d1 + col) = mn;
       // sum over the 16 column lanes of this row (lanes cx = 0..15 are adjacent within the wave)
       rs += __shfl_xor(rs, 8); rs += __shfl_xor(rs, 4); rs += __shfl_xor(rs, 2); rs += __shfl_xor(rs, 1);
-      if (cx == 0) rowsh[ry + 16 * (i0 + u)] = rs;
+      if (cx == 0) L.rowsh[ry + 16 * (i0 + u)] = rs;
     }
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) colsh[ry][cx * 4 + e] = cs[e];
-  __syncthreads();
-  float* rowpart = a.ws + t.ws_row + (long)it.tc * t.d0;
-  if (it.tr * AF_TR + tid < t.d0) AF_PUBLISH(rowpart + it.tr * AF_TR + tid, rowsh[tid]);
-  if (tid < AF_TC) {
-    const int c = it.tc * AF_TC + tid;
-    if (c < t.d1) {
-      float s = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s += colsh[r][tid];
-      AF_PUBLISH(a.ws + t.ws_col + (long)it.tr * t.d1 + c, s);
-    }
-  }
-  const float beta = RES ? a.beta3 : a.beta2, omb = RES ? a.omb3 : a.omb2;
-  const long row_off = RES ? t.rr_off : t.r_off, col_off = RES ? t.cr_off : t.c_off;
-  // the last tile of this 256-row strip: the strip's row EMAs and their sum (the row mean = sum of the slots / d0)
-  if (af_last_block(a.counters + t.cnt0 + 1 + it.tr, (unsigned)ntc, tid, &flag[0])) {
-    const int r = it.tr * AF_TR + tid;
-    float v = 0.f;
-    if (r < t.d0) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int c = 0; c < ntc; ++c) s += AF_FETCH(a.ws + t.ws_row + (long)c * t.d0 + r);
-      float* st = a.state + row_off + r;
-      v = *st * beta + (s / (float)t.d1) * omb;
-      *st = v;
-    }
-    v = block_sum_256(v, red);
-    if (tid == 0) a.mean_row[t.mr0 + (RES ? ntr : 0) + it.tr] = v;
-  }
-  // ... and of this 64-column strip: its column EMAs
-  if (af_last_block(a.counters + t.cnt0 + 1 + ntr + it.tc, (unsigned)ntr, tid, &flag[1])) {
-    const int c = it.tc * AF_TC + tid;
-    if (tid < AF_TC && c < t.d1) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int r = 0; r < ntr; ++r) s += AF_FETCH(a.ws + t.ws_col + (long)r * t.d1 + c);
-      float* st = a.state + col_off + c;
-      *st = *st * beta + (s / (float)t.d0) * omb;
-    }
-  }
+  const int ntr = (t.d0 + AF_TR - 1) / AF_TR;
+  fac_strip_finish(a, t, it, T, L, cs, tid, RES ? a.beta3 : a.beta2, RES ? a.omb3 : a.omb2, RES ? t.rr_off : t.r_off, RES ? t.cr_off : t.c_off,
+                   t.mr0 + (RES ? ntr : 0));
 }
 
 // ---- conv weights: one thread per (o, i) pair; all of that pair's KH x KW taps and factored statistics stay in registers ---------------
@@ -348,46 +304,10 @@ __global__ __launch_bounds__(256) void came_stats_kernel(const NkCmArgs a) {
 // ---- pass B (matrices): partial sums of u^2, the clip denominator ------------------------------------------------------------------
 __global__ __launch_bounds__(256) void came_u2_kernel(const NkCmArgs a) {
   AF_HEALTH_GATE(a);
-  __shared__ float red[4];
-  __shared__ unsigned flag;
   const NkAfItem it = a.items[a.item_lo + blockIdx.x];
   const NkCameTensor t = a.tensors[it.tensor];
   if (t.kind != 1) return;
-  const int tid = threadIdx.x;
-  const int ry = tid >> 4, cx = tid & 15;
-  const int col = it.tc * AF_TC + cx * 4;
-  const bool cok = col < t.d1;
-  const float mr = cm_mean_slots(a, t, 0);
-  const float gs = a.grad_scale;
-  float ci[4] = {0.f, 0.f, 0.f, 0.f};
-  if (cok) {
-    const float4_t c4 = *(const float4_t*)(a.state + t.c_off + col);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ci[e] = rsqrtf(c4[e]);
-  }
-  float acc = 0.f;
-#pragma unroll 1
-  for (int i0 = 0; i0 < AF_TR / 16; i0 += 4) {
-    float4_t g[4];
-    float rf[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r = it.tr * AF_TR + ry + 16 * (i0 + u);
-      const bool ok = cok && r < t.d0;
-      g[u] = ok ? *(const float4_t*)(a.grad + t.off + (long)r * t.d1 + col) : (float4_t){0.f, 0.f, 0.f, 0.f};
-      rf[u] = ok ? rsqrtf(a.state[t.r_off + r] / mr) : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float uu = rf[u] * ci[e] * (g[u][e] * gs);
-        acc += uu * uu;
-      }
-  }
-  acc = block_sum_256(acc, red);
-  if (tid == 0) AF_PUBLISH(a.u2_part + a.item_lo + blockIdx.x, acc);
-  if (af_last_block(a.counters + t.cnt0, (unsigned)t.nitems, tid, &flag)) cm_tensor_denom(a, t, it.tensor, tid, red);
+  fac_matrix_u2(a, t, it, t.r_off, t.c_off, [&](int tid, float* red) { cm_tensor_denom(a, t, it.tensor, tid, red); });
 }
 
 // ---- pass C1: first moment; matrices: residual statistics; conv weights and vectors: the whole rest of the update ----------------------
@@ -427,41 +347,32 @@ __global__ __launch_bounds__(256) void came_apply_kernel(const NkCmArgs a) {
   const NkAfItem it = a.items[a.item_lo + blockIdx.x];
   const NkCameTensor t = a.tensors[it.tensor];
   if (t.kind != 1) return;
-  const int tid = threadIdx.x;
-  const int ry = tid >> 4, cx = tid & 15;
-  const int col = it.tc * AF_TC + cx * 4;
-  if (col >= t.d1) return;                          // (no block-wide synchronisation below)
-  const float mr = cm_mean_slots(a, t, (t.d0 + AF_TR - 1) / AF_TR);
+  const FacTile T(it, t.d0, t.d1, threadIdx.x);
+  if (!T.cok) return;                               // (no block-wide synchronisation below)
+  const float mr = fac_mean_slots(a.mean_row, t.mr0 + (t.d0 + AF_TR - 1) / AF_TR, t.d0);
   float ci[4];
-  const float4_t c4 = *(const float4_t*)(a.state + t.cr_off + col);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ci[e] = rsqrtf(c4[e]);
+  T.col_factors(a.state + t.cr_off, ci);
 #pragma unroll 1
   for (int i0 = 0; i0 < AF_TR / 16; i0 += 4) {
     float4_t m[4], p[4];
     float rf[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const int r = it.tr * AF_TR + ry + 16 * (i0 + u);
-      const bool ok = r < t.d0;
-      const long o = (long)r * t.d1 + col;
-      m[u] = ok ? *(const float4_t*)(a.state + t.m_off + o) : (float4_t){0.f, 0.f, 0.f, 0.f};
-      p[u] = ok ? *(const float4_t*)(a.master + t.off + o) : (float4_t){0.f, 0.f, 0.f, 0.f};
+      const int r = T.row(i0 + u);
+      const bool ok = T.ok(r);
+      const long o = T.at(r);
+      m[u] = T.load(ok, a.state + t.m_off + o);
+      p[u] = T.load(ok, a.master + t.off + o);
       rf[u] = ok ? rsqrtf(a.state[t.rr_off + r] / mr) : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const int r = it.tr * AF_TR + ry + 16 * (i0 + u);
-      if (r >= t.d0) continue;
-      const long o = t.off + (long)r * t.d1 + col;
+      const int r = T.row(i0 + u);
+      if (!T.ok(r)) continue;
       float4_t pn;
 #pragma unroll
       for (int e = 0; e < 4; ++e) pn[e] = p[u][e] * a.decay - (rf[u] * ci[e] * m[u][e]) * a.lr;
-      *(float4_t*)(a.master + o) = pn;
-      uint2_t sh;
-      sh.x = pack2bf(pn[0], pn[1]);
-      sh.y = pack2bf(pn[2], pn[3]);
-      *(uint2_t*)(a.shadow + o) = sh;
+      T.store(a.master, a.shadow, t.off, r, pn);
     }
   }
 }
@@ -477,8 +388,6 @@ extern "C" long nk_came_tensor_bytes(void) { return (long)sizeof(NkCameTensor); 
 
 extern "C" int nk_came_chunk(const NkCameArgs* h, void* stream_) {
   if (int e = cm_check(h)) return e;
-  if (h->tensor_lo == 0)                        // first chunk of a step: an EARLIER step's backward was flagged -> refuse to go on silently
-    if (int e = nk_health_poll()) return e;
   hipStream_t stream = (hipStream_t)stream_;
   NkCmArgs a;
   a.master = h->master; a.grad = h->grad; a.shadow = (bf16_t*)h->shadow; a.state = h->state; a.ws = h->ws;
@@ -488,21 +397,11 @@ extern "C" int nk_came_chunk(const NkCameArgs* h, void* stream_) {
   a.beta1 = h->beta1; a.beta2 = h->beta2; a.beta3 = h->beta3;
   a.omb1 = h->one_minus_beta1; a.omb2 = h->one_minus_beta2; a.omb3 = h->one_minus_beta3; a.eps1 = h->eps1; a.eps2 = h->eps2; a.clip = h->clip_threshold;
   a.lr = h->lr; a.decay = h->decay; a.grad_scale = h->grad_scale;
-  a.health = nk_health_word();
-  if (!a.health) { nk_set_error(__FILE__, __LINE__, "health word allocation failed"); return NK_ERR_LAUNCH; }
-  const dim3 grid(a.item_hi - a.item_lo);
-  hipLaunchKernelGGL(came_stats_kernel, grid, dim3(256), 0, stream, a);
-  if (int e = nk_check_launch("came_stats_kernel")) return e;
-  if (h->has_matrix) {
-    hipLaunchKernelGGL(came_u2_kernel, grid, dim3(256), 0, stream, a);
-    if (int e = nk_check_launch("came_u2_kernel")) return e;
-  }
-  hipLaunchKernelGGL(came_moment_kernel, grid, dim3(256), 0, stream, a);
-  if (int e = nk_check_launch("came_moment_kernel")) return e;
-  if (h->has_matrix) {
-    hipLaunchKernelGGL(came_apply_kernel, grid, dim3(256), 0, stream, a);
-    if (int e = nk_check_launch("came_apply_kernel")) return e;
-  }
-  nk_health_snapshot(stream);                    // what the backward in front of this update left in the word
-  return NK_OK;
+  if (int e = nk_opt_begin(h->tensor_lo == 0, &a.health)) return e;
+  const int nitems = a.item_hi - a.item_lo;
+  NK_OPT_LAUNCH(came_stats_kernel, nitems, stream, a);
+  if (h->has_matrix) NK_OPT_LAUNCH(came_u2_kernel, nitems, stream, a);
+  NK_OPT_LAUNCH(came_moment_kernel, nitems, stream, a);
+  if (h->has_matrix) NK_OPT_LAUNCH(came_apply_kernel, nitems, stream, a);
+  return nk_opt_end(stream);
 }

@@ -62,6 +62,41 @@ def test_flat_adafactor_matches_reference_steps(tag, streams, monkeypatch):
         assert rel_err(p.detach().cpu(), want) <= 2e-5
 
 
+def _adafactor_run(c, steps, scale=1.0, grad_scale=1.0):
+    """master, shadow and state after `steps` steps of the golden case `c` in 8 KiB chunks (the fixture has three steps of gradients: a
+    fourth step takes the first's again)"""
+    from neurosis_amd.optim import FlatAdafactor
+
+    store, params = make_store(c["init"])
+    opt = FlatAdafactor(store, chunk_bytes=8 << 10, **c["kwargs"])
+    assert len(opt.chunks) > 2
+    for s in range(steps):
+        set_grads(params, c["grads"][s % len(c["grads"])], scale=scale)
+        opt.step(grad_scale=grad_scale)
+    torch.cuda.synchronize()
+    return store.master.clone(), store.shadow.clone(), opt.state.clone()
+
+
+@pytest.mark.parametrize("streams", ["1", "2"])
+@pytest.mark.parametrize("tag", ["relative", "manual"])
+def test_bitwise_deterministic(tag, streams, monkeypatch):
+    """Fixed-order partial sums, no atomics on values: two runs give the same bits."""
+    monkeypatch.setenv("NK_AF_STREAMS", streams)
+    c = load_fixture("adafactor_steps")[tag]
+    for a, b in zip(_adafactor_run(c, 4), _adafactor_run(c, 4)):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("streams", ["1", "2"])
+@pytest.mark.parametrize("tag", ["relative", "manual"])
+def test_grad_scale_is_exact(tag, streams, monkeypatch):
+    """grad_scale (the data-parallel mean): 4 g with grad_scale 0.25 is g, bit for bit."""
+    monkeypatch.setenv("NK_AF_STREAMS", streams)
+    c = load_fixture("adafactor_steps")[tag]
+    for a, b in zip(_adafactor_run(c, 4), _adafactor_run(c, 4, scale=4.0, grad_scale=0.25)):
+        assert torch.equal(a, b)
+
+
 def test_flat_adafactor_sdxl_like_shapes_vs_oracle():
     """Real channel counts (ragged tiles: 1280x2048 context projections, 320-channel convs, 4-channel conv_out, 2816 label
     input), five steps, against the CPU oracle."""
