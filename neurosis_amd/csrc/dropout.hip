@@ -80,13 +80,11 @@ __global__ void dropout_draw_kernel(unsigned long long* state, unsigned long lon
   }
 }
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 extern "C" int nk_dropout(const void* x, const void* residual, void* y, long rows, int cols, long ld_x, long ld_res, long ld_y, const void* token,
                           int site, int thr, float scale, void* stream) {
   NK_CHECK_ARG(x && y && token && rows > 0 && cols > 0 && (cols & 7) == 0);
-  NK_CHECK_ARG(ld_x >= cols && ld_y >= cols && (ld_x & 7) == 0 && (ld_y & 7) == 0 && aligned16(x) && aligned16(y));
-  NK_CHECK_ARG(!residual || (ld_res >= cols && (ld_res & 7) == 0 && aligned16(residual)));
+  NK_CHECK_ARG(ld_x >= cols && ld_y >= cols && (ld_x & 7) == 0 && (ld_y & 7) == 0 && nk_aligned16(x) && nk_aligned16(y));
+  NK_CHECK_ARG(!residual || (ld_res >= cols && (ld_res & 7) == 0 && nk_aligned16(residual)));
   NK_CHECK_ARG(((uintptr_t)token & 7) == 0 && site >= 0 && thr >= 0 && thr <= 65536);
   const int cpr = cols >> 3;
   const long total = rows * cpr;

@@ -2,43 +2,30 @@
 // All bf16 traffic is 16 B per lane; fp32 traffic 16 B per lane where the layout allows.
 #include "../../include/neurosis_hip.h"
 #include "nk_common.h"
+#include "nk_ew.h"
 #include "nk_reduce.h"
 #include "norm_plan.h"
 
-#define EW_THREADS 256
-static inline int ew_blocks(long work_items) {
-  long b = (work_items + EW_THREADS - 1) / EW_THREADS;
-  if (b > 8192) b = 8192;  // grid-stride the rest
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
+// ---- the map kernels: functors on the core of nk_ew.h -------------------------------------------------------------------------------------
 // ---- GEGLU (modules/attention.py:55-57): y = u[:, :I] * gelu(u[:, I:]) ------------------------
-__global__ void geglu_fwd_kernel(const bf16_t* __restrict__ u, bf16_t* __restrict__ y, long M, int I) {
-  const int cpr = I >> 3;
-  const long total = M * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long row = i / cpr;
-    int ch = (int)(i - row * cpr);
+struct GegluFwd {
+  const bf16_t* u; bf16_t* y; int I;
+  __device__ void operator()(long, long row, int ch) const {
     float a[8], g[8];
-    unpack8(*(const uint4_t*)(u + row * 2 * I + ch * 8), a);
-    unpack8(*(const uint4_t*)(u + row * 2 * I + I + ch * 8), g);
+    ew_load(u + row * 2 * I + ch * 8, a);
+    ew_load(u + row * 2 * I + I + ch * 8, g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] *= gelu_erf(g[e]);
-    *(uint4_t*)(y + row * I + ch * 8) = pack8(a);
+    ew_store(y + row * I + ch * 8, a);
   }
-}
-__global__ void geglu_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ u, bf16_t* __restrict__ du,
-                                 long M, int I) {
-  const int cpr = I >> 3;
-  const long total = M * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long row = i / cpr;
-    int ch = (int)(i - row * cpr);
+};
+struct GegluBwd {
+  const bf16_t *dy, *u; bf16_t* du; int I;
+  __device__ void operator()(long, long row, int ch) const {
     float a[8], g[8], d[8], da[8], dg[8];
-    unpack8(*(const uint4_t*)(u + row * 2 * I + ch * 8), a);
-    unpack8(*(const uint4_t*)(u + row * 2 * I + I + ch * 8), g);
-    unpack8(*(const uint4_t*)(dy + row * I + ch * 8), d);
+    ew_load(u + row * 2 * I + ch * 8, a);
+    ew_load(u + row * 2 * I + I + ch * 8, g);
+    ew_load(dy + row * I + ch * 8, d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float cdf, pdf;
@@ -46,21 +33,18 @@ __global__ void geglu_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __
       da[e] = d[e] * (g[e] * cdf);
       dg[e] = d[e] * a[e] * (cdf + g[e] * pdf);
     }
-    *(uint4_t*)(du + row * 2 * I + ch * 8) = pack8(da);
-    *(uint4_t*)(du + row * 2 * I + I + ch * 8) = pack8(dg);
+    ew_store(du + row * 2 * I + ch * 8, da);
+    ew_store(du + row * 2 * I + I + ch * 8, dg);
   }
-}
+};
 // saved-derivative form (round 6): y = a gelu(g) and s = [gelu(g) | a gelu'(g)] from u = [a | g] (s may BE u: every thread rewrites the two
-// chunks it read); the backward is then two products per element
-__global__ void geglu_fwd_s_kernel(const bf16_t* __restrict__ u, bf16_t* __restrict__ y, bf16_t* s, long M, int I) {
-  const int cpr = I >> 3;
-  const long total = M * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long row = i / cpr;
-    int ch = (int)(i - row * cpr);
+// chunks it read, after it has read both); the backward is then two products per element
+struct GegluFwdS {
+  const bf16_t* u; bf16_t *y, *s; int I;
+  __device__ void operator()(long, long row, int ch) const {
     float a[8], g[8], h[8], s1[8], s2[8];
-    unpack8(*(const uint4_t*)(u + row * 2 * I + ch * 8), a);
-    unpack8(*(const uint4_t*)(u + row * 2 * I + I + ch * 8), g);
+    ew_load(u + row * 2 * I + ch * 8, a);
+    ew_load(u + row * 2 * I + I + ch * 8, g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float cdf, pdf;
@@ -69,151 +53,122 @@ __global__ void geglu_fwd_s_kernel(const bf16_t* __restrict__ u, bf16_t* __restr
       h[e] = a[e] * s1[e];
       s2[e] = a[e] * (cdf + g[e] * pdf);
     }
-    *(uint4_t*)(y + row * I + ch * 8) = pack8(h);
-    *(uint4_t*)(s + row * 2 * I + ch * 8) = pack8(s1);
-    *(uint4_t*)(s + row * 2 * I + I + ch * 8) = pack8(s2);
+    ew_store(y + row * I + ch * 8, h);
+    ew_store(s + row * 2 * I + ch * 8, s1);
+    ew_store(s + row * 2 * I + I + ch * 8, s2);
   }
-}
-__global__ void geglu_bwd_s_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ s, bf16_t* __restrict__ du, long M, int I) {
-  const int cpr = I >> 3;
-  const long total = M * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long row = i / cpr;
-    int ch = (int)(i - row * cpr);
+};
+struct GegluBwdS {
+  const bf16_t *dy, *s; bf16_t* du; int I;
+  __device__ void operator()(long, long row, int ch) const {
     float s1[8], s2[8], d[8];
-    unpack8(*(const uint4_t*)(s + row * 2 * I + ch * 8), s1);
-    unpack8(*(const uint4_t*)(s + row * 2 * I + I + ch * 8), s2);
-    unpack8(*(const uint4_t*)(dy + row * I + ch * 8), d);
+    ew_load(s + row * 2 * I + ch * 8, s1);
+    ew_load(s + row * 2 * I + I + ch * 8, s2);
+    ew_load(dy + row * I + ch * 8, d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] *= d[e]; s2[e] *= d[e]; }
-    *(uint4_t*)(du + row * 2 * I + ch * 8) = pack8(s1);
-    *(uint4_t*)(du + row * 2 * I + I + ch * 8) = pack8(s2);
+    ew_store(du + row * 2 * I + ch * 8, s1);
+    ew_store(du + row * 2 * I + I + ch * 8, s2);
   }
-}
+};
 extern "C" int nk_geglu_fwd_s(const void* u, void* y, void* s, long M, int I, void* stream) {
   NK_CHECK_ARG(u && y && s && M > 0 && I > 0 && (I & 7) == 0);
-  hipLaunchKernelGGL(geglu_fwd_s_kernel, dim3(ew_blocks(M * (I >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)u, (bf16_t*)y,
-                     (bf16_t*)s, M, I);
-  return nk_check_launch("geglu_fwd_s");
+  return nk_ew_rows("geglu_fwd_s", stream, M, I >> 3, GegluFwdS{(const bf16_t*)u, (bf16_t*)y, (bf16_t*)s, I});
 }
 extern "C" int nk_geglu_bwd_s(const void* dy, const void* s, void* du, long M, int I, void* stream) {
   NK_CHECK_ARG(dy && s && du && M > 0 && I > 0 && (I & 7) == 0);
-  hipLaunchKernelGGL(geglu_bwd_s_kernel, dim3(ew_blocks(M * (I >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                     (const bf16_t*)s, (bf16_t*)du, M, I);
-  return nk_check_launch("geglu_bwd_s");
+  return nk_ew_rows("geglu_bwd_s", stream, M, I >> 3, GegluBwdS{(const bf16_t*)dy, (const bf16_t*)s, (bf16_t*)du, I});
 }
 extern "C" int nk_geglu_fwd(const void* u, void* y, long M, int I, void* stream) {
   NK_CHECK_ARG(u && y && M > 0 && I > 0 && (I & 7) == 0);
-  hipLaunchKernelGGL(geglu_fwd_kernel, dim3(ew_blocks(M * (I >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)u, (bf16_t*)y, M, I);
-  return nk_check_launch("geglu_fwd");
+  return nk_ew_rows("geglu_fwd", stream, M, I >> 3, GegluFwd{(const bf16_t*)u, (bf16_t*)y, I});
 }
 extern "C" int nk_geglu_bwd(const void* dy, const void* u, void* du, long M, int I, void* stream) {
   NK_CHECK_ARG(dy && u && du && M > 0 && I > 0 && (I & 7) == 0);
-  hipLaunchKernelGGL(geglu_bwd_kernel, dim3(ew_blocks(M * (I >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)dy, (const bf16_t*)u, (bf16_t*)du, M, I);
-  return nk_check_launch("geglu_bwd");
+  return nk_ew_rows("geglu_bwd", stream, M, I >> 3, GegluBwd{(const bf16_t*)dy, (const bf16_t*)u, (bf16_t*)du, I});
 }
 
 // ---- SiLU on a flat bf16 array (openaimodel.py:274, 588, 615) ----------------------------------
-__global__ void silu_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long n8) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+struct SiluFwd {
+  const bf16_t* x; bf16_t* y;
+  __device__ void operator()(long i) const {
     float f[8];
-    unpack8(*(const uint4_t*)(x + i * 8), f);
+    ew_load(x + i * 8, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] = silu_f(f[e]);
-    *(uint4_t*)(y + i * 8) = pack8(f);
+    ew_store(y + i * 8, f);
   }
-}
-__global__ void silu_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, bf16_t* __restrict__ dx,
-                                long n8) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+};
+struct SiluBwd {
+  const bf16_t *dy, *x; bf16_t* dx;
+  __device__ void operator()(long i) const {
     float f[8], d[8];
-    unpack8(*(const uint4_t*)(x + i * 8), f);
-    unpack8(*(const uint4_t*)(dy + i * 8), d);
+    ew_load(x + i * 8, f);
+    ew_load(dy + i * 8, d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) d[e] *= dsilu_f(f[e]);
-    *(uint4_t*)(dx + i * 8) = pack8(d);
+    ew_store(dx + i * 8, d);
   }
-}
+};
 extern "C" int nk_silu_fwd(const void* x, void* y, long n, void* stream) {
   NK_CHECK_ARG(x && y && n > 0 && (n & 7) == 0);
-  hipLaunchKernelGGL(silu_fwd_kernel, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (bf16_t*)y, n >> 3);
-  return nk_check_launch("silu_fwd");
+  return nk_ew_flat("silu_fwd", stream, n >> 3, SiluFwd{(const bf16_t*)x, (bf16_t*)y});
 }
 extern "C" int nk_silu_bwd(const void* dy, const void* x, void* dx, long n, void* stream) {
   NK_CHECK_ARG(dy && x && dx && n > 0 && (n & 7) == 0);
-  hipLaunchKernelGGL(silu_bwd_kernel, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, n >> 3);
-  return nk_check_launch("silu_bwd");
+  return nk_ew_flat("silu_bwd", stream, n >> 3, SiluBwd{(const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx});
 }
 
 // ---- GELU of the CLIP text transformers ---------------------------------------------------------
 // mode 0: exact erf form (open_clip's nn.GELU); mode 1: quick_gelu x * sigmoid(1.702 x) (openai/clip-vit-large-patch14);
-// mode 2: "gelu_new", the tanh form 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) of T5 v1.1 / ByT5; mode 3: ReLU (T5 v1.0)
-// 0.5 (1 + tanh z) = 1 / (1 + exp(-2 z)): one exponential, and no cancellation where tanh z is near -1
-__device__ __forceinline__ float gelu_tanh(float x) {
-  const float z2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);      // 2 sqrt(2 / pi) (x + 0.044715 x^3)
-  return x / (1.0f + __expf(-z2));
-}
+// mode 2: "gelu_new", the tanh form of T5 v1.1 / ByT5 (gelu_tanh, nk_common.h); mode 3: ReLU (T5 v1.0)
 template <int MODE>
-__global__ void gelu_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long n8) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+struct GeluFwd {
+  const bf16_t* x; bf16_t* y;
+  __device__ void operator()(long i) const {
     float f[8];
-    unpack8(*(const uint4_t*)(x + i * 8), f);
+    ew_load(x + i * 8, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
       f[e] = MODE == 0 ? 0.5f * f[e] * (1.0f + erff(f[e] * 0.70710678118654752f)) : MODE == 1 ? f[e] / (1.0f + __expf(-1.702f * f[e]))
            : MODE == 2 ? gelu_tanh(f[e]) : fmaxf(f[e], 0.f);
-    *(uint4_t*)(y + i * 8) = pack8(f);
+    ew_store(y + i * 8, f);
   }
-}
+};
 extern "C" int nk_gelu_fwd(const void* x, void* y, long n, int mode, void* stream) {
   NK_CHECK_ARG(x && y && n > 0 && (n & 7) == 0 && mode >= 0 && mode <= 3);
-  if (mode == 0)
-    hipLaunchKernelGGL(gelu_fwd_kernel<0>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
-  else if (mode == 1)
-    hipLaunchKernelGGL(gelu_fwd_kernel<1>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
-  else if (mode == 2)
-    hipLaunchKernelGGL(gelu_fwd_kernel<2>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
-  else
-    hipLaunchKernelGGL(gelu_fwd_kernel<3>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3);
-  return nk_check_launch("gelu_fwd");
+  return nk_ew_mode<0, 3>(mode, [&](auto m) { return nk_ew_flat("gelu_fwd", stream, n >> 3, GeluFwd<decltype(m)::value>{(const bf16_t*)x, (bf16_t*)y}); });
 }
 
 // ---- gated activation of the T5 v1.1 / ByT5 FeedForward: y = gelu_new(u[:, :I]) * u[:, I:] ----------------------------------------------
 // u [M][2 I] = one stacked projection [wi_0; wi_1] of the normed tokens, so the FeedForward is two GEMMs and this pass.  (The GEGLU of the
-// UNet, geglu_fwd_kernel above, gates the other way round and with the erf form.)
-__global__ void gated_gelu_tanh_kernel(const bf16_t* __restrict__ u, bf16_t* __restrict__ y, long M, int I) {
-  const int cpr = I >> 3;
-  const long total = M * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long row = i / cpr;
-    const int ch = (int)(i - row * cpr);
+// UNet, GegluFwd above, gates the other way round and with the erf form.)
+struct GatedGeluTanh {
+  const bf16_t* u; bf16_t* y; int I;
+  __device__ void operator()(long, long row, int ch) const {
     float a[8], g[8];
-    unpack8(*(const uint4_t*)(u + row * 2 * I + ch * 8), a);
-    unpack8(*(const uint4_t*)(u + row * 2 * I + I + ch * 8), g);
+    ew_load(u + row * 2 * I + ch * 8, a);
+    ew_load(u + row * 2 * I + I + ch * 8, g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] = gelu_tanh(a[e]) * g[e];
-    *(uint4_t*)(y + row * I + ch * 8) = pack8(a);
+    ew_store(y + row * I + ch * 8, a);
   }
-}
+};
 extern "C" int nk_gated_gelu_tanh_fwd(const void* u, void* y, long M, int I, void* stream) {
   NK_CHECK_ARG(u && y && M > 0 && I > 0 && (I & 7) == 0);
-  NK_CHECK_ARG(((uintptr_t)u & 15) == 0 && ((uintptr_t)y & 15) == 0);     // 16-byte accesses
-  hipLaunchKernelGGL(gated_gelu_tanh_kernel, dim3(ew_blocks(M * (I >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)u, (bf16_t*)y, M, I);
-  return nk_check_launch("gated_gelu_tanh_kernel");
+  NK_CHECK_ARG(nk_aligned16(u) && nk_aligned16(y));     // 16-byte accesses
+  return nk_ew_rows("gated_gelu_tanh_kernel", stream, M, I >> 3, GatedGeluTanh{(const bf16_t*)u, (bf16_t*)y, I});
 }
 
 // GELU backward (trainable text towers): dx = dy * gelu'(x), fp32 arithmetic on bf16 data, the same modes as the forward
 //   mode 0: gelu'(x) = Phi(x) + x phi(x);  mode 1: s + 1.702 x s (1 - s), s = sigmoid(1.702 x)
 template <int MODE>
-__global__ void gelu_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, bf16_t* __restrict__ dx, long n8) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+struct GeluBwd {
+  const bf16_t *dy, *x; bf16_t* dx;
+  __device__ void operator()(long i) const {
     float g[8], f[8];
-    unpack8(*(const uint4_t*)(dy + i * 8), g);
-    unpack8(*(const uint4_t*)(x + i * 8), f);
+    ew_load(dy + i * 8, g);
+    ew_load(x + i * 8, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float d;
@@ -225,19 +180,15 @@ __global__ void gelu_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __r
       }
       g[e] *= d;
     }
-    *(uint4_t*)(dx + i * 8) = pack8(g);
+    ew_store(dx + i * 8, g);
   }
-}
+};
 extern "C" int nk_gelu_bwd(const void* dy, const void* x, void* dx, long n, int mode, void* stream) {
   NK_CHECK_ARG(dy && x && dx && n > 0 && (n & 7) == 0 && (mode == 0 || mode == 1));
-  NK_CHECK_ARG(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0);     // 16-byte accesses
-  if (mode == 0)
-    hipLaunchKernelGGL(gelu_bwd_kernel<0>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x,
-                       (bf16_t*)dx, n >> 3);
-  else
-    hipLaunchKernelGGL(gelu_bwd_kernel<1>, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x,
-                       (bf16_t*)dx, n >> 3);
-  return nk_check_launch("gelu_bwd");
+  NK_CHECK_ARG(nk_aligned16(dy) && nk_aligned16(x) && nk_aligned16(dx));     // 16-byte accesses
+  return nk_ew_mode<0, 1>(mode, [&](auto m) {
+    return nk_ew_flat("gelu_bwd", stream, n >> 3, GeluBwd<decltype(m)::value>{(const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx});
+  });
 }
 
 // ---- token + position embedding backward (trainable text towers) --------------------------------
@@ -291,7 +242,7 @@ __global__ void embedding_bwd_kernel(const long long* __restrict__ ids, const bf
 extern "C" int nk_embedding_bwd(const long long* ids, const void* dx, long ldx, float* dtable, float* dpos, int B, int L, int V, int P, int C,
                                 int accumulate, void* stream_) {
   NK_CHECK_ARG(ids && dx && dtable && dpos && B > 0 && L > 0 && L <= P && V > 0 && C > 0 && (C & 7) == 0 && (ldx & 7) == 0 && ldx >= C);
-  NK_CHECK_ARG(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dtable & 15) == 0 && ((uintptr_t)dpos & 15) == 0);
+  NK_CHECK_ARG(nk_aligned16(dx) && nk_aligned16(dtable) && nk_aligned16(dpos));
   NK_CHECK_ARG((long)B * L <= NK_EMBEDDING_BWD_MAX_TOKENS && accumulate >= 0 && accumulate <= 2);     // (the id scans are quadratic in B * L)
   hipStream_t stream = (hipStream_t)stream_;
   if (accumulate == 0) {     // overwrite: rows no token (no position) hit are zero; (2: the caller's buffers are zero already)
@@ -317,9 +268,9 @@ __global__ void gather_rows_bwd_kernel(const bf16_t* __restrict__ dsel, long lds
 }
 extern "C" int nk_gather_rows_bwd(const void* dsel, long ldsel, const long long* idx, void* dx, int B, int L, int C, void* stream) {
   NK_CHECK_ARG(dsel && idx && dx && B > 0 && L > 0 && C > 0 && (C & 7) == 0 && (ldsel & 7) == 0 && ldsel >= C);
-  NK_CHECK_ARG(((uintptr_t)dsel & 15) == 0 && ((uintptr_t)dx & 15) == 0);                                 // 16-byte accesses
+  NK_CHECK_ARG(nk_aligned16(dsel) && nk_aligned16(dx));                                 // 16-byte accesses
   const long n8 = (long)B * L * (C >> 3);
-  hipLaunchKernelGGL(gather_rows_bwd_kernel, dim3(ew_blocks(n8)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)dsel, ldsel, idx,
+  hipLaunchKernelGGL(gather_rows_bwd_kernel, dim3(nk_ew_grid(n8)), dim3(NK_EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)dsel, ldsel, idx,
                      (bf16_t*)dx, L, C >> 3, n8);
   return nk_check_launch("gather_rows_bwd");
 }
@@ -341,173 +292,130 @@ extern "C" int nk_wgrad_few_rows(const void* x, long ldx, const void* dy, long l
                                  void* stream) {
   NK_CHECK_ARG(x && dy && dw && M > 0 && M <= 256 && K > 0 && N > 0 && ldx >= K && lddy >= N && lddw >= N);
   const long total = (long)K * N;
-  hipLaunchKernelGGL(wgrad_few_rows_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
+  hipLaunchKernelGGL(wgrad_few_rows_kernel, dim3(nk_ew_grid(total)), dim3(NK_EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
                      (const bf16_t*)dy, lddy, dw, lddw, M, K, N, accumulate);
   return nk_check_launch("wgrad_few_rows");
 }
 
 // ---- out = a + b (gradient join where a tensor feeds two consumers) ----------------------------
-__global__ void add_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, bf16_t* __restrict__ o, long n8) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+struct Add {
+  const bf16_t *a, *b; bf16_t* o;
+  __device__ void operator()(long i) const {
     float f[8], g[8];
-    unpack8(*(const uint4_t*)(a + i * 8), f);
-    unpack8(*(const uint4_t*)(b + i * 8), g);
+    ew_load(a + i * 8, f);
+    ew_load(b + i * 8, g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] += g[e];
-    *(uint4_t*)(o + i * 8) = pack8(f);
+    ew_store(o + i * 8, f);
   }
-}
+};
 extern "C" int nk_add(const void* a, const void* b, void* out, long n, void* stream) {
   NK_CHECK_ARG(a && b && out && n > 0 && (n & 7) == 0);
-  hipLaunchKernelGGL(add_kernel, dim3(ew_blocks(n >> 3)), dim3(EW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)a,
-                     (const bf16_t*)b, (bf16_t*)out, n >> 3);
-  return nk_check_launch("add");
+  return nk_ew_flat("add", stream, n >> 3, Add{(const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out});
 }
 
 // ---- channel concat / split on channels-last rows (torch.cat(dim=1), openaimodel.py:836) -------
 // dir 0: out[row] = [a[row] | b[row]] ; dir 1: a[row], b[row] = split(out[row]) (either may be NULL)
-__global__ void cat_kernel(bf16_t* __restrict__ a, bf16_t* __restrict__ b, bf16_t* __restrict__ o, long rows, int Ca,
-                           int Cb, int dir) {
-  const int cpr = (Ca + Cb) >> 3, ca8 = Ca >> 3;
-  const long total = rows * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long row = i / cpr;
-    int ch = (int)(i - row * cpr);
+struct Cat {
+  bf16_t *a, *b, *o; int Ca, Cb, dir;
+  __device__ void operator()(long i, long row, int ch) const {
+    const int ca8 = Ca >> 3;
     bf16_t* side = ch < ca8 ? (a ? a + row * Ca + ch * 8 : nullptr) : (b ? b + row * Cb + (ch - ca8) * 8 : nullptr);
-    if (!side) continue;
+    if (!side) return;
     uint4_t* op = (uint4_t*)(o + i * 8);
     if (dir == 0) *op = *(const uint4_t*)side;
     else *(uint4_t*)side = *op;
   }
-}
+};
 extern "C" int nk_cat_channels(const void* a, const void* b, void* out, long rows, int Ca, int Cb, void* stream) {
   NK_CHECK_ARG(a && b && out && rows > 0 && Ca > 0 && Cb > 0 && (Ca & 7) == 0 && (Cb & 7) == 0);
-  hipLaunchKernelGGL(cat_kernel, dim3(ew_blocks(rows * ((Ca + Cb) >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (bf16_t*)a, (bf16_t*)b, (bf16_t*)out, rows, Ca, Cb, 0);
-  return nk_check_launch("cat_channels");
+  return nk_ew_rows("cat_channels", stream, rows, (Ca + Cb) >> 3, Cat{(bf16_t*)a, (bf16_t*)b, (bf16_t*)out, Ca, Cb, 0});
 }
 extern "C" int nk_split_channels(const void* src, void* a, void* b, long rows, int Ca, int Cb, void* stream) {
   NK_CHECK_ARG(src && (a || b) && rows > 0 && Ca > 0 && Cb > 0 && (Ca & 7) == 0 && (Cb & 7) == 0);
-  hipLaunchKernelGGL(cat_kernel, dim3(ew_blocks(rows * ((Ca + Cb) >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (bf16_t*)a, (bf16_t*)b, (bf16_t*)src, rows, Ca, Cb, 1);
-  return nk_check_launch("split_channels");
-}
-
-// ---- backward of nearest 2x upsampling: dx[n,h,w,:] = sum of the 2x2 block of dup --------------
-__global__ void up2_bwd_kernel(const bf16_t* __restrict__ dup, bf16_t* __restrict__ dx, int N, int H, int W, int C) {
-  const int cpr = C >> 3;
-  const long total = (long)N * H * W * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int ch = (int)(i % cpr);
-    long pix = i / cpr;
-    int w = (int)(pix % W);
-    long t = pix / W;
-    int h = (int)(t % H);
-    int n = (int)(t / H);
-    const bf16_t* s = dup + (((long)n * 2 * H + 2 * h) * 2 * W + 2 * w) * C + ch * 8;
-    float acc[8], f[8];
-    unpack8(*(const uint4_t*)s, acc);
-    unpack8(*(const uint4_t*)(s + C), f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] += f[e];
-    unpack8(*(const uint4_t*)(s + (long)2 * W * C), f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] += f[e];
-    unpack8(*(const uint4_t*)(s + (long)2 * W * C + C), f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] += f[e];
-    *(uint4_t*)(dx + i * 8) = pack8(acc);
-  }
-}
-extern "C" int nk_upsample2x_bwd(const void* dup, void* dx, int N, int H, int W, int C, void* stream) {
-  NK_CHECK_ARG(dup && dx && N > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0);
-  hipLaunchKernelGGL(up2_bwd_kernel, dim3(ew_blocks((long)N * H * W * (C >> 3))), dim3(EW_THREADS), 0,
-                     (hipStream_t)stream, (const bf16_t*)dup, (bf16_t*)dx, N, H, W, C);
-  return nk_check_launch("upsample2x_bwd");
+  return nk_ew_rows("split_channels", stream, rows, (Ca + Cb) >> 3, Cat{(bf16_t*)a, (bf16_t*)b, (bf16_t*)src, Ca, Cb, 1});
 }
 
 // ---- parameter-free resampling (Upsample / Downsample with use_conv=False, the up / down ResBlock; openaimodel.py:96-197) ----
-// nearest 2x forward, materialised: up[n, h, w, :] = x[n, h/2, w/2, :]   (its backward is up2_bwd_kernel)
-__global__ void up2_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ up, int N, int H, int W, int C) {
-  const int cpr = C >> 3;
-  const long total = (long)N * 2 * H * 2 * W * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int ch = (int)(i % cpr);
-    long pix = i / cpr;
-    int w = (int)(pix % (2 * W));
-    long t = pix / (2 * W);
-    int h = (int)(t % (2 * H));
-    int n = (int)(t / (2 * H));
+// The pixel ops run over their OUTPUT image; H, W, C are the entry point's.
+// backward of nearest 2x upsampling: dx[n,h,w,:] = sum of the 2x2 block of dup
+struct Up2Bwd {
+  const bf16_t* dup; bf16_t* dx; int H, W, C;
+  __device__ void operator()(long i, int n, int h, int w, int ch) const {
+    const bf16_t* s = dup + (((long)n * 2 * H + 2 * h) * 2 * W + 2 * w) * C + ch * 8;
+    float acc[8], f[8];
+    ew_load(s, acc);
+    ew_load(s + C, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += f[e];
+    ew_load(s + (long)2 * W * C, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += f[e];
+    ew_load(s + (long)2 * W * C + C, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += f[e];
+    ew_store(dx + i * 8, acc);
+  }
+};
+// nearest 2x forward, materialised: up[n, h, w, :] = x[n, h/2, w/2, :]
+struct Up2Fwd {
+  const bf16_t* x; bf16_t* up; int H, W, C;
+  __device__ void operator()(long i, int n, int h, int w, int ch) const {
     *(uint4_t*)(up + i * 8) = *(const uint4_t*)(x + (((long)n * H + (h >> 1)) * W + (w >> 1)) * C + ch * 8);
   }
+};
+extern "C" int nk_upsample2x_bwd(const void* dup, void* dx, int N, int H, int W, int C, void* stream) {
+  NK_CHECK_ARG(dup && dx && N > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0);
+  return nk_ew_pixels("upsample2x_bwd", stream, N, H, W, C >> 3, Up2Bwd{(const bf16_t*)dup, (bf16_t*)dx, H, W, C});
 }
 extern "C" int nk_upsample2x_fwd(const void* x, void* up, int N, int H, int W, int C, void* stream) {
   NK_CHECK_ARG(x && up && N > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0);
-  hipLaunchKernelGGL(up2_fwd_kernel, dim3(ew_blocks((long)N * 4 * H * W * (C >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (bf16_t*)up, N, H, W, C);
-  return nk_check_launch("upsample2x_fwd");
+  return nk_ew_pixels("upsample2x_fwd", stream, N, 2 * H, 2 * W, C >> 3, Up2Fwd{(const bf16_t*)x, (bf16_t*)up, H, W, C});
 }
 
 // avg_pool2d(2, 2), floor mode: y[n, h, w, :] = mean of x[n, 2h..2h+1, 2w..2w+1, :], summed in fp32 and rounded once; an odd last row or
 // column of x is not read
-__global__ void avgpool2x_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int N, int H, int W, int C) {
-  const int cpr = C >> 3, Ho = H >> 1, Wo = W >> 1;
-  const long total = (long)N * Ho * Wo * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int ch = (int)(i % cpr);
-    long pix = i / cpr;
-    int w = (int)(pix % Wo);
-    long t = pix / Wo;
-    int h = (int)(t % Ho);
-    int n = (int)(t / Ho);
+struct AvgPool2xFwd {
+  const bf16_t* x; bf16_t* y; int H, W, C;
+  __device__ void operator()(long i, int n, int h, int w, int ch) const {
     const bf16_t* s = x + (((long)n * H + 2 * h) * W + 2 * w) * C + ch * 8;
     float acc[8], f[8];
-    unpack8(*(const uint4_t*)s, acc);
-    unpack8(*(const uint4_t*)(s + C), f);
+    ew_load(s, acc);
+    ew_load(s + C, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] += f[e];
-    unpack8(*(const uint4_t*)(s + (long)W * C), f);
+    ew_load(s + (long)W * C, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] += f[e];
-    unpack8(*(const uint4_t*)(s + (long)W * C + C), f);
+    ew_load(s + (long)W * C + C, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = (acc[e] + f[e]) * 0.25f;
-    *(uint4_t*)(y + i * 8) = pack8(acc);
+    ew_store(y + i * 8, acc);
   }
-}
+};
 // ... backward: dx[n, h, w, :] = dy[n, h/2, w/2, :] / 4; zeros in the odd last row or column the forward dropped
-__global__ void avgpool2x_bwd_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx, int N, int H, int W, int C) {
-  const int cpr = C >> 3, Ho = H >> 1, Wo = W >> 1;
-  const long total = (long)N * H * W * cpr;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int ch = (int)(i % cpr);
-    long pix = i / cpr;
-    int w = (int)(pix % W);
-    long t = pix / W;
-    int h = (int)(t % H);
-    int n = (int)(t / H);
+struct AvgPool2xBwd {
+  const bf16_t* dy; bf16_t* dx; int H, W, C;
+  __device__ void operator()(long i, int n, int h, int w, int ch) const {
+    const int Ho = H >> 1, Wo = W >> 1;
     uint4_t out = {0u, 0u, 0u, 0u};
     if ((h >> 1) < Ho && (w >> 1) < Wo) {
       float f[8];
-      unpack8(*(const uint4_t*)(dy + (((long)n * Ho + (h >> 1)) * Wo + (w >> 1)) * C + ch * 8), f);
+      ew_load(dy + (((long)n * Ho + (h >> 1)) * Wo + (w >> 1)) * C + ch * 8, f);
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] *= 0.25f;
       out = pack8(f);
     }
     *(uint4_t*)(dx + i * 8) = out;
   }
-}
+};
 extern "C" int nk_avgpool2x_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
   NK_CHECK_ARG(x && y && N > 0 && H > 1 && W > 1 && C > 0 && (C & 7) == 0);
-  hipLaunchKernelGGL(avgpool2x_fwd_kernel, dim3(ew_blocks((long)N * (H >> 1) * (W >> 1) * (C >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (bf16_t*)y, N, H, W, C);
-  return nk_check_launch("avgpool2x_fwd");
+  return nk_ew_pixels("avgpool2x_fwd", stream, N, H >> 1, W >> 1, C >> 3, AvgPool2xFwd{(const bf16_t*)x, (bf16_t*)y, H, W, C});
 }
 extern "C" int nk_avgpool2x_bwd(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
   NK_CHECK_ARG(dy && dx && N > 0 && H > 1 && W > 1 && C > 0 && (C & 7) == 0);
-  hipLaunchKernelGGL(avgpool2x_bwd_kernel, dim3(ew_blocks((long)N * H * W * (C >> 3))), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                     (const bf16_t*)dy, (bf16_t*)dx, N, H, W, C);
-  return nk_check_launch("avgpool2x_bwd");
+  return nk_ew_pixels("avgpool2x_bwd", stream, N, H, W, C >> 3, AvgPool2xBwd{(const bf16_t*)dy, (bf16_t*)dx, H, W, C});
 }
 
 // ---- layout / dtype boundary: NCHW (fp32 or bf16) <-> channels-last bf16 with channel padding ---
@@ -744,14 +652,14 @@ __global__ void cast_bf16_f32_kernel(const bf16_t* __restrict__ s, float* __rest
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) d[i] = bf2f(s[i]);
 }
 extern "C" int nk_cast_f32_to_bf16(const float* src, void* dst, long n, void* stream) {
-  NK_CHECK_ARG(src && dst && n > 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0);
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(ew_blocks((n >> 3) + 1)), dim3(EW_THREADS), 0, (hipStream_t)stream, src,
+  NK_CHECK_ARG(src && dst && n > 0 && nk_aligned16(src) && nk_aligned16(dst));
+  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(nk_ew_grid((n >> 3) + 1)), dim3(NK_EW_THREADS), 0, (hipStream_t)stream, src,
                      (bf16_t*)dst, n);
   return nk_check_launch("cast_f32_to_bf16");
 }
 extern "C" int nk_cast_bf16_to_f32(const void* src, float* dst, long n, void* stream) {
   NK_CHECK_ARG(src && dst && n > 0);
-  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(nk_ew_grid(n)), dim3(NK_EW_THREADS), 0, (hipStream_t)stream,
                      (const bf16_t*)src, dst, n);
   return nk_check_launch("cast_bf16_to_f32");
 }
@@ -1030,7 +938,7 @@ __global__ void edm_prepare_kernel(const float* __restrict__ x, const float* __r
 // the wrapper joins `extra` behind them UNSCALED): net_in[b][p][c] = bf16(z_t*c_in) for c < C, bf16(extra[b][c-C][p]) for
 // C <= c < C+Ce, 0 up to Cpad.  extra: fp32 NCHW [B][Ce][HW].  One thread per pixel, NCHW reads coalesced across pixels, the
 // token side one 16-byte vector per 8 channels (Cpad % 8 == 0).
-__global__ __launch_bounds__(EW_THREADS) void edm_prepare_cat_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+__global__ __launch_bounds__(NK_EW_THREADS) void edm_prepare_cat_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                                                      const float* __restrict__ sigma, const float* __restrict__ c_in,
                                                                      const float* __restrict__ extra, float* __restrict__ zt,
                                                                      bf16_t* __restrict__ net_in, int B, int C, int Ce, int HW, int Cpad) {
@@ -1059,7 +967,7 @@ __global__ __launch_bounds__(EW_THREADS) void edm_prepare_cat_kernel(const float
 extern "C" int nk_edm_prepare(const float* x, const float* eps, const float* sigma, const float* c_in, float* zt,
                               void* net_in, int B, int C, int HW, int Cpad, void* stream) {
   NK_CHECK_ARG(x && eps && sigma && c_in && zt && net_in && B > 0 && C > 0 && HW > 0 && Cpad >= C);
-  hipLaunchKernelGGL(edm_prepare_kernel, dim3(ew_blocks((long)B * HW)), dim3(EW_THREADS), 0, (hipStream_t)stream, x,
+  hipLaunchKernelGGL(edm_prepare_kernel, dim3(nk_ew_grid((long)B * HW)), dim3(NK_EW_THREADS), 0, (hipStream_t)stream, x,
                      eps, sigma, c_in, zt, (bf16_t*)net_in, B, C, HW, Cpad);
   return nk_check_launch("edm_prepare");
 }
@@ -1067,7 +975,7 @@ extern "C" int nk_edm_prepare_cat(const float* x, const float* eps, const float*
                                   float* zt, void* net_in, int B, int C, int Ce, int HW, int Cpad, void* stream) {
   NK_CHECK_ARG(x && eps && sigma && c_in && zt && net_in && B > 0 && C > 0 && HW > 0 && Ce >= 0 && (extra || Ce == 0));
   NK_CHECK_ARG(Cpad >= C + Ce && (Cpad & 7) == 0 && Cpad - (C + Ce) < 8);
-  hipLaunchKernelGGL(edm_prepare_cat_kernel, dim3(ew_blocks((long)B * HW)), dim3(EW_THREADS), 0, (hipStream_t)stream, x,
+  hipLaunchKernelGGL(edm_prepare_cat_kernel, dim3(nk_ew_grid((long)B * HW)), dim3(NK_EW_THREADS), 0, (hipStream_t)stream, x,
                      eps, sigma, c_in, extra, zt, (bf16_t*)net_in, B, C, Ce, HW, Cpad);
   return nk_check_launch("edm_prepare_cat");
 }
@@ -1153,7 +1061,7 @@ extern "C" int nk_adamw_flat(float* p, const float* g, float* m, float* v, void*
   const unsigned* health = nk_health_word();
   if (!health) { nk_set_error(__FILE__, __LINE__, "health word allocation failed"); return NK_ERR_LAUNCH; }
   float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_flat_kernel, dim3(ew_blocks(n >> 2)), dim3(EW_THREADS), 0, (hipStream_t)stream, p, g, m, v,
+  hipLaunchKernelGGL(adamw_flat_kernel, dim3(nk_ew_grid(n >> 2)), dim3(NK_EW_THREADS), 0, (hipStream_t)stream, p, g, m, v,
                      (bf16_t*)shadow, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, health);
   if (int e = nk_check_launch("adamw_flat")) return e;
   nk_health_snapshot((hipStream_t)stream);

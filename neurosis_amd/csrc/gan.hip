@@ -6,7 +6,12 @@
 // 16 B), fp32 partials per 64-row slab, single-writer finalisation in a fixed order (bitwise reproducible).  All three passes
 // are HBM-bound: forward = 2 reads + 1 write of x, backward = 3 reads + 1 write.
 #include "nk_common.h"
+#include "nk_ew.h"
 #include "../../include/neurosis_hip.h"
+
+// The map kernels of this file keep the grid cap they always had (elementwise.hip's run at NK_EW_CAP = 8192): at the VAE-training sizes the two
+// caps give different grids (the first PatchGAN LeakyReLU, 32 x 128 x 128 x 64, is 4 194 304 chunks = 16 384 blocks).
+#define GAN_EW_CAP 65535
 
 #define BN_ROWS 64
 static int bn_slabs(long M) { return (int)((M + BN_ROWS - 1) / BN_ROWS); }
@@ -14,42 +19,36 @@ static int bn_slabs(long M) { return (int)((M + BN_ROWS - 1) / BN_ROWS); }
 __device__ __forceinline__ float leaky(float v, float slope) { return v >= 0.f ? v : v * slope; }
 
 // ---- LeakyReLU --------------------------------------------------------------------------------------
-__global__ void leaky_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, long n8, float slope) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+struct LeakyFwd {
+  const bf16_t* x; bf16_t* y; float slope;
+  __device__ void operator()(long i) const {
     float f[8];
-    unpack8(*(const uint4_t*)(x + i * 8), f);
+    ew_load(x + i * 8, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] = leaky(f[e], slope);
-    *(uint4_t*)(y + i * 8) = pack8(f);
+    ew_store(y + i * 8, f);
   }
-}
+};
 // dx = dy where the OUTPUT is > 0, else dy * slope (the output has the input's sign for slope > 0, and is 0 exactly where a
 // ReLU -- slope 0 -- blocked it; torch takes the `slope` branch at 0 as well)
-__global__ void leaky_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y, bf16_t* __restrict__ dx, long n8,
-                                 float slope) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
+struct LeakyBwd {
+  const bf16_t *dy, *y; bf16_t* dx; float slope;
+  __device__ void operator()(long i) const {
     float f[8], g[8];
-    unpack8(*(const uint4_t*)(y + i * 8), f);
-    unpack8(*(const uint4_t*)(dy + i * 8), g);
+    ew_load(y + i * 8, f);
+    ew_load(dy + i * 8, g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) g[e] = f[e] > 0.f ? g[e] : g[e] * slope;
-    *(uint4_t*)(dx + i * 8) = pack8(g);
+    ew_store(dx + i * 8, g);
   }
-}
-static int ew_grid(long n) {
-  long b = (n + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 65535 ? 65535 : b));
-}
+};
 extern "C" int nk_leaky_relu_fwd(const void* x, void* y, long n, float slope, void* stream) {
   NK_CHECK_ARG(x && y && n > 0 && (n & 7) == 0 && slope >= 0.f);
-  hipLaunchKernelGGL(leaky_fwd_kernel, dim3(ew_grid(n >> 3)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, n >> 3, slope);
-  return nk_check_launch("leaky_relu_fwd");
+  return nk_ew_flat("leaky_relu_fwd", stream, n >> 3, LeakyFwd{(const bf16_t*)x, (bf16_t*)y, slope}, GAN_EW_CAP);
 }
 extern "C" int nk_leaky_relu_bwd(const void* dy, const void* y, void* dx, long n, float slope, void* stream) {
   NK_CHECK_ARG(dy && y && dx && n > 0 && (n & 7) == 0 && slope >= 0.f);
-  hipLaunchKernelGGL(leaky_bwd_kernel, dim3(ew_grid(n >> 3)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)y,
-                     (bf16_t*)dx, n >> 3, slope);
-  return nk_check_launch("leaky_relu_bwd");
+  return nk_ew_flat("leaky_relu_bwd", stream, n >> 3, LeakyBwd{(const bf16_t*)dy, (const bf16_t*)y, (bf16_t*)dx, slope}, GAN_EW_CAP);
 }
 
 // ---- column partials: part[slab][2][C] = { sum_m a, sum_m a*b } over the slab's rows -----------------
@@ -161,35 +160,29 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
   dgamma[c] = accumulate ? dgamma[c] + q : q;
 }
 
-// y = act((x - mean) * rstd * gamma + beta)
-__global__ void bn_apply_kernel(const bf16_t* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
-                                const float* __restrict__ gamma, const float* __restrict__ beta, bf16_t* __restrict__ y, long M, int C,
-                                float slope) {
-  const int chunks = C >> 3;
-  const long total = M * chunks;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % chunks) * 8;
+// y = act((x - mean) * rstd * gamma + beta); a rows op on [M][C]: ch is the chunk's channel block
+struct BnApply {
+  const bf16_t* x; const float *mean, *rstd, *gamma, *beta; bf16_t* y; float slope;
+  __device__ void operator()(long i, long, int chunk) const {
+    const int ch = chunk * 8;
     float f[8];
-    unpack8(*(const uint4_t*)(x + i * 8), f);
+    ew_load(x + i * 8, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] = leaky((f[e] - mean[ch + e]) * rstd[ch + e] * gamma[ch + e] + beta[ch + e], slope);
-    *(uint4_t*)(y + i * 8) = pack8(f);
+    ew_store(y + i * 8, f);
   }
-}
+};
 // dx = gamma * rstd * (g - sum_g / M - xhat * sum_gx / M),  g = dy * act'(y)
-__global__ void bn_bwd_dx_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const bf16_t* __restrict__ y,
-                                 const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                 const float* __restrict__ sums, bf16_t* __restrict__ dx, long M, int C, float slope) {
-  const int chunks = C >> 3;
-  const long total = M * chunks;
-  const float inv_m = 1.f / (float)M;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % chunks) * 8;
+struct BnBwdDx {
+  const bf16_t *dy, *x, *y; const float *mean, *rstd, *gamma, *sums; bf16_t* dx; long M; int C; float slope;
+  __device__ void operator()(long i, long, int chunk) const {
+    const int ch = chunk * 8;
+    const float inv_m = 1.f / (float)M;
     float g[8], v[8], o[8];
-    unpack8(*(const uint4_t*)(dy + i * 8), g);
-    unpack8(*(const uint4_t*)(x + i * 8), v);
+    ew_load(dy + i * 8, g);
+    ew_load(x + i * 8, v);
     if (slope != 1.f) {
-      unpack8(*(const uint4_t*)(y + i * 8), o);
+      ew_load(y + i * 8, o);
 #pragma unroll
       for (int e = 0; e < 8; ++e) g[e] = o[e] > 0.f ? g[e] : g[e] * slope;
     }
@@ -198,9 +191,9 @@ __global__ void bn_bwd_dx_kernel(const bf16_t* __restrict__ dy, const bf16_t* __
       const float xhat = (v[e] - mean[ch + e]) * rstd[ch + e];
       g[e] = gamma[ch + e] * rstd[ch + e] * (g[e] - sums[ch + e] * inv_m - xhat * sums[C + ch + e] * inv_m);
     }
-    *(uint4_t*)(dx + i * 8) = pack8(g);
+    ew_store(dx + i * 8, g);
   }
-}
+};
 
 extern "C" long nk_batchnorm_ws_floats(long M, int C) { return (long)bn_slabs(M) * 2 * C + 2 * (long)C + 64; }
 
@@ -217,9 +210,7 @@ extern "C" int nk_batchnorm_fwd(const void* x, const float* gamma, const float* 
   hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((C + 63) / 64), dim3(1024), 0, stream, ws, slabs, C, M, eps, momentum, mean, rstd,
                      running_mean, running_var);
   if (int e = nk_check_launch("bn_stats_finalize")) return e;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(M * (C >> 3))), dim3(256), 0, stream, (const bf16_t*)x, mean, rstd, gamma, beta,
-                     (bf16_t*)y, M, C, slope);
-  return nk_check_launch("bn_apply");
+  return nk_ew_rows("bn_apply", stream, M, C >> 3, BnApply{(const bf16_t*)x, mean, rstd, gamma, beta, (bf16_t*)y, slope}, GAN_EW_CAP);
 }
 
 // nn.BatchNorm2d in evaluation mode (+ the LeakyReLU behind it): the running statistics as a per-channel affine map.
@@ -234,9 +225,7 @@ extern "C" int nk_batchnorm_eval(const void* x, const float* gamma, const float*
   NK_CHECK_ARG(x && gamma && beta && running_mean && running_var && y && ws && M > 0 && C > 0 && (C & 7) == 0 && slope > 0.f);
   hipLaunchKernelGGL(bn_eval_rstd_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, running_var, eps, ws, C);
   if (int e = nk_check_launch("bn_eval_rstd")) return e;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(M * (C >> 3))), dim3(256), 0, stream, (const bf16_t*)x, running_mean, ws, gamma, beta,
-                     (bf16_t*)y, M, C, slope);
-  return nk_check_launch("bn_apply (eval)");
+  return nk_ew_rows("bn_apply (eval)", stream, M, C >> 3, BnApply{(const bf16_t*)x, running_mean, ws, gamma, beta, (bf16_t*)y, slope}, GAN_EW_CAP);
 }
 
 extern "C" int nk_batchnorm_bwd(const void* dy, const void* x, const void* y, const float* gamma, const float* mean,
@@ -251,53 +240,41 @@ extern "C" int nk_batchnorm_bwd(const void* dy, const void* x, const void* y, co
   if (int e = nk_check_launch("bn_partial<1>")) return e;
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(1024), 0, stream, ws, slabs, C, sums, dgamma, dbeta, accumulate);
   if (int e = nk_check_launch("bn_bwd_finalize")) return e;
-  hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(ew_grid(M * (C >> 3))), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)x,
-                     (const bf16_t*)y, mean, rstd, gamma, sums, (bf16_t*)dx, M, C, slope);
-  return nk_check_launch("bn_bwd_dx");
+  return nk_ew_rows("bn_bwd_dx", stream, M, C >> 3,
+                    BnBwdDx{(const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)y, mean, rstd, gamma, sums, (bf16_t*)dx, M, C, slope}, GAN_EW_CAP);
 }
 
 
 // =====================================================================================================
 // LPIPS pieces (modules/losses/perceptual.py:64-228 over a VGG16 trunk): 2x2 max-pool and the per-layer distance.
 // =====================================================================================================
-// y[n][ho][wo][c] = max over the 2x2 window (H, W even).  One thread per 8 channels of an output pixel.
-__global__ void maxpool2_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int N, int H, int W, int C) {
-  const int Ho = H >> 1, Wo = W >> 1, chunks = C >> 3;
-  const long total = (long)N * Ho * Wo * chunks;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % chunks) * 8;
-    long pix = i / chunks;
-    const int wo = (int)(pix % Wo);
-    pix /= Wo;
-    const int ho = (int)(pix % Ho), n = (int)(pix / Ho);
-    const bf16_t* base = x + (((long)n * H + 2 * ho) * W + 2 * wo) * C + ch;
+// The pixel ops run over the image named in their comment; H, W, C are the INPUT's.
+// y[n][ho][wo][c] = max over the 2x2 window (H, W even).  One item per 8 channels of an output pixel.
+struct MaxPool2Fwd {
+  const bf16_t* x; bf16_t* y; int H, W, C;
+  __device__ void operator()(long i, int n, int ho, int wo, int chunk) const {
+    const bf16_t* base = x + (((long)n * H + 2 * ho) * W + 2 * wo) * C + chunk * 8;
     float a[8], b[8], c[8], d[8];
-    unpack8(*(const uint4_t*)base, a);
-    unpack8(*(const uint4_t*)(base + C), b);
-    unpack8(*(const uint4_t*)(base + (long)W * C), c);
-    unpack8(*(const uint4_t*)(base + (long)W * C + C), d);
+    ew_load(base, a);
+    ew_load(base + C, b);
+    ew_load(base + (long)W * C, c);
+    ew_load(base + (long)W * C + C, d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] = fmaxf(fmaxf(a[e], b[e]), fmaxf(c[e], d[e]));
-    *(uint4_t*)(y + i * 8) = pack8(a);
+    ew_store(y + i * 8, a);
   }
-}
-// dx: the window's gradient goes to its FIRST maximal element in scan order (as torch's max_pool2d); the rest get 0
-__global__ void maxpool2_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, bf16_t* __restrict__ dx, int N, int H,
-                                    int W, int C) {
-  const int Ho = H >> 1, Wo = W >> 1, chunks = C >> 3;
-  const long total = (long)N * Ho * Wo * chunks;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % chunks) * 8;
-    long pix = i / chunks;
-    const int wo = (int)(pix % Wo);
-    pix /= Wo;
-    const int ho = (int)(pix % Ho), n = (int)(pix / Ho);
-    const long o00 = (((long)n * H + 2 * ho) * W + 2 * wo) * C + ch;
+};
+// dx: the window's gradient goes to its FIRST maximal element in scan order (as torch's max_pool2d); the rest get 0.  One item per 8
+// channels of an OUTPUT pixel writes the four chunks of its window.
+struct MaxPool2Bwd {
+  const bf16_t *dy, *x; bf16_t* dx; int H, W, C;
+  __device__ void operator()(long i, int n, int ho, int wo, int chunk) const {
+    const long o00 = (((long)n * H + 2 * ho) * W + 2 * wo) * C + chunk * 8;
     const long offs[4] = {o00, o00 + C, o00 + (long)W * C, o00 + (long)W * C + C};
     float v[4][8], g[8], out[4][8];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) unpack8(*(const uint4_t*)(x + offs[k]), v[k]);
-    unpack8(*(const uint4_t*)(dy + i * 8), g);
+    for (int k = 0; k < 4; ++k) ew_load(x + offs[k], v[k]);
+    ew_load(dy + i * 8, g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       int best = 0;
@@ -307,59 +284,44 @@ __global__ void maxpool2_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t*
       for (int k = 0; k < 4; ++k) out[k][e] = k == best ? g[e] : 0.f;
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) *(uint4_t*)(dx + offs[k]) = pack8(out[k]);
+    for (int k = 0; k < 4; ++k) ew_store(dx + offs[k], out[k]);
   }
-}
+};
 extern "C" int nk_maxpool2x2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
   NK_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0 && (H & 1) == 0 && (W & 1) == 0);
-  hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(ew_grid((long)N * (H / 2) * (W / 2) * (C >> 3))), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (bf16_t*)y, N, H, W, C);
-  return nk_check_launch("maxpool2x2_fwd");
+  return nk_ew_pixels("maxpool2x2_fwd", stream, N, H / 2, W / 2, C >> 3, MaxPool2Fwd{(const bf16_t*)x, (bf16_t*)y, H, W, C}, GAN_EW_CAP);
 }
 extern "C" int nk_maxpool2x2_bwd(const void* dy, const void* x, void* dx, int N, int H, int W, int C, void* stream) {
   NK_CHECK_ARG(dy && x && dx && N > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0 && (H & 1) == 0 && (W & 1) == 0);
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid((long)N * (H / 2) * (W / 2) * (C >> 3))), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, N, H, W, C);
-  return nk_check_launch("maxpool2x2_bwd");
+  return nk_ew_pixels("maxpool2x2_bwd", stream, N, H / 2, W / 2, C >> 3, MaxPool2Bwd{(const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, H, W, C},
+                      GAN_EW_CAP);
 }
 
 // General k x k / stride s max pooling without padding (floor mode), for the AlexNet trunk's overlapping 3x3 / 2 pools.
-// Forward: one thread per 8 channels of an output pixel.  Backward GATHERS: one thread per 8 channels of an INPUT pixel walks the
+// Forward: one item per 8 channels of an output pixel.  Backward GATHERS: one item per 8 channels of an INPUT pixel walks the
 // (at most ceil(k/s)^2) windows that contain it, re-derives each window's first maximal element in scan order (torch's max_pool2d
 // tie rule) and adds that window's gradient when the element is this pixel -- overlapping windows need no atomics this way.
-__global__ void maxpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int N, int H, int W, int C, int k, int s, int Ho,
-                                   int Wo) {
-  const int chunks = C >> 3;
-  const long total = (long)N * Ho * Wo * chunks;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % chunks) * 8;
-    long pix = i / chunks;
-    const int wo = (int)(pix % Wo);
-    pix /= Wo;
-    const int ho = (int)(pix % Ho), n = (int)(pix / Ho);
+struct MaxPoolFwd {
+  const bf16_t* x; bf16_t* y; int H, W, C, k, s;
+  __device__ void operator()(long i, int n, int ho, int wo, int chunk) const {
+    const int ch = chunk * 8;
     float m[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
     for (int kh = 0; kh < k; ++kh)
       for (int kw = 0; kw < k; ++kw) {
         float v[8];
-        unpack8(*(const uint4_t*)(x + (((long)n * H + ho * s + kh) * W + wo * s + kw) * C + ch), v);
+        ew_load(x + (((long)n * H + ho * s + kh) * W + wo * s + kw) * C + ch, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], v[e]);
       }
-    *(uint4_t*)(y + i * 8) = pack8(m);
+    ew_store(y + i * 8, m);
   }
-}
-__global__ void maxpool_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, bf16_t* __restrict__ dx, int N, int H,
-                                   int W, int C, int k, int s, int Ho, int Wo) {
-  const int chunks = C >> 3;
-  const long total = (long)N * H * W * chunks;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ch = (int)(i % chunks) * 8;
-    long pix = i / chunks;
-    const int w = (int)(pix % W);
-    pix /= W;
-    const int h = (int)(pix % H), n = (int)(pix / H);
+};
+struct MaxPoolBwd {
+  const bf16_t *dy, *x; bf16_t* dx; int H, W, C, k, s, Ho, Wo;
+  __device__ void operator()(long i, int n, int h, int w, int chunk) const {
+    const int ch = chunk * 8;
     float g[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) g[e] = 0.f;
@@ -374,33 +336,30 @@ __global__ void maxpool_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* 
         for (int kh = 0; kh < k; ++kh)
           for (int kw = 0; kw < k; ++kw) {
             float v[8];
-            unpack8(*(const uint4_t*)(x + (((long)n * H + ho * s + kh) * W + wo * s + kw) * C + ch), v);
+            ew_load(x + (((long)n * H + ho * s + kh) * W + wo * s + kw) * C + ch, v);
 #pragma unroll
             for (int e = 0; e < 8; ++e)
               if (v[e] > best[e] || arg[e] < 0) { best[e] = v[e]; arg[e] = kh * k + kw; }
           }
         const int mine = (h - ho * s) * k + (w - wo * s);
         float d[8];
-        unpack8(*(const uint4_t*)(dy + (((long)n * Ho + ho) * Wo + wo) * C + ch), d);
+        ew_load(dy + (((long)n * Ho + ho) * Wo + wo) * C + ch, d);
 #pragma unroll
         for (int e = 0; e < 8; ++e) g[e] += arg[e] == mine ? d[e] : 0.f;
       }
-    *(uint4_t*)(dx + i * 8) = pack8(g);
+    ew_store(dx + i * 8, g);
   }
-}
+};
 extern "C" int nk_maxpool_fwd(const void* x, void* y, int N, int H, int W, int C, int k, int s, void* stream) {
   NK_CHECK_ARG(x && y && N > 0 && C > 0 && (C & 7) == 0 && k > 0 && s > 0 && H >= k && W >= k);
   const int Ho = (H - k) / s + 1, Wo = (W - k) / s + 1;
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(ew_grid((long)N * Ho * Wo * (C >> 3))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (bf16_t*)y, N, H, W, C, k, s, Ho, Wo);
-  return nk_check_launch("maxpool_fwd");
+  return nk_ew_pixels("maxpool_fwd", stream, N, Ho, Wo, C >> 3, MaxPoolFwd{(const bf16_t*)x, (bf16_t*)y, H, W, C, k, s}, GAN_EW_CAP);
 }
 extern "C" int nk_maxpool_bwd(const void* dy, const void* x, void* dx, int N, int H, int W, int C, int k, int s, void* stream) {
   NK_CHECK_ARG(dy && x && dx && N > 0 && C > 0 && (C & 7) == 0 && k > 0 && s > 0 && H >= k && W >= k);
   const int Ho = (H - k) / s + 1, Wo = (W - k) / s + 1;
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(ew_grid((long)N * H * W * (C >> 3))), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                     (const bf16_t*)x, (bf16_t*)dx, N, H, W, C, k, s, Ho, Wo);
-  return nk_check_launch("maxpool_bwd");
+  return nk_ew_pixels("maxpool_bwd", stream, N, H, W, C >> 3,
+                      MaxPoolBwd{(const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, H, W, C, k, s, Ho, Wo}, GAN_EW_CAP);
 }
 
 // One LPIPS layer: per pixel, unit-normalise both feature vectors over the channels (x / (||x|| + eps)), square the difference,

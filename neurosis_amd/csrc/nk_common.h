@@ -25,6 +25,8 @@ typedef __attribute__((ext_vector_type(2))) unsigned int uint2_t;
     }                                                                             \
   } while (0)
 
+static inline bool nk_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }     // for the entry points whose kernels move 16 bytes per access
+
 void nk_set_error(const char* file, int line, const char* what);
 int nk_check_launch(const char* what);
 // launch log (test hook, errors.hip): 0 = off, 1 = logging, 3 = plan-only (the tile engine, the attention and the norm / column-sum entry points log their plan and launch nothing)
@@ -126,6 +128,12 @@ __device__ __forceinline__ float dgelu_erf(float x) {
   float cdf, pdf;
   normal_cdf_pdf(x, cdf, pdf);
   return cdf + x * pdf;
+}
+// "gelu_new", the tanh form 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) of T5 v1.1 / ByT5.
+// 0.5 (1 + tanh z) = 1 / (1 + exp(-2 z)): one exponential, and no cancellation where tanh z is near -1
+__device__ __forceinline__ float gelu_tanh(float x) {
+  const float z2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);      // 2 sqrt(2 / pi) (x + 0.044715 x^3)
+  return x / (1.0f + __expf(-z2));
 }
 
 // ---- for the entry points that run a plan of norm_plan.h (norm.hip, elementwise.hip) ----------------------------------------------------------

@@ -73,7 +73,6 @@ __global__ __launch_bounds__(256) void resample_cols_kernel(const float* __restr
 }
 
 static bool rs_rows_first(int H, int W, int OH, int OW) { return (long)OH * W <= (long)H * OW; }
-static bool rs_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" long nk_resample_ws_floats(long P, int H, int W, int OH, int OW) {
   if (P < 1 || H < 1 || W < 1 || OH < 1 || OW < 1) return 0;
@@ -82,7 +81,7 @@ extern "C" long nk_resample_ws_floats(long P, int H, int W, int OH, int OW) {
 
 static void rs_rows(const float* in, float* out, const int* start, const int* count, const float* wt, int taps, long P, int Hin, int Hout, int Wd,
                     hipStream_t stream) {
-  if (Wd % 4 == 0 && rs_aligned16(in) && rs_aligned16(out)) {
+  if (Wd % 4 == 0 && nk_aligned16(in) && nk_aligned16(out)) {
     const long total = P * Hout * (Wd / 4);
     hipLaunchKernelGGL(resample_rows_kernel<float4_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, in, out, start, count, wt, taps,
                        total, Hin, Hout, Wd / 4);

@@ -12,7 +12,7 @@
 #include "../../include/neurosis_hip.h"
 
 #define SMP_THREADS 256
-static inline int smp_blocks(long n) {
+static inline int smp_blocks(long n) {      // (not nk_ew_grid of nk_ew.h: the same block, but this cap is 65 535 where the map core's is 8 192)
   long b = (n + SMP_THREADS - 1) / SMP_THREADS;
   return (int)(b < 1 ? 1 : (b > 65535 ? 65535 : b));
 }

@@ -16,7 +16,7 @@ from tests import adm_ref as R
 from tests.golden.fixture_io import load_fixture
 from tests.golden.make_golden import BLOCK_SAMPLE_ROWS, VAE_TINY, block_inputs, block_upstream, synth_state_dict
 from tests.golden.make_golden_adm import ADM_BLOCK_CASES, CONV_SAMPLE_CIN, unet_inputs
-from tests.util import assert_close, bf16_round, check_grad_cosines, cosine, rel_err
+from tests.util import _call_into, assert_close, bf16_round, check_grad_cosines, cosine, rel_err
 
 pytestmark = pytest.mark.gpu
 G = Path(__file__).resolve().parent / "golden"
@@ -162,24 +162,6 @@ def test_modulated_groupnorm_is_reproducible_and_accumulates(ops):
 # 2. the resamplers
 # ------------------------------------------------------------------------------------------------
 RS_SHAPES = [(2, 8, 7, 10), (1, 320, 16, 16), (2, 64, 5, 5)]
-SENTINEL = 0x7FC1        # a NaN bit pattern no kernel writes (as int16)
-
-
-def _guarded(rows, C):
-    """a token matrix with 64 guard rows on each side, all filled with the sentinel: (whole buffer, the view a kernel writes)"""
-    buf = torch.full((rows + 128, C), SENTINEL, dtype=torch.int16, device="cuda")
-    return buf, buf[64:64 + rows].view(BF)
-
-
-def _call_into(ops, name, dst_rows, C, *args):
-    """run C-ABI entry point `name` with its destination placed between sentinel rows; returns the destination, guards checked"""
-    buf, dst = _guarded(dst_rows, C)
-    ptrs = [a.data_ptr() if torch.is_tensor(a) else a for a in args]
-    ops.call(name, *ptrs[:1], dst.data_ptr(), *ptrs[1:], ops._stream())
-    torch.cuda.synchronize()
-    assert bool((buf[:64] == SENTINEL).all()) and bool((buf[64 + dst_rows:] == SENTINEL).all()), f"{name} wrote outside its destination"
-    assert not bool((dst.view(torch.int16) == SENTINEL).any()), f"{name} left part of its destination unwritten"
-    return dst.clone()
 
 
 @pytest.mark.parametrize("kind", ["integers", "randn"])

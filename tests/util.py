@@ -36,6 +36,27 @@ def assert_close(got, ref, tol, name=""):
     assert c >= 1.0 - 10 * tol * tol - 1e-4, f"{name}: cosine {c:.6f} too low"
 
 
+SENTINEL = 0x7FC1        # a NaN bit pattern no kernel writes (as int16)
+
+
+def _guarded(rows, C):
+    """a token matrix with 64 guard rows on each side, all filled with the sentinel: (whole buffer, the view a kernel writes)"""
+    buf = torch.full((rows + 128, C), SENTINEL, dtype=torch.int16, device="cuda")
+    return buf, buf[64:64 + rows].view(torch.bfloat16)
+
+
+def _call_into(ops, name, dst_rows, C, *args, dst_pos=1):
+    """run C-ABI entry point `name` with its destination (argument number `dst_pos`) placed between sentinel rows; returns the destination,
+    guards checked"""
+    buf, dst = _guarded(dst_rows, C)
+    ptrs = [a.data_ptr() if torch.is_tensor(a) else a for a in args]
+    ops.call(name, *ptrs[:dst_pos], dst.data_ptr(), *ptrs[dst_pos:], ops._stream())
+    torch.cuda.synchronize()
+    assert bool((buf[:64] == SENTINEL).all()) and bool((buf[64 + dst_rows:] == SENTINEL).all()), f"{name} wrote outside its destination"
+    assert not bool((dst.view(torch.int16) == SENTINEL).any()), f"{name} left part of its destination unwritten"
+    return dst.clone()
+
+
 WORST_COSINES = {}     # test label -> (worst cosine over >= 2-D parameters, its name, worst over 1-D parameters, its name): printed by the tests
 
 

@@ -5,7 +5,7 @@ usage: python tools/bench_adm.py [--steps 10] [--warmup 4] [--batch 4] [--plain]
 --plain: the same network with use_scale_shift_norm=False, resblock_updown=False (the SD-style blocks), for comparison.
 Under `rocprofv3 --kernel-trace -- python tools/bench_adm.py ...` followed by tools/kstats.py the per-kernel shares come out; the new
 kernels are gn_apply_kernel<true>, gn_bwd_stats_kernel<true>, gn_bwd_apply_kernel<true>, colpart_reduce_mod_kernel, gn_dmod_kernel,
-avgpool2x_fwd_kernel, avgpool2x_bwd_kernel and up2_fwd_kernel."""
+nk_ew_pixels_kernel<AvgPool2xFwd>, <AvgPool2xBwd> and <Up2Fwd>."""
 import argparse
 import json
 import os

@@ -46,7 +46,7 @@ def run():
 def report(db_path: str):
     db = sqlite3.connect(db_path)
     rows = db.execute("select name, end - start from kernels order by start").fetchall()
-    by = {"dropout": [d for n, d in rows if "dropout_kernel" in n], "silu": [d for n, d in rows if "silu_fwd_kernel" in n]}
+    by = {"dropout": [d for n, d in rows if "dropout_kernel" in n], "silu": [d for n, d in rows if "SiluFwd" in n]}
     for k, v in by.items():
         assert len(v) == len(SHAPES) * (WARM + N), (k, len(v))
     for i, (r, c) in enumerate(SHAPES):

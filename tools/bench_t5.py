@@ -8,7 +8,7 @@
     python tools/bench_t5.py --db OUT/t5_results.db xxl 256
         the per-kernel split of one call from a kernel trace taken in a run of its own (one stream, launched from Python: the kernels run
         one after the other): ms per call by kernel, the GEMMs' achieved TFLOP/s (their FLOPs from the shapes over their kernel time) and
-        the share of the three T5 kernels (rms_fwd_kernel, attn_fwd_kernel<relbias>, gated_gelu_tanh_kernel).  The subject runs 1 + CALLS
+        the share of the three T5 kernels (rms_fwd_kernel, attn_fwd_kernel<relbias>, nk_ew_rows_kernel<GatedGeluTanh>).  The subject runs 1 + CALLS
         calls; the split is taken from the first RMSNorm launch of the second call on (weight preparation happens in the first), so the
         second call's embedding gather and cast, two launches of a few microseconds, are left out.
 
@@ -28,7 +28,7 @@ SHAPES = {
     "xxl": dict(vocab_size=32128, d_model=4096, d_kv=64, d_ff=10240, num_layers=24, num_heads=64, feed_forward_proj="gated-gelu"),
 }
 BATCH, WARM, RUNS, CALLS = 4, 3, 15, 5
-NEW_KERNELS = ("rms_fwd_kernel", "attn_fwd_kernel", "gated_gelu_tanh_kernel")
+NEW_KERNELS = ("rms_fwd_kernel", "attn_fwd_kernel", "GatedGeluTanh")
 
 
 def flops(cfg: dict, B: int, L: int) -> dict:
