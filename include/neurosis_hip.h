@@ -404,6 +404,29 @@ long nk_vq_quantize_ws_floats(long N);
 int nk_vq_quantize(const long long* idx, const float* codebook, const float* z, long ldz, float* zq, float* sumsq, float* ws, long N, int D,
                    int n_e, int HW, void* stream);
 
+/* Gumbel-softmax quantizer bottleneck (modules/autoencoding/regularizers/quantize.py:59-160, GumbelQuantizer.forward :114-148),
+ * csrc/gumbel.hip.  No float atomics: every result is bit-identical from run to run.  z [N][h] fp32 with row stride ldz, 1 <= h <=
+ * NK_VQ_MAX_D, 1 <= n <= NK_VQ_MAX_CODES, N < 2^31, refused with a message otherwise.
+ * logits:      logits[i][j] = fadd_rn(sum_k z_ik w_jk, bias_j) into fp32 [N][n] with row stride ldl; w [n][h] dense (the 1x1 conv's weight).  The
+ *              dot product is the fp32 fma chain in rising k from 0 (on v_mfma_f32_16x16x4_f32, as nk_vq_search): the forward decides an index.
+ * noise:       g[rows][cols] dense fp32, a pure function of (token, site, e = i * cols + j): Philox4x32-10, one call per 4 consecutive e,
+ *              counter (e / 4 low, e / 4 high, site, step low word), key (seed low, seed high ^ 0x47554D42); element e % 4 takes word w,
+ *              u = (2 (w >> 9) + 1) 2^-24, g = -logf(-logf(u)).  {seed, step} are read from device memory at `token` (nk_dropout_draw).
+ * softmax_fwd: a_j = fmul_rn(fadd_rn(l_j, g_j), inv_tau), g from `noise` [N][n] dense or (noise NULL) from the generator above with `token`,
+ *              `site` -- bitwise the same either way; y = softmax(a) as bf16 [N][n] dense; idx[i] = argmax_j a_j (lowest index among equal
+ *              scores, a NaN never taken); kl[0] = (1 / N) sum_i sum_j q_j log(q_j n + 1e-10), q = softmax(l), summed in a fixed order.
+ *              ws: nk_gumbel_softmax_ws_floats(N) floats (the rows' KL terms).
+ * softmax_bwd: in place on bf16 G [N][n] dense (the gradient with respect to the soft one-hot): G_j <- inv_tau y_j (G_j - sum_k G_k y_k) +
+ *              (w_kl / N) q_j (h_j - sum_k q_k h_k), h_j = log(q_j n + 1e-10) + q_j n / (q_j n + 1e-10), q recomputed from the logits, fp32
+ *              sums in a fixed order: the gradient of <G, y> + w_kl * kl with respect to the logits.
+ * inv_tau and w_kl are launch arguments (a captured graph would freeze them). */
+int nk_gumbel_logits(const float* z, long ldz, const float* w, const float* bias, float* logits, long ldl, long N, int h, int n, void* stream);
+int nk_gumbel_noise(float* g, long rows, int cols, const void* token, int site, void* stream);
+long nk_gumbel_softmax_ws_floats(long N);
+int nk_gumbel_softmax_fwd(const float* logits, long ldl, const float* noise, const void* token, int site, float inv_tau, void* y,
+                          long long* idx, float* kl, float* ws, long N, int n, void* stream);
+int nk_gumbel_softmax_bwd(const float* logits, long ldl, const void* y, void* G, float inv_tau, float w_kl, long N, int n, void* stream);
+
 /* Separable banded resampler on dense fp32 planes, csrc/resample.hip: y[p] = Wv . x[p] . Wh^T for p < P, x [P][H][W] -> y [P][OH][OW].
  * With the tables of F.interpolate(mode="bicubic", antialias=True) it is the resize_input / resize_target step of the autoencoder losses
  * (modules/autoencoding/losses/vae_lpips_discr.py:104-107, :326-329); called with the transposed tables ([H x OH], [W x OW]) and the sizes

@@ -95,6 +95,10 @@ SIGNATURES: dict[str, list] = {
     "nk_vq_search": [vp, i64, vp, vp, vp, i64, i32, i32, vp],
     "nk_vq_code_stats": [vp, vp, i64, vp, vp, i64, i32, i32, vp],
     "nk_vq_quantize": [vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp],
+    "nk_gumbel_logits": [vp, i64, vp, vp, vp, i64, i64, i32, i32, vp],
+    "nk_gumbel_noise": [vp, i64, i32, vp, i32, vp],
+    "nk_gumbel_softmax_fwd": [vp, i64, vp, vp, i32, f32, vp, vp, vp, vp, i64, i32, vp],
+    "nk_gumbel_softmax_bwd": [vp, i64, vp, vp, f32, f32, i64, i32, vp],
     "nk_resample_planes": [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i64, i32, i32, i32, i32, vp],
     "nk_leaky_relu_fwd": [vp, vp, i64, f32, vp],
     "nk_leaky_relu_bwd": [vp, vp, vp, i64, f32, vp],
@@ -160,6 +164,7 @@ SIZE_QUERIES: dict[str, list] = {
     "nk_attention_bwd_ws_floats": [adp],
     "nk_vq_search_ws_floats": [i64, i32],
     "nk_vq_quantize_ws_floats": [i64],
+    "nk_gumbel_softmax_ws_floats": [i64],
     "nk_resample_ws_floats": [i64, i32, i32, i32, i32],
     "nk_adafactor_tensor_bytes": [],
     "nk_came_tensor_bytes": [],

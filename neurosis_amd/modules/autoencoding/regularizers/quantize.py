@@ -12,8 +12,9 @@ Besides forward(z) -> (z_q, dict) the classes speak the engine's protocol: regul
 bwd(dz, weight) -> dz_e the gradient of <dz, z_q> + weight * log[loss_key] with respect to z_e (z_q is the straight-through
 z_e + sg[z_q - z_e]); VectorQuantizer's bwd also writes the codebook gradient into the parameter's gradient slot.
 
-Not built (refused by name): remap= / unknown_index="extra" (index remapping), embedding_weight_norm=True; GumbelQuantizer and
-VectorQuantizerWithInputProjection do not exist here.
+Not built (refused by name): remap= / unknown_index="extra" (index remapping), embedding_weight_norm=True; VectorQuantizerWithInputProjection
+does not exist here.  The reference's third class of this file, GumbelQuantizer, lives in .gumbel and resolves as
+neurosis_amd.modules.autoencoding.regularizers.GumbelQuantizer, the path the reference's configs name; it is not an attribute of this module.
 """
 from __future__ import annotations
 

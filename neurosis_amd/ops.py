@@ -1492,6 +1492,114 @@ def vq_quantize(idx: Tensor, codebook: Tensor, z: Tensor, hw: int = 1, out: Opti
 
 
 # ------------------------------------------------------------------------------------------------
+# Gumbel-softmax quantizer (csrc/gumbel.hip)
+# ------------------------------------------------------------------------------------------------
+def _gumbel_token(token: Tensor, device, op: str) -> Tensor:
+    if token.dtype != torch.int64 or token.numel() != 2 or token.device != device or not token.is_contiguous():
+        raise ValueError(f"{op}: token must be the int64 [2] tensor of ops.dropout_draw() on the data's device")
+    return token
+
+
+def _gumbel_bf16(t: Tensor, N: int, n: int, name: str, op: str) -> Tensor:
+    if not t.is_cuda or t.dtype != BF16 or tuple(t.shape) != (N, n) or not t.is_contiguous():
+        raise ValueError(f"{op}: {name} must be a dense bf16 [{N}, {n}] device tensor, got {tuple(t.shape)} {t.dtype} {t.stride()}")
+    return t
+
+
+def gumbel_logits(z: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
+    """logits [N, n] fp32 = z [N, h] @ weight [n, h]^T + bias [n] (nk_gumbel_logits: exact fp32 on the matrix pipe, the fma chain in rising k
+    and one rounded add of the bias; a column slice of a wider z is taken as it is)."""
+    z, weight = _vq_rows(z, "z", "gumbel_logits"), _vq_rows(weight, "weight", "gumbel_logits").contiguous()
+    N, h = z.shape
+    n = weight.shape[0]
+    if weight.shape[1] != h or not bias.is_cuda or bias.dtype != torch.float32 or tuple(bias.shape) != (n,):
+        raise ValueError(f"gumbel_logits: z [N, {h}] against weight {tuple(weight.shape)} and bias {tuple(bias.shape)} {bias.dtype}")
+    logits = torch.empty(N, n, dtype=torch.float32, device=z.device)
+    call("nk_gumbel_logits", z.data_ptr(), z.stride(0), weight.data_ptr(), bias.contiguous().data_ptr(), logits.data_ptr(), n, N, h, n, _stream())
+    return logits
+
+
+def gumbel_noise(rows: int, cols: int, site: int, token: Tensor) -> Tensor:
+    """g [rows, cols] fp32: the Gumbel noise of (token, site), a pure function of the logical element index (nk_gumbel_noise;
+    tests/gumbel_reference.py restates it)."""
+    if not token.is_cuda:
+        raise NotImplementedError("gumbel_noise: the token is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    token = _gumbel_token(token, token.device, "gumbel_noise")
+    if rows < 0 or cols < 1 or site < 0:
+        raise ValueError(f"gumbel_noise: rows >= 0, cols >= 1 and site >= 0, got {rows}, {cols}, {site}")
+    g = torch.empty(rows, cols, dtype=torch.float32, device=token.device)
+    call("nk_gumbel_noise", g.data_ptr(), int(rows), int(cols), token.data_ptr(), int(site), _stream())
+    return g
+
+
+def _inv_tau(tau: float, op: str) -> float:
+    tau = float(tau)
+    if not tau > 0.0:
+        raise ValueError(f"{op}: the temperature must be positive, got {tau!r}")
+    return 1.0 / tau
+
+
+def gumbel_softmax_fwd(logits: Tensor, tau: float, *, noise: Optional[Tensor] = None, token: Optional[Tensor] = None, site: int = 0):
+    """(y, idx, kl): y = softmax((logits + g) / tau) as bf16 [N, n], idx [N] int64 its argmax (lowest index among equal scores), kl the device
+    scalar mean_i sum_j q_j log(q_j n + 1e-10) with q = softmax(logits).  g is `noise` (fp32 [N, n]) or, with noise=None, the noise of
+    (token, site) generated inside the kernel -- bitwise what gumbel_noise(N, n, site, token) would have passed."""
+    logits = _vq_rows(logits, "logits", "gumbel_softmax_fwd")
+    N, n = logits.shape
+    if (noise is None) == (token is None):
+        raise ValueError("gumbel_softmax_fwd: exactly one of noise= and token=")
+    if noise is not None:
+        if not noise.is_cuda or noise.dtype != torch.float32 or tuple(noise.shape) != (N, n):
+            raise ValueError(f"gumbel_softmax_fwd: noise must be an fp32 [{N}, {n}] device tensor, got {tuple(noise.shape)} {noise.dtype}")
+        noise = noise.contiguous()
+    else:
+        token = _gumbel_token(token, logits.device, "gumbel_softmax_fwd")
+    y = torch.empty(N, n, dtype=BF16, device=logits.device)
+    idx = torch.empty(N, dtype=torch.int64, device=logits.device)
+    kl = torch.empty((), dtype=torch.float32, device=logits.device)
+    ws = _ws(query("nk_gumbel_softmax_ws_floats", N), logits.device)
+    call("nk_gumbel_softmax_fwd", logits.data_ptr(), logits.stride(0), _p(noise), _p(token), int(site), _inv_tau(tau, "gumbel_softmax_fwd"),
+         y.data_ptr(), idx.data_ptr(), kl.data_ptr(), ws.data_ptr(), N, n, _stream())
+    return y, idx, kl
+
+
+def gumbel_softmax_bwd(logits: Tensor, y: Tensor, G: Tensor, tau: float, w_kl: float) -> Tensor:
+    """d [N, n] bf16, written IN PLACE over G: the gradient of <G, y> + w_kl * kl with respect to the logits, y and kl those of
+    gumbel_softmax_fwd (nk_gumbel_softmax_bwd)."""
+    logits = _vq_rows(logits, "logits", "gumbel_softmax_bwd")
+    N, n = logits.shape
+    y, G = _gumbel_bf16(y, N, n, "y", "gumbel_softmax_bwd"), _gumbel_bf16(G, N, n, "G", "gumbel_softmax_bwd")
+    call("nk_gumbel_softmax_bwd", logits.data_ptr(), logits.stride(0), y.data_ptr(), G.data_ptr(), _inv_tau(tau, "gumbel_softmax_bwd"), float(w_kl),
+         N, n, _stream())
+    return G
+
+
+GUMBEL_WIDTH_RULE = "a multiple of 8 (the 16-byte operand rule of the bf16 GEMMs behind the gradients: ops.gemm_nt / gemm_nn / gemm_tn_f32)"
+
+
+def gumbel_quantize(rows: Tensor, W: Tensor, bias: Tensor, E: Tensor, Wb: Tensor, Eb: Tensor, tau: float, hard: bool, *,
+                    noise: Optional[Tensor] = None, token: Optional[Tensor] = None, site: int = 0):
+    """The Gumbel-softmax bottleneck on latent rows [N, h] fp32: W [n, h], bias [n], E [n, d] the fp32 projection and codebook, Wb / Eb their
+    bf16 copies.  Returns (z_q [N, d] fp32, idx [N], kl, logits, y, bwd): hard -> z_q = E[idx] (the straight-through one-hot), else
+    z_q = y @ E (bf16 operands, fp32 accumulation).  bwd(dz_rows fp32 [N, d], w_kl) -> (d_rows bf16 [N, h], d bf16 [N, n], dz bf16 [N, d]):
+    the gradient of <dz, z_q> + w_kl * kl with respect to the rows and to the logits, and the bf16 copy of dz the caller's weight
+    gradients read (dW = d^T rows, db = colsum d, dE = y^T dz or the per-code sum of dz)."""
+    N, d = rows.shape[0], E.shape[1]
+    logits = gumbel_logits(rows, W, bias)
+    y, idx, kl = gumbel_softmax_fwd(logits, tau, noise=noise, token=token, site=site)
+    if hard:
+        z_q, _ = vq_quantize(idx, E, torch.zeros(N, d, dtype=torch.float32, device=rows.device))
+    else:
+        z_q = gemm_nn(y, Eb).float()
+
+    def bwd(dz_rows: Tensor, w_kl: float):
+        dzb = cast_bf16(dz_rows)
+        dl = gumbel_softmax_bwd(logits, y, gemm_nt(dzb, Eb), tau, w_kl)
+        return gemm_nn(dl, Wb), dl, dzb
+
+    return z_q, idx, kl, logits, y, bwd
+
+
+# ------------------------------------------------------------------------------------------------
 # antialiased bicubic resize (csrc/resample.hip; host tables in neurosis_amd/resample.py)
 # ------------------------------------------------------------------------------------------------
 def _resize_planes(x: Tensor, out_hw, transposed: bool, op: str) -> Tensor:

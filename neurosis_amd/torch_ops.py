@@ -953,6 +953,94 @@ vq_quantize.register_autograd(_vq_quantize_bwd, setup_context=_vq_quantize_setup
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# Gumbel-softmax quantizer (csrc/gumbel.hip): exact-fp32 logits, counter-based noise, the row passes, and the whole bottleneck
+# ---------------------------------------------------------------------------------------------------------------
+@_op("gumbel_logits")
+def gumbel_logits(z: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
+    """logits [N, n] fp32 = z [N, h] @ weight [n, h]^T + bias, the fp32 fma chain in k order (not differentiable here: gumbel_quantize is)"""
+    return ops.gumbel_logits(z, weight, bias)
+
+
+@gumbel_logits.register_fake
+def _(z, weight, bias):
+    return z.new_empty(z.shape[0], weight.shape[0])
+
+
+@_op("gumbel_noise")
+def gumbel_noise(rows: int, cols: int, site: int, token: Tensor) -> Tensor:
+    """g [rows, cols] fp32: the Gumbel noise of (token, site); token the int64 [2] {seed, step} tensor of neurosis_amd.ops.dropout_draw()"""
+    return ops.gumbel_noise(rows, cols, site, token)
+
+
+@gumbel_noise.register_fake
+def _(rows, cols, site, token):
+    return token.new_empty(rows, cols, dtype=torch.float32)
+
+
+@_op("gumbel_softmax_fwd")
+def gumbel_softmax_fwd(logits: Tensor, tau: float, noise: Optional[Tensor] = None, token: Optional[Tensor] = None, site: int = 0) -> Tuple[Tensor, Tensor, Tensor]:
+    """(y bf16 [N, n], idx int64 [N], kl scalar) of softmax((logits + g) / tau), g = noise or the generator's under (token, site)"""
+    return ops.gumbel_softmax_fwd(logits, tau, noise=noise, token=token, site=site)
+
+
+@gumbel_softmax_fwd.register_fake
+def _(logits, tau, noise=None, token=None, site=0):
+    return logits.new_empty(logits.shape, dtype=BF16), logits.new_empty(logits.shape[0], dtype=torch.int64), logits.new_empty(())
+
+
+@_op("gumbel_softmax_bwd")
+def gumbel_softmax_bwd(logits: Tensor, y: Tensor, G: Tensor, tau: float, w_kl: float) -> Tensor:
+    """d [N, n] bf16: the gradient of <G, y> + w_kl * kl with respect to the logits (G is left untouched here; ops.gumbel_softmax_bwd works in place)"""
+    return ops.gumbel_softmax_bwd(logits, y, G.clone(), tau, w_kl)
+
+
+@gumbel_softmax_bwd.register_fake
+def _(logits, y, G, tau, w_kl):
+    return torch.empty_like(G, memory_format=torch.contiguous_format)
+
+
+@_op("gumbel_quantize")
+def gumbel_quantize(z: Tensor, proj_w: Tensor, proj_b: Tensor, embed: Tensor, noise: Tensor, tau: float, hard: bool,
+                    kl_weight: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """(z_q [N, d] fp32, loss, idx [N]) of GumbelQuantizer on latent rows z [N, h] fp32: proj_w [n, h], proj_b [n], embed [n, d] fp32, noise
+    [N, n] fp32 Gumbel values; loss = kl_weight * KL.  Differentiable in z, proj_w, proj_b and embed (bf16 GEMM gradients)."""
+    z_q, idx, kl, _, _, _ = ops.gumbel_quantize(z.contiguous(), proj_w, proj_b, embed, ops.cast_bf16(proj_w), ops.cast_bf16(embed), tau, hard, noise=noise)
+    return z_q, kl_weight * kl, idx
+
+
+@gumbel_quantize.register_fake
+def _(z, proj_w, proj_b, embed, noise, tau, hard, kl_weight):
+    return z.new_empty(z.shape[0], embed.shape[1]), z.new_empty(()), z.new_empty(z.shape[0], dtype=torch.int64)
+
+
+def _gumbel_quantize_setup(ctx, inputs, output):
+    z, proj_w, proj_b, embed, noise, ctx.tau, ctx.hard, ctx.kl_weight = inputs
+    ctx.save_for_backward(z, proj_w, proj_b, embed, noise, output[2])
+
+
+def _gumbel_quantize_bwd(ctx, d_zq, d_loss, d_idx):
+    """the forward is run again from the saved inputs (same noise, same bits), then the closure's backward"""
+    z, proj_w, proj_b, embed, noise, idx = ctx.saved_tensors
+    z = z.contiguous()
+    n = proj_w.shape[0]
+    _, _, _, _, y, bwd = ops.gumbel_quantize(z, proj_w, proj_b, embed, ops.cast_bf16(proj_w), ops.cast_bf16(embed), ctx.tau, ctx.hard, noise=noise)
+    dz_rows = d_zq.float().contiguous()
+    d_rows, dl, dzb = bwd(dz_rows, float(d_loss) * ctx.kl_weight)
+    dW = torch.empty_like(proj_w)
+    db = torch.empty_like(proj_b)
+    ops.gemm_tn_f32(dl, ops.cast_bf16(z), dW, False, dbias=db)
+    if ctx.hard:
+        dE = ops.vq_code_stats(idx, dz_rows, n)[1]
+    else:
+        dE = torch.empty_like(embed)
+        ops.gemm_tn_f32(y, dzb, dE, False)
+    return d_rows.float(), dW, db, dE, None, None, None, None
+
+
+gumbel_quantize.register_autograd(_gumbel_quantize_bwd, setup_context=_gumbel_quantize_setup)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # antialiased bicubic resize (csrc/resample.hip): fp32 NCHW planes, forward and adjoint on one banded kernel
 # ---------------------------------------------------------------------------------------------------------------
 @_op("resize_bicubic_aa")
@@ -996,4 +1084,5 @@ resize_bicubic_aa_bwd.register_autograd(lambda ctx, dx: (torch.ops.neurosis_hip.
 OPS = ("resize_bicubic_aa", "resize_bicubic_aa_bwd", "vq_search", "vq_code_stats", "vq_quantize", "groupnorm_mod_fwd", "groupnorm_mod_bwd", "groupnorm_mod", "upsample2x_nearest", "avgpool2x", "avgpool2x_bwd", "dropout", "cat_channels", "split_channels", "upsample2x_nearest_bwd", "upsample2x_nearest_conv", "edm_prepare", "edm_prepare_cat", "sample_prepare_cat", "edm_loss_fwd", "edm_loss_bwd", "edm_loss",
        "flat_allreduce_start", "flat_allreduce_wait", "conv2d_fwd_stats", "linear_dgrad_geglu", "linear_fwd_geglu", "linear_fwd", "linear_dgrad", "linear_wgrad", "colsum", "linear", "layernorm_fwd", "layernorm_bwd", "layernorm", "groupnorm_silu_fwd",
        "groupnorm_silu_bwd", "groupnorm_silu", "geglu_fwd", "geglu_bwd", "geglu", "attention_fwd", "attention_bwd", "attention", "conv2d_fwd",
-       "conv2d_dgrad", "conv2d_wgrad", "conv2d", "timestep_embedding", "nchw_to_nlc", "nlc_to_nchw")
+       "conv2d_dgrad", "conv2d_wgrad", "conv2d", "timestep_embedding", "nchw_to_nlc", "nlc_to_nchw", "gumbel_logits", "gumbel_noise", "gumbel_softmax_fwd",
+       "gumbel_softmax_bwd", "gumbel_quantize")
