@@ -555,6 +555,35 @@ typedef struct NkAdamW8bitArgs {
 long nk_adamw8bit_tensor_bytes(void);
 int nk_adamw8bit_step(const NkAdamW8bitArgs* args, void* stream);
 
+/* Frozen DreamSim ViT towers (neurosis_amd/csrc/vit.hip): what is not a transformer layer.
+ * nk_vit_patchify: x fp32 NCHW [N, 3, H, W] (H, W multiples of p, p % 8 == 0) -> rows bf16 [N * (H/p) * (W/p), 3 p p], row = (n, py, px),
+ * column = (c, ky, kx) -- nn.Conv2d's weight order, so the patch embedding is rows @ proj.weight.view(E, 3 p p)^T.  `affine` is a HOST array of
+ * 8 floats {a_0, a_1, a_2, b_0, b_1, b_2, lo, hi}: each value is a_c * clamp(x, lo, hi) + b_c, product and sum rounded separately.
+ * nk_vit_patchify_bwd is its adjoint: dx fp32 NCHW (+)= a_c * drows where lo <= x <= hi, zero where the forward clamped; accumulate = 1 adds to
+ * dx.  One writer per pixel, no atomics.
+ * nk_vit_tokens: tokens FP32 [N (Np + 1), E] (the towers' residual stream is fp32); row 0 of a sample = cls + pos[0], row 1 + i = patches row i + pos[1 + i] (cls [E], pos [Np + 1, E]
+ * fp32, E % 8 == 0).  nk_vit_tokens_bwd: dpatches bf16 [N Np, E] = dtokens (bf16) without the cls rows.
+ * nk_vit_add_ln, the seam between the fp32 stream x [M, E] and the bf16 GEMMs: x += branch (bf16 [M, E], or NULL) in place; then, unless gamma
+ * is NULL, y = LayerNorm(x) gamma + beta as bf16 (y_f32 = 0) or fp32 (1) with mean / rstd [M] written; xb (or NULL) receives x rounded to bf16,
+ * what nk_layernorm_bwd_dx reads in the backward.  E <= 2048.
+ * nk_dreamsim_head_fwd: f fp32 [2, B, Dz] -> d [B] = 1 - cosine_similarity(z_0, z_1, eps), z_j = f_j / |f_j| - mean(f_j / |f_j|).
+ * nk_dreamsim_head_bwd: df1 [B, Dz] = upstream_b * d d_b / d f[1] (f[0] gets no gradient).  fp32, fixed-order sums (nk_reduce.h). */
+int nk_vit_patchify(const float* x, void* rows, const float* affine, int N, int H, int W, int p, void* stream);
+int nk_vit_patchify_bwd(const void* drows, const float* x, float* dx, const float* affine, int N, int H, int W, int p, int accumulate, void* stream);
+int nk_vit_tokens(const void* patches, const float* cls, const float* pos, void* tokens, int N, int Np, int E, void* stream);
+int nk_vit_tokens_bwd(const void* dtokens, void* dpatches, int N, int Np, int E, void* stream);
+int nk_vit_add_ln(float* x, const void* branch, const float* gamma, const float* beta, void* y, int y_f32, void* xb, float* mean, float* rstd, int M,
+                  int E, float eps, void* stream);
+ /* nk_vit_cls_head_fwd: the cls row of each sample (row n * sample_stride / E of the fp32 token matrix; sample_stride in elements) through the
+ * final LayerNorm (gamma / beta fp32, or both NULL) and the head (W fp32 [nc, E] and bias, or W NULL and nc == E), all in fp32 -> out fp32
+ * [N, nc]; mean / rstd [N] are written when there is a norm.  nk_vit_cls_head_bwd: dcls bf16 [N, E], the gradient w.r.t. the cls rows. E <= 2048. */
+int nk_vit_cls_head_fwd(const void* tokens, long sample_stride, const float* gamma, const float* beta, const float* W, const float* bias, float* out,
+                        float* mean, float* rstd, int N, int E, int nc, float eps, void* stream);
+int nk_vit_cls_head_bwd(const float* dout, const void* tokens, long sample_stride, const float* gamma, const float* W, const float* mean,
+                        const float* rstd, void* dcls, int N, int E, int nc, void* stream);
+int nk_dreamsim_head_fwd(const float* f, float* d, int B, int Dz, float eps, void* stream);
+int nk_dreamsim_head_bwd(const float* f, const float* upstream, float* df1, int B, int Dz, float eps, void* stream);
+
 /* LitEma.forward (reference modules/ema.py:40-59) as one pass over the flat fp32 buffers (n % 4 == 0):
  * ema[i] -= one_minus_decay * (ema[i] - p[i]).  The decay schedule min(decay, (1+n)/(10+n)) is the host's. */
 int nk_ema_flat(float* ema, const float* p, long n, float one_minus_decay, void* stream);

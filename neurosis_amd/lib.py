@@ -100,6 +100,15 @@ SIGNATURES: dict[str, list] = {
     "nk_gumbel_softmax_fwd": [vp, i64, vp, vp, i32, f32, vp, vp, vp, vp, i64, i32, vp],
     "nk_gumbel_softmax_bwd": [vp, i64, vp, vp, f32, f32, i64, i32, vp],
     "nk_resample_planes": [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i64, i32, i32, i32, i32, vp],
+    "nk_vit_patchify": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "nk_vit_patchify_bwd": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "nk_vit_tokens": [vp, vp, vp, vp, i32, i32, i32, vp],
+    "nk_vit_tokens_bwd": [vp, vp, i32, i32, i32, vp],
+    "nk_vit_add_ln": [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, vp],
+    "nk_vit_cls_head_fwd": [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
+    "nk_vit_cls_head_bwd": [vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "nk_dreamsim_head_fwd": [vp, vp, i32, i32, f32, vp],
+    "nk_dreamsim_head_bwd": [vp, vp, vp, i32, i32, f32, vp],
     "nk_leaky_relu_fwd": [vp, vp, i64, f32, vp],
     "nk_leaky_relu_bwd": [vp, vp, vp, i64, f32, vp],
     "nk_maxpool2x2_fwd": [vp, vp, i32, i32, i32, i32, vp],

@@ -132,7 +132,7 @@ class AutoencodingEngine(nn.Module):
                  perceptual_loss: Optional[nn.Module] = None, perceptual_weight: float = 1.0, resize: Optional[str] = None, **kwargs):
         super().__init__()
         self.encoder, self.decoder = encoder, decoder
-        self.perceptual_only = False
+        self.perceptual_only, self.perceptual_kind = False, "lpips"
         self.disc_store: Optional[FlatParamStore] = None
         self.regularization = regularizer if regularizer is not None else DiagonalGaussianRegularizer()
         if hasattr(loss, "engine_settings"):
@@ -160,6 +160,7 @@ class AutoencodingEngine(nn.Module):
             # AutoencoderPerceptual: clamped images, per-sample means, no discriminator (_perceptual_loss); its LPIPS is read from the loss
             # object at each step, so that `delay_setup` / `configure_model()` work as in the reference
             self.perceptual_only = bool(cfg.get("perceptual_only", False))
+            self.perceptual_kind = cfg.get("perceptual_kind", "lpips")          # "dreamsim": AutoencoderDreamsim, read from `loss.dreamsim_loss`
             if self.perceptual_only:
                 self.perceptual_weight = cfg["perceptual_weight"]
         else:
@@ -320,7 +321,8 @@ class AutoencodingEngine(nn.Module):
     def _perceptual_loss(self, x: torch.Tensor, xrec: torch.Tensor, out_img: Img):
         """AutoencoderPerceptual (vae_lpips_discr.py:97-137):  loss = mean_b(recon_weight * rec_b + perceptual_weight * relu(LPIPS_b)),  rec_b the
         per-sample mean of |x - xrec| or (x - xrec)^2, both images clamped to [-1, 1]; no gradient where xrec was clamped.  (The reference
-        adds a [B] to a [B, 1, 1, 1] tensor, which backpropagates only at B = 1, where it is this formula.)
+        adds a [B] to a [B, 1, 1, 1] tensor, which backpropagates only at B = 1, where it is this formula.)  AutoencoderDreamsim shares everything
+        but the perceptual term, which is dreamsim_weight * relu(sum_b' d_b') for every sample (below).
         Returns (loss, d loss / d reconstruction tokens, log); every log entry is a device scalar."""
         B, C, H, W = x.shape
         inside = (xrec >= -1.0) & (xrec <= 1.0)
@@ -330,8 +332,18 @@ class AutoencodingEngine(nn.Module):
         rec_term = self.rec_weight * rec.mean(dim=(1, 2, 3))                                 # [B]
         d_rec = (2.0 * diff if self.rec_loss_type == "l2" else torch.sign(diff)) * (self.rec_weight / (B * C * H * W))
         p_term = torch.zeros(B, device=x.device)
-        lpips = self.loss.perceptual_loss
-        if self.perceptual_weight > 0:
+        if self.perceptual_weight > 0 and self.perceptual_kind == "dreamsim":
+            # AutoencoderDreamsim (losses/dreamsim.py:101-140): the distances are summed over the batch BEFORE the relu and that scalar joins every
+            # sample's term:  loss = mean_b(recon_weight * rec_b + dreamsim_weight * relu(sum_b' d_b')),  d loss / d d_b' = dreamsim_weight * [sum > 0]
+            dreamsim = self.loss.dreamsim_loss
+            if dreamsim is None:
+                raise RuntimeError("AutoencoderDreamsim(delay_setup=True): call configure_model() on the loss before the first training step")
+            d, b_dreamsim = dreamsim.fwdb(xc, rc, rescale=self.loss.rescale_input)
+            d_sum = d.sum()
+            p_term = (self.perceptual_weight * torch.relu(d_sum)).expand(B)
+            d_rec = d_rec + b_dreamsim(((d_sum > 0) * self.perceptual_weight).expand(B).contiguous())
+        elif self.perceptual_weight > 0:
+            lpips = self.loss.perceptual_loss
             if lpips is None:
                 raise RuntimeError("AutoencoderPerceptual(delay_setup=True): call configure_model() on the loss before the first training step")
             p_loss, b_lpips = lpips.fwdb(xc, Img(ops.nchw_to_tokens(rc, out_img.C), B, H, W))

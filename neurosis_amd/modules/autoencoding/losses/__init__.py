@@ -5,6 +5,7 @@ SDXL one does.
     GeneralLPIPSWithDiscriminator   /root/reference/src/neurosis/modules/autoencoding/losses/discriminator_loss.py:22-88
     AutoencoderLPIPSWithDiscr       /root/reference/src/neurosis/modules/autoencoding/losses/vae_lpips_discr.py:140-200
     AutoencoderPerceptual           the same file, :25-137
+    AutoencoderDreamsim             the reference's modules/autoencoding/losses/dreamsim.py:16-152
 
 In the reference these modules own the LPIPS network, the PatchGAN discriminator and the output log-variance, and their `forward`
 assembles the loss from torch ops under autograd.  Here they OWN THE SAME SUBMODULES UNDER THE SAME NAMES (so `loss.*` checkpoint
@@ -33,8 +34,9 @@ import torch
 from torch import nn
 
 from ...losses import LPIPS, NLayerDiscriminator, get_discr_loss_fn, weights_init
+from ...losses.dreamsim import DreamsimBackbone, DreamsimEnsemble, DreamsimModel
 
-__all__ = ["AutoencoderLPIPSWithDiscr", "AutoencoderPerceptual", "GeneralLPIPSWithDiscriminator"]
+__all__ = ["AutoencoderDreamsim", "AutoencoderLPIPSWithDiscr", "AutoencoderPerceptual", "GeneralLPIPSWithDiscriminator"]
 
 logger = logging.getLogger(__name__)
 
@@ -232,3 +234,67 @@ class AutoencoderPerceptual(_FusedLossConfig):
 
     def engine_settings(self) -> dict:
         return {**super().engine_settings(), "perceptual_only": True}
+
+
+class AutoencoderDreamsim(_FusedLossConfig):
+    """dreamsim.py:16-152: l1 / l2 reconstruction + the DreamSim distance of frozen ViT-B/16 towers (modules/losses/dreamsim), no discriminator
+    and no second optimizer.  Passed as `loss=` it makes the engine compute, per step,
+
+        loss = mean_b( recon_weight * rec_b + dreamsim_weight * relu(sum_b' d_b') )
+
+    rec_b the per-sample mean of |x - xrec| (l1) or (x - xrec)^2 (l2), both images clamped to [-1, 1] first (after the resize, if one is
+    configured) and, with rescale_input, mapped to [0, 1] for the towers; the gradient is zero where xrec was clamped.  (The reference adds the
+    [B] reconstruction term and the scalar DreamSim term and returns the [B] tensor; this is its mean.)  The log carries `{split}/loss/total`,
+    `/rec` and `/p` as device scalars.  `dreamsim_name_or_path` names a LOCAL directory in the diffusers layout (config.json plus
+    diffusion_pytorch_model.safetensors): there is no hub access, so the reference's default hub name raises at configure_model().
+
+    `vit_config` (keyword-only) is this package's addition: VisionTransformer arguments that override ViT-B's.  With it and no directory at
+    `dreamsim_name_or_path` the towers are built at their seeded initialisation instead of loaded (tests, benchmarks)."""
+
+    perceptual_loss = None             # (what the adversarial classes call their LPIPS: the engine reads `dreamsim_loss` from this class)
+
+    def __init__(self, dreamsim_name_or_path="neggles/dreamsim:ensemble_vitb16", dreamsim_weight: float = 1.0, dreamsim_ensemble: bool = True,
+                 recon_type="l1", recon_weight: float = 1.0, resize_input: bool = False, resize_target: bool = False, extra_log_keys: list[str] = [],
+                 rescale_input: bool = True, delay_setup: bool = False, dreamsim_compile: bool = False, *, vit_config: Optional[dict] = None):
+        super().__init__()
+        self.recon_type = recon_type
+        self.rec_loss_type = _rec_type(recon_type)
+        self.recon_weight = self.rec_weight = float(recon_weight)
+        self.resize = _resize_mode(resize_input, resize_target)
+        self.resize_input_to_target, self.resize_target_to_input = resize_input, resize_target
+        self.rescale_input = bool(rescale_input)
+        self._dreamsim_cls = DreamsimEnsemble if dreamsim_ensemble else DreamsimModel
+        self._dreamsim_name = str(dreamsim_name_or_path)
+        self._vit_config = None if vit_config is None else dict(vit_config)
+        self.dreamsim_loss: Optional[DreamsimBackbone] = None
+        self.dreamsim_weight = self.perceptual_weight = float(dreamsim_weight)
+        self.forward_keys = ["split"]
+        self.extra_log_keys = set(extra_log_keys)
+        self.dreamsim_compile = dreamsim_compile
+        if dreamsim_compile:
+            logger.info("AutoencoderDreamsim(dreamsim_compile=True): ignored, the DreamSim towers run on this package's HIP kernels, not through TorchInductor")
+        # no discriminator: the settings the adversarial classes share are fixed
+        self.disc_start, self.disc_factor, self.discriminator_weight, self.disc_loss_name, self.learn_logvar = maxsize, 0.0, 0.0, "hinge", False
+        if delay_setup:
+            logger.info("Delaying Dreamsim model loading until configure_model() call")
+        else:
+            self.configure_model()
+
+    def configure_model(self) -> None:
+        if self.dreamsim_loss is None:
+            import os
+
+            if self._vit_config is not None and not os.path.isdir(self._dreamsim_name):
+                self.dreamsim_loss = self._dreamsim_cls(vit_config=self._vit_config)
+            else:
+                self.dreamsim_loss = self._dreamsim_cls.from_pretrained(self._dreamsim_name, local_files_only=True, vit_config=self._vit_config)
+        self.dreamsim_loss = self.dreamsim_loss.requires_grad_(False).eval()
+
+    def get_trainable_parameters(self) -> Iterator[nn.Parameter]:
+        yield from ()
+
+    def _discriminator_module(self) -> Optional[nn.Module]:
+        return None
+
+    def engine_settings(self) -> dict:
+        return {**super().engine_settings(), "perceptual_only": True, "perceptual_kind": "dreamsim"}

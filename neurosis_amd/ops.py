@@ -13,6 +13,7 @@ Conventions
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 import weakref
@@ -1658,6 +1659,203 @@ def resize_bicubic_aa_bwd(dy: Tensor, size) -> Tensor:
     if dy.is_cuda and dy.dim() == 4 and tuple(dy.shape[2:]) == (IH, IW):
         return dy
     return _resize_planes(dy, (IH, IW), True, "resize_bicubic_aa_bwd")
+
+
+# ------------------------------------------------------------------------------------------------
+# frozen ViT towers of the DreamSim loss (csrc/vit.hip): what is not a transformer layer
+# ------------------------------------------------------------------------------------------------
+def _vit_image(x: Tensor, patch: int, op: str):
+    if not x.is_cuda:
+        raise NotImplementedError(f"{op}: the input is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{op}: expected a dense fp32 NCHW tensor with 3 channels, got {tuple(x.shape)} {x.dtype}")
+    N, _, H, W = x.shape
+    if patch % 8 or H % patch or W % patch:
+        raise ValueError(f"{op}: height and width must be multiples of the patch size (itself a multiple of 8), got {(H, W)} and patch {patch}")
+    return N, H, W, (H // patch) * (W // patch)
+
+
+def vit_affine(scale, shift, lo: float = -math.inf, hi: float = math.inf):
+    """the host array {a_0..2, b_0..2, lo, hi} of vit_patchify: each value is a_c * clamp(x, lo, hi) + b_c"""
+    return (C.c_float * 8)(*[float(v) for v in scale], *[float(v) for v in shift], float(lo), float(hi))
+
+
+def vit_patchify(x: Tensor, patch: int, affine) -> Tensor:
+    """x fp32 NCHW [N, 3, H, W] -> bf16 rows [N * Np, 3 p p], row (n, py, px), column (c, ky, kx) (nn.Conv2d's weight order), each value the bf16
+    rounding of a_c * clamp(x, lo, hi) + b_c (`affine` from vit_affine)."""
+    N, H, W, Np = _vit_image(x, patch, "vit_patchify")
+    rows = torch.empty(N * Np, 3 * patch * patch, dtype=BF16, device=x.device)
+    call("nk_vit_patchify", x.data_ptr(), rows.data_ptr(), affine, N, H, W, patch, _stream())
+    return rows
+
+
+def vit_patchify_bwd(drows: Tensor, x: Tensor, patch: int, affine, out: Optional[Tensor] = None) -> Tensor:
+    """The adjoint of vit_patchify at x: fp32 NCHW a_c * drows, zero where the forward clamped.  With `out` (fp32, x's shape) the result is ADDED
+    to it (the towers of an ensemble add their input gradients in a fixed order); one writer per pixel, no atomics."""
+    N, H, W, Np = _vit_image(x, patch, "vit_patchify_bwd")
+    _check2d(drows, "drows")
+    if tuple(drows.shape) != (N * Np, 3 * patch * patch) or not drows.is_contiguous():
+        raise ValueError(f"vit_patchify_bwd: drows must be a dense [{N * Np}, {3 * patch * patch}] matrix, got {tuple(drows.shape)}")
+    if out is not None and (out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device):
+        raise ValueError("vit_patchify_bwd: out must be a dense fp32 tensor of x's shape on x's device")
+    dx = torch.empty_like(x) if out is None else out
+    call("nk_vit_patchify_bwd", drows.data_ptr(), x.data_ptr(), dx.data_ptr(), affine, N, H, W, patch, int(out is not None), _stream())
+    return dx
+
+
+def vit_tokens(patches: Tensor, cls: Tensor, pos: Tensor, N: int) -> Tensor:
+    """tokens FP32 [N (Np + 1), E] (a tower's residual stream is fp32, vit_add_ln): row 0 of a sample is cls + pos[0], row 1 + i patch row i + pos[1 + i]; patches bf16 [N Np, E] (the patch
+    GEMM's output, bias included), cls fp32 [E], pos fp32 [Np + 1, E]."""
+    _check2d(patches, "patches")
+    E = patches.shape[1]
+    Np = patches.shape[0] // max(N, 1)
+    if N < 1 or Np < 1 or Np * N != patches.shape[0] or not patches.is_contiguous() or E % 8:
+        raise ValueError(f"vit_tokens: patches must be a dense [N * Np, E] matrix with E % 8 == 0, got {tuple(patches.shape)} for N = {N}")
+    for name, t, shape in (("cls", cls, (E,)), ("pos", pos, (Np + 1, E))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != patches.device:
+            raise ValueError(f"vit_tokens: {name} must be a dense fp32 {shape} tensor on the patches' device, got {tuple(t.shape)} {t.dtype}")
+    tokens = torch.empty(N * (Np + 1), E, dtype=torch.float32, device=patches.device)
+    call("nk_vit_tokens", patches.data_ptr(), cls.data_ptr(), pos.data_ptr(), tokens.data_ptr(), N, Np, E, _stream())
+    return tokens
+
+
+def vit_tokens_bwd(dtokens: Tensor, N: int) -> Tensor:
+    """The adjoint of vit_tokens w.r.t. the patch rows: dtokens bf16 [N (Np + 1), E] -> [N Np, E], the cls rows dropped."""
+    _check2d(dtokens, "dtokens")
+    L, E = dtokens.shape[0] // max(N, 1), dtokens.shape[1]
+    if N < 1 or L < 2 or L * N != dtokens.shape[0] or not dtokens.is_contiguous() or E % 8:
+        raise ValueError(f"vit_tokens_bwd: dtokens must be a dense [N * (Np + 1), E] matrix with E % 8 == 0, got {tuple(dtokens.shape)} for N = {N}")
+    dpatches = torch.empty(N * (L - 1), E, dtype=BF16, device=dtokens.device)
+    call("nk_vit_tokens_bwd", dtokens.data_ptr(), dpatches.data_ptr(), N, L - 1, E, _stream())
+    return dpatches
+
+
+def vit_add_ln(x: Tensor, branch: Optional[Tensor], norm: Optional[torch.nn.LayerNorm], copy: bool = False, y_f32: bool = False):
+    """The seam between a frozen tower's fp32 residual stream x [M, E] and the bf16 GEMMs (nk_vit_add_ln):  x += branch IN PLACE (bf16 [M, E];
+    skipped when None), then y = norm(x) as bf16 (or fp32 with y_f32: norm_pre, whose output is the stream) when a norm is given.
+    Returns (y or None, xb or None, mean, rstd): xb is x rounded to bf16 (copy=True), which with mean / rstd [M] is what
+    layernorm_bwd_dx reads in the backward."""
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f"vit_add_ln: x must be a dense fp32 CUDA matrix, got {tuple(x.shape)} {x.dtype}")
+    M, E = x.shape
+    if branch is not None:
+        _check2d(branch, "branch")
+        if branch.shape != x.shape or not branch.is_contiguous():
+            raise ValueError(f"vit_add_ln: branch must be a dense bf16 matrix of x's shape {tuple(x.shape)}, got {tuple(branch.shape)}")
+    if norm is None and branch is None and not copy:
+        raise ValueError("vit_add_ln: nothing to do")
+    y = mean = rstd = None
+    if norm is not None:
+        y = torch.empty(M, E, dtype=torch.float32 if y_f32 else BF16, device=x.device)
+        mean = torch.empty(M, dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+    xb = torch.empty(M, E, dtype=BF16, device=x.device) if copy else None
+    call("nk_vit_add_ln", x.data_ptr(), _p(branch), _p(norm.weight) if norm is not None else None, _p(norm.bias) if norm is not None else None, _p(y),
+         int(y_f32), _p(xb), _p(mean), _p(rstd), M, E, float(norm.eps) if norm is not None else 1.0, _stream())
+    return y, xb, mean, rstd
+
+
+def vit_cls_head(tokens: Tensor, N: int, norm: Optional[torch.nn.LayerNorm], head: Optional[torch.nn.Linear], tape_from: Optional[int] = None):
+    """(embedding fp32 [N, width], bwd): the cls row of each of the N samples of a dense FP32 token matrix [N * L, E] through the final
+    LayerNorm (when given) and the head (when given), in fp32 on the fp32 parameters (nk_vit_cls_head_fwd).  With tape_from = s,
+    bwd(d embedding[s:] fp32) -> bf16 [N - s, E], the gradient w.r.t. the cls rows of samples s..N-1; no parameter gradient exists."""
+    if tokens.dim() != 2 or tokens.dtype != torch.float32 or not tokens.is_cuda or N < 1 or tokens.shape[0] % N or not tokens.is_contiguous():
+        raise ValueError(f"vit_cls_head: tokens must be a dense fp32 CUDA [N * L, E] matrix, got {tuple(tokens.shape)} {tokens.dtype} for N = {N}")
+    L, E = tokens.shape[0] // N, tokens.shape[1]
+    for p in ([norm.weight, norm.bias] if norm is not None else []) + ([head.weight, head.bias] if head is not None else []):
+        if p is not None and (p.dtype != torch.float32 or not p.is_contiguous() or p.device != tokens.device):
+            raise ValueError("vit_cls_head: the norm's and the head's parameters must be dense fp32 tensors on the tokens' device")
+    nc = head.weight.shape[0] if head is not None else E
+    out = torch.empty(N, nc, dtype=torch.float32, device=tokens.device)
+    mean = torch.empty(N, dtype=torch.float32, device=tokens.device)
+    rstd = torch.empty_like(mean)
+    gamma, beta = (norm.weight, norm.bias) if norm is not None else (None, None)
+    W, bias = (head.weight, head.bias) if head is not None else (None, None)
+    call("nk_vit_cls_head_fwd", tokens.data_ptr(), L * E, _p(gamma), _p(beta), _p(W), _p(bias), out.data_ptr(), mean.data_ptr(), rstd.data_ptr(), N, E, nc,
+         float(norm.eps) if norm is not None else 1.0, _stream())
+    if tape_from is None:
+        return out, None
+    s = tape_from
+
+    def bwd(dout: Tensor) -> Tensor:
+        dout = dout.to(torch.float32).contiguous()
+        if tuple(dout.shape) != (N - s, nc):
+            raise ValueError(f"vit_cls_head backward: expected a gradient of shape {(N - s, nc)}, got {tuple(dout.shape)}")
+        dcls = torch.empty(N - s, E, dtype=BF16, device=tokens.device)
+        call("nk_vit_cls_head_bwd", dout.data_ptr(), tokens[s * L:].data_ptr(), L * E, _p(gamma), _p(W), mean[s:].data_ptr(), rstd[s:].data_ptr(),
+             dcls.data_ptr(), N - s, E, nc, _stream())
+        return dcls
+
+    return out, bwd
+
+
+def dreamsim_head(f: Tensor, eps: float = 1e-8):
+    """(d [B], bwd): f fp32 [2, B, Dz]; z = f / |f| - mean(f / |f|) per vector, d_b = 1 - F.cosine_similarity(z[0], z[1], eps).
+    bwd(upstream [B]) -> d sum_b upstream_b d_b / d f[1], fp32 [B, Dz]; f[0] (the input image's features) gets no gradient."""
+    if not f.is_cuda:
+        raise NotImplementedError("dreamsim_head: the input is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    if f.dim() != 3 or f.shape[0] != 2 or f.dtype != torch.float32 or not f.is_contiguous():
+        raise ValueError(f"dreamsim_head: expected a dense fp32 [2, B, Dz] tensor, got {tuple(f.shape)} {f.dtype}")
+    _, B, Dz = f.shape
+    d = torch.empty(B, dtype=torch.float32, device=f.device)
+    call("nk_dreamsim_head_fwd", f.data_ptr(), d.data_ptr(), B, Dz, float(eps), _stream())
+
+    def bwd(upstream: Tensor) -> Tensor:
+        up = upstream.to(torch.float32).contiguous()
+        if tuple(up.shape) != (B,) or up.device != f.device:
+            raise ValueError(f"dreamsim_head backward: upstream must be [{B}] on f's device, got {tuple(up.shape)}")
+        df1 = torch.empty(B, Dz, dtype=torch.float32, device=f.device)
+        call("nk_dreamsim_head_bwd", f.data_ptr(), up.data_ptr(), df1.data_ptr(), B, Dz, float(eps), _stream())
+        return df1
+
+    return d, bwd
+
+
+def layernorm_bwd_dx(dy: Tensor, x: Tensor, weight: Tensor, mean: Tensor, rstd: Tensor, dx_add: Optional[Tensor] = None) -> Tensor:
+    """The input gradient of a LayerNorm alone (nk_layernorm_bwd_dx): no gamma / beta gradient is launched.  dx_add joins the result."""
+    for name, t in (("dy", dy), ("x", x)) + ((("dx_add", dx_add),) if dx_add is not None else ()):
+        _check2d(t, name)
+        if t.shape != x.shape or not t.is_contiguous():
+            raise ValueError(f"layernorm_bwd_dx: {name} must be a dense matrix of x's shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    M, Cc = x.shape
+    if mean.numel() != M or rstd.numel() != M:
+        raise ValueError(f"layernorm_bwd_dx: mean / rstd must hold {M} rows")
+    dx = torch.empty_like(x)
+    call("nk_layernorm_bwd_dx", dy.data_ptr(), x.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _p(dx_add), dx.data_ptr(), M, Cc, _stream())
+    return dx
+
+
+def gelu_bwd(dy: Tensor, x: Tensor, quick: bool = False) -> Tensor:
+    """dx = dy * gelu'(x) (nk_gelu_bwd): gelu_fwd's backward without its closure"""
+    if dy.shape != x.shape or dy.dtype != BF16 or x.dtype != BF16 or not dy.is_contiguous() or not x.is_contiguous():
+        raise ValueError("gelu_bwd: dy and x must be dense bf16 tensors of one shape")
+    dx = torch.empty_like(x)
+    call("nk_gelu_bwd", dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), int(quick), _stream())
+    return dx
+
+
+def attention_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, lse: Tensor, do: Tensor, B: int, heads: int, dim_head: int, dq: Tensor, dk: Tensor,
+                  dv: Tensor) -> None:
+    """The backward of the non-causal attention_fwd from its saved tensors (or the row slices of them that belong to B whole samples):
+    q / o / do / dq [B*Lq, H*D], k / v / dk / dv [B*Lk, H*D] token matrices (column slices allowed), lse fp32 [B, heads, Lq] dense."""
+    for n, t in (("q", q), ("k", k), ("v", v), ("o", o), ("do", do), ("dq", dq), ("dk", dk), ("dv", dv)):
+        _check2d(t, n)
+    if dim_head > 160:
+        raise NotImplementedError("attention_bwd: head dim <= 160")
+    Lq, Lk = q.shape[0] // B, k.shape[0] // B
+    if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * heads * Lq:
+        raise ValueError(f"attention_bwd: lse must be a dense fp32 [{B}, {heads}, {Lq}] tensor")
+    d = NkAttnDesc()
+    d.B, d.H, d.Lq, d.Lk, d.D = B, heads, Lq, Lk, dim_head
+    d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
+    d.bq, d.bk, d.bv, d.bo = Lq * q.stride(0), Lk * k.stride(0), Lk * v.stride(0), Lq * o.stride(0)
+    d.scale = float(dim_head) ** -0.5
+    d.causal = 0
+    d.sdq, d.sdk, d.sdv, d.sdo = dq.stride(0), dk.stride(0), dv.stride(0), do.stride(0)
+    d.bdq, d.bdk, d.bdv, d.bdo = Lq * dq.stride(0), Lk * dk.stride(0), Lk * dv.stride(0), Lq * do.stride(0)
+    delta = _ws(query("nk_attention_bwd_ws_floats", C.byref(d)), do.device)
+    call("nk_attention_bwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(),
+         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), _stream())
 
 
 # ------------------------------------------------------------------------------------------------
