@@ -1,6 +1,7 @@
 """Fused multi-tensor CAME on the flat buffers (csrc/came.hip) against the reference's own steps (golden fixture came_steps), against
 an fp64 restatement of the reference step on a larger SDXL-like parameter set, and inside the engine (hipGraph replay, gradient
-accumulation, the backward-health gate).  fp32 throughout: 2e-5 relative on parameters (reduction orders differ), 1e-4 on states."""
+accumulation, the backward-health gate).  fp32 throughout: 2e-5 relative on parameters (reduction orders differ), 1e-4 on states.  One
+step moves a parameter by far less than it is wide, so each step's delta (p_after - p_before) is compared with the reference's as well."""
 import json
 import os
 from functools import partial
@@ -24,6 +25,29 @@ def _clean_health():
     lib.call("nk_health_clear")
     yield
     lib.call("nk_health_clear")
+
+
+# rel_err of a step's delta.  For the fixture, measured on the CPU: the fp32 reference's deltas against the deltas of the float64 chain of
+# came_ref_step on the same inputs are at most 1.03e-3 (default), 1.76e-3 (decay) and 9.7e-5 (fixed) over the four steps; the tolerance
+# is twice that: the kernels' deviation and the reference's are independent and of the same kind.  A step that leaves the masters alone
+# has rel_err 1.
+# On the SDXL-like set the reference is float64 itself, so what it lacks is the fp32 format of the masters, and that is computed, not
+# sampled: a delta between fp32 masters is off by half an ulp of p twice (the master the step started from against the float64 chain's,
+# and the rounding of the new one), 2^-23 max |p| at most, which delta_floor() puts in relation to the reference delta per tensor
+# (6e-6 for the matrices, 2e-4 .. 2e-3 for the vectors, whose update is lr m without a second preconditioner).  On top, the arithmetic:
+# twice the worst per-element bound of one CAME step's p_new relative to its update, 900 U (tests/optim_bounds.py), the factor two for
+# the drift of the states over three steps.  (A first version took twice the floor as sampled from the float64 chain, 2 x 1.95e-4 on the
+# third step; the five-element vector came out at 4.8e-4 under a floor of 8.2e-4: rounding luck of five values, not arithmetic.)
+DELTA_TOL = {"default": 2 * 1.03e-3, "decay": 2 * 1.76e-3, "fixed": 2 * 9.7e-5}
+SDXL_DELTA_ARITH = 2 * 900 * 2.0 ** -24
+
+
+def delta_floor(ref_before, ref_after) -> float:
+    return float(2.0 ** -23 * ref_after.abs().max() / (ref_after - ref_before).abs().max())
+
+
+def delta_err(p_before, p_after, ref_before, ref_after) -> float:
+    return rel_err(p_after.double() - p_before.double(), ref_after.double() - ref_before.double())
 
 
 def make_store(tensors):
@@ -50,10 +74,13 @@ def test_flat_came_matches_reference_steps(tag):
     assert len(opt.chunks) > 2
     for s in range(4):
         set_grads(params, c["grads"][s])
+        before = [p.detach().cpu().clone() for p in params]
         opt.step()
         torch.cuda.synchronize()
         for p, want in zip(params, c["after"][s]):
             assert rel_err(p.detach().cpu(), want) <= 2e-5, (s, tuple(p.shape))
+        for p, p0, want0, want in zip(params, before, c["after"][s - 1] if s else c["init"], c["after"][s]):
+            assert delta_err(p0, p.detach().cpu(), want0, want) <= DELTA_TOL[tag], (s, tuple(p.shape))
         for p in params:          # the bf16 shadows the kernels read follow the masters
             assert rel_err(ops._phys_flat(p).float().cpu(), p._nk_shadow.float().cpu()) <= 1e-2
     for i, want in enumerate(c["states"]):
@@ -115,11 +142,14 @@ def test_flat_came_sdxl_like_shapes_vs_fp64():
     for s, mag in enumerate((1.0, 10.0, 0.1)):
         grads = [torch.randn(*sh, generator=g) * mag for sh in shapes]
         set_grads(params, grads)
+        before, ref_before = [p.detach().cpu().clone() for p in params], ref
         opt.step()
         ref = [came_ref_step(p, gr, st, **kw) for p, gr, st in zip(ref, grads, sts)]
         torch.cuda.synchronize()
         for p, want in zip(params, ref):
             assert rel_err(p.detach().cpu(), want) <= 1e-5, (s, tuple(p.shape))
+        for p, p0, want0, want in zip(params, before, ref_before, ref):
+            assert delta_err(p0, p.detach().cpu(), want0, want) <= SDXL_DELTA_ARITH + delta_floor(want0, want), (s, tuple(p.shape))
     for i, st in enumerate(sts):
         got = opt.param_state(i)
         for k, v in st.items():

@@ -1,6 +1,7 @@
 """Fused multi-tensor Adafactor on the flat buffers (csrc/optim.hip) against the reference's own steps (golden fixture)
 and against the CPU oracle on a larger, SDXL-like parameter set.  fp32 throughout: tolerance 2e-5 relative on parameters
-(reduction orders differ), 1e-4 on the factored states."""
+(reduction orders differ), 1e-4 on the factored states.  One step moves a parameter by far less than it is wide, so each step's delta
+(p_after - p_before) is compared with the reference's delta as well, at DELTA_TOL / SDXL_DELTA_TOL."""
 from pathlib import Path
 
 import pytest
@@ -11,6 +12,20 @@ from tests.golden.fixture_io import load_fixture
 
 pytestmark = pytest.mark.gpu
 GOLD = Path(__file__).parent / "golden"
+
+
+# rel_err of a step's delta.  Measured on the CPU: the fp32 reference's own delta against the delta of a float64 chain on the same inputs
+# (tests/optim_bounds.py::adafactor_ref_step) is at most 6.6e-2 / 4.7e-2 / 3.6e-2 over the three steps of the `relative` fixture (the step
+# is 1e-6 of max |p| there: a delta between fp32 masters carries an ulp of |p|) and 1.85e-4 / 1.93e-4 / 1.96e-4 for `manual`; for the
+# SDXL-like set and the fp32 CPU oracle 1.12e-1, 3.36e-1, 3.73e-2, 1.64e-1, 1.91e-2 for its five steps.  The tolerance is twice the largest
+# measured value (per step for the SDXL-like set): the kernels' deviation and the reference's are independent and of the same kind.
+# A step that leaves the masters alone has rel_err 1.
+DELTA_TOL = {"relative": 2 * 6.6e-2, "manual": 2 * 1.97e-4}
+SDXL_DELTA_TOL = [2 * t for t in (1.12e-1, 3.36e-1, 3.73e-2, 1.64e-1, 1.91e-2)]
+
+
+def delta_err(p_before, p_after, ref_before, ref_after) -> float:
+    return rel_err(p_after.double() - p_before.double(), ref_after.double() - ref_before.double())
 
 
 def make_store(tensors):
@@ -39,10 +54,13 @@ def test_flat_adafactor_matches_reference_steps(tag, streams, monkeypatch):
     assert len(opt.chunks) > 2
     for s in range(3):
         set_grads(params, c["grads"][s])
+        before = [p.detach().cpu().clone() for p in params]
         opt.step()
         torch.cuda.synchronize()
         for p, want in zip(params, c["after"][s]):
             assert rel_err(p.detach().cpu(), want) <= 2e-5, (s, tuple(p.shape))
+        for p, p0, want0, want in zip(params, before, c["after"][s - 1] if s else c["init"], c["after"][s]):
+            assert delta_err(p0, p.detach().cpu(), want0, want) <= DELTA_TOL[tag], (s, tuple(p.shape))
         # the bf16 shadows the kernels read follow the masters
         for p in params:
             from neurosis_amd import ops
@@ -58,8 +76,9 @@ def test_flat_adafactor_matches_reference_steps(tag, streams, monkeypatch):
     opt2 = FlatAdafactor(store2, **c["kwargs"])
     set_grads(params2, c["grads"][0], scale=4.0)
     opt2.step(grad_scale=0.25)
-    for p, want in zip(params2, c["after"][0]):
+    for p, p0, want in zip(params2, c["init"], c["after"][0]):
         assert rel_err(p.detach().cpu(), want) <= 2e-5
+        assert delta_err(p0, p.detach().cpu(), p0, want) <= DELTA_TOL[tag], tuple(p.shape)
 
 
 def _adafactor_run(c, steps, scale=1.0, grad_scale=1.0):
@@ -99,7 +118,7 @@ def test_grad_scale_is_exact(tag, streams, monkeypatch):
 
 def test_flat_adafactor_sdxl_like_shapes_vs_oracle():
     """Real channel counts (ragged tiles: 1280x2048 context projections, 320-channel convs, 4-channel conv_out, 2816 label
-    input), five steps, against the CPU oracle."""
+    input), five steps, against the CPU oracle: parameters, each step's delta (SDXL_DELTA_TOL), lr, and the factored states at the end."""
     from neurosis_amd.optim import AdafactorScheduler, FlatAdafactor
     from oracle import adafactor_oracle as AO
 
@@ -117,14 +136,23 @@ def test_flat_adafactor_sdxl_like_shapes_vs_oracle():
     for s in range(5):
         grads = [torch.randn(*sh, generator=g) * (0.1 if s % 2 else 3.0) for sh in shapes]
         set_grads(params, grads)
+        before, ref_before = [p.detach().cpu().clone() for p in params], [t.clone() for t in ref]
         opt.step()
         lrs = [AO.step_tensor(p, gr, st, **kw) for p, gr, st in zip(ref, grads, sts)]
         torch.cuda.synchronize()
         for p, want in zip(params, ref):
             assert rel_err(p.detach().cpu(), want) <= 2e-5, (s, tuple(p.shape))
+        for p, p0, want0, want in zip(params, before, ref_before, ref):
+            assert delta_err(p0, p.detach().cpu(), want0, want) <= SDXL_DELTA_TOL[s], (s, tuple(p.shape))
         # lr = max(eps2, RMS(p)) * rel_step: torch's CPU norm over 2-4 M elements carries ~1e-5..1e-4 of fp32 accumulation noise
         assert rel_err(opt.current_lrs().cpu(), torch.tensor(lrs)) <= 3e-4
     assert abs(sched.get_lr()[0] - lrs[0]) <= 3e-4 * lrs[0]
+    for i, want in enumerate(sts):
+        got = opt.param_state(i)
+        for k in ("exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_sq"):
+            if k in want:
+                assert tuple(got[k].shape) == tuple(want[k].shape), (i, k)
+                assert rel_err(got[k].cpu(), want[k]) <= 1e-4, (i, k)
 
 
 def test_flat_adafactor_argument_errors():
