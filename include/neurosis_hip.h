@@ -193,6 +193,20 @@ int nk_attention_bwd_causal(const NkAttnDesc* d, const void* q, const void* k, c
  * fp32 [H][Lq + Lk - 1], one row per head, indexed by key minus query position; added in fp32 before the running max.  Lq == Lk <= 1024,
  * D % 8 == 0, D <= 160, !causal; q / k / v / o as for nk_attention_fwd. */
 int nk_attention_relbias_fwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, void* o, const float* rel, void* stream);
+/* The same under training (the T5 / ByT5 towers trained with the UNet).  _fwd_lse: the same kernel, same launch shape and the same bits in o,
+ * also writing lse fp32 [B][H][L], the natural-log sum-exp of the BIASED scores.  _bwd: dq, dk, dv (bf16, strides in d; dq / dk carry
+ * d->scale, the bias does not) and d_rel fp32 [H][2 L - 1], d_rel[h][key - query + L - 1] = sum over batch and queries of the fp32
+ * dS = P (dP - delta); accumulate 1 adds to d_rel (one tower sums every layer into one buffer), 0 overwrites.  No atomics: every sum has
+ * a fixed order, so all four outputs are bitwise reproducible.  ws: nk_attention_relbias_bwd_ws_floats(d) uninitialised floats.  Limits of
+ * the forward: Lq == Lk <= 1024, D % 8 == 0, D <= 160, !causal. */
+int nk_attention_relbias_fwd_lse(const NkAttnDesc* d, const void* q, const void* k, const void* v, void* o, float* lse, const float* rel, void* stream);
+long nk_attention_relbias_bwd_ws_floats(const NkAttnDesc* d);
+int nk_attention_relbias_bwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, const void* o, const float* lse, const void* d_o, void* dq,
+                             void* dk, void* dv, const float* rel, float* d_rel, float* ws, int accumulate, void* stream);
+/* relative_attention_bias.weight's gradient [num_buckets][H] from d_rel [H][2 L - 1]: d_weight[bucket][h] (+)= sum of d_rel[h][i] over the
+ * entries i with buckets[i] == bucket (int32 [2 L - 1]), i ascending.  accumulate 0: overwritten (unused buckets exactly 0); 1: added to;
+ * 2: written, the caller guarantees zeros. */
+int nk_relbias_bucket_sum(const float* d_rel, const int* buckets, float* d_weight, int H, int L, int num_buckets, int accumulate, void* stream);
 /* in-place row softmax on bf16 [M][L]: unfused single-head attention = nk_linear_fwd (q k^T) -> nk_softmax_rows -> nk_linear_dgrad (p v).
  * Serves head dims the flash kernels do not take, and the chunked recomputing backward of the VAE mid block (d = 512) beyond 2 048 tokens per
  * sample (ops.attention512_fwd; up to there nk_attention_bwd's flash kernels run); d = 512 forward and backward are nk_attention_fwd / _bwd. */
@@ -242,6 +256,14 @@ long nk_layernorm_ws_floats(int M, int C); /* `ws` of nk_layernorm_bwd and _bwd_
 /* T5LayerNorm (RMS norm: no mean subtraction, no bias), forward only: y[m][c] = x[m][c] * rsqrt(mean_c(x[m]^2) + eps) * gamma[c] on bf16
  * [M][C], fp32 gamma, C % 8 == 0, C <= 4096.  The fp32 reduction has a fixed order: a row's bits do not depend on M. */
 int nk_rmsnorm_fwd(const void* x, const float* gamma, void* y, int M, int C, float eps, void* stream);
+/* ... under training: _fwd_rstd also keeps rstd [M] fp32 (y has nk_rmsnorm_fwd's bits).  _bwd: dx = rstd (g o dy - xhat mean_c(g o dy o xhat))
+ * (+ dx_add, added in fp32 before the single rounding to bf16), xhat = x rstd, and dgamma[c] (+)= sum_m dy xhat through partial rows and the
+ * fixed-order column reducer (accumulate 0 / 1).  ws: nk_rmsnorm_bwd_ws_floats(M, C) floats.  C % 8 == 0, C <= 4096, any M; a row's dx does
+ * not depend on M. */
+int nk_rmsnorm_fwd_rstd(const void* x, const float* gamma, void* y, float* rstd, int M, int C, float eps, void* stream);
+long nk_rmsnorm_bwd_ws_floats(int M, int C);
+int nk_rmsnorm_bwd(const void* dy, const void* x, const float* gamma, const float* rstd, const void* dx_add, void* dx, float* dgamma, float* ws, int M, int C,
+                   int accumulate, void* stream);
 int nk_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                      const void* dx_add, void* dx, float* dgamma, float* dbeta, float* ws, int M, int C, int accumulate, void* stream);
 /* The one-pass form in its two halves (round 5: what the transformer blocks use): _rows writes dx and nk_layernorm_part_rows(M) partial rows
@@ -370,10 +392,15 @@ int nk_gelu_fwd(const void* x, void* y, long n, int mode, void* stream);
 int nk_gated_gelu_tanh_fwd(const void* u, void* y, long M, int I, void* stream);
 /* dx = dy * gelu'(x), same modes as nk_gelu_fwd; bf16 in and out, fp32 arithmetic (trainable text towers) */
 int nk_gelu_bwd(const void* dy, const void* x, void* dx, long n, int mode, void* stream);
+/* ... in all four modes of nk_gelu_fwd (2: gelu_new; 3: ReLU, dx = dy where x > 0, exactly): the T5 FeedForwards under training.
+ * nk_gated_gelu_tanh_bwd: du [M][2 I] = [dy b gelu_new'(a) | dy gelu_new(a)] from dy [M][I] and u = [a | b] (nk_gated_gelu_tanh_fwd's input). */
+int nk_act_bwd(const void* dy, const void* x, void* dx, long n, int mode, void* stream);
+int nk_gated_gelu_tanh_bwd(const void* dy, const void* u, void* du, long M, int I, void* stream);
 /* Token + position embedding backward of the text towers (x[b * L + l] = table[ids[b][l]] + pos[l]): dx [B * L][C] bf16 (row stride ldx);
  * dtable [V][C] and dpos [P][C] fp32 gradients.  accumulate 0: both are overwritten and rows no token (position) hit come out zero;
  * 1: added to; 2: written, the caller guarantees both are zero already (no clearing pass).  Deterministic: every row is a sum in token
- * order, no atomics.  ids int64 [B * L], 0 <= id < V; B * L <= NK_EMBEDDING_BWD_MAX_TOKENS (the duplicate-id scans are quadratic). */
+ * order, no atomics.  ids int64 [B * L], 0 <= id < V; B * L <= NK_EMBEDDING_BWD_MAX_TOKENS (the duplicate-id scans are quadratic).
+ * dpos == NULL with P == 0: no position table (the T5 encoders). */
 #define NK_EMBEDDING_BWD_MAX_TOKENS 8192
 int nk_embedding_bwd(const long long* ids, const void* dx, long ldx, float* dtable, float* dpos, int B, int L, int V, int P, int C,
                      int accumulate, void* stream);

@@ -18,6 +18,7 @@
 #include "../../include/neurosis_hip.h"
 #include "nk_common.h"
 #include "attn_plan.h"
+#include "nk_reduce.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -37,7 +38,10 @@ struct AttnParams {
   int qsplit;           // dK/dV kernel: workgroups per key block along the query range (partials in dkv_part)
   float* dkv_part;      // [qsplit][2][B][Lk][H*D] fp32 partial dK / dV when qsplit > 1
   int gx;               // > 0: the launch is a 1-D grid of gx * H * B workgroups and attn_wg() maps it XCD-aware; 0: the 3-D grid (x, head, batch)
-  const float* rel;     // attn_fwd_kernel<.., RELBIAS>: [H][Lq + Lk - 1] fp32, added to the scaled score of (query i, key j) at [h][j - i + Lq - 1]
+  const float* rel;     // RELBIAS instances: [H][Lq + Lk - 1] fp32, added to the scaled score of (query i, key j) at [h][j - i + Lq - 1]
+  float* drel_part;     // attn_bwd_dq_kernel<.., RELBIAS>: [B][H][query waves][attn_drel_width(Lk)] fp32 partial rows of d_rel
+  float* d_rel;         // attn_drel_reduce_kernel: [H][Lq + Lk - 1] fp32
+  int drel_acc;         // ... added to (1) or overwritten (0)
 };
 
 // Which (x block, head, batch item) this workgroup is.  Workgroups go to the eight XCDs round-robin in launch order.  With the plain 3-D grid
@@ -139,7 +143,9 @@ struct TileLoader {
 // only on j - i, so the head's whole table (Lq + Lk - 1 floats, 4 KiB at L = 512) sits in LDS behind the K / V ring; the score becomes
 // scale * s + bias in fp32 where the MASKED branch edits the raw scores, in front of the running max, and the softmax below runs on it with
 // scale 1.  No log-sum-exp leaves (no backward follows).  The other instances compile as before: every use is `if constexpr`.
-template <int DP, int NW = 4, bool RELBIAS = false>   // NW waves x 32 rows per workgroup (2: twice the workgroups for short sequences)
+// RB_LSE (nk_attention_relbias_fwd_lse: the T5 encoders under training): the RELBIAS instance also writes the log-sum-exp of the biased
+// scores, m + log l (m is already the maximum of scale * s + bias); everything else is the RELBIAS instance's code, so o has its bits.
+template <int DP, int NW = 4, bool RELBIAS = false, bool RB_LSE = false>   // NW waves x 32 rows per workgroup (2: twice the workgroups for short sequences)
 __global__ __launch_bounds__(NW * 64, 3) void attn_fwd_kernel(const AttnParams p) {
   constexpr int RS = DP * 2 + 16, KS = DP / 16, DT = DP / 32, TILE = 64 * RS;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages][K,V][64][RS] (RELBIAS: + [Lq + Lk - 1] floats)
@@ -375,6 +381,8 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_fwd_kernel(const AttnParams p
       }
     if constexpr (!RELBIAS) {
       if (h5 == 0) p.LSE[((long)b * p.H + hd) * p.Lq + q] = m * p.scale + logf(l);
+    } else if constexpr (RB_LSE) {
+      if (h5 == 0) p.LSE[((long)b * p.H + hd) * p.Lq + q] = m + logf(l);
     }
   }
 }
@@ -1390,18 +1398,25 @@ __global__ __launch_bounds__(256, 2) void attn64_bwd_small_kernel(const AttnPara
 // ================================================================================================
 // backward: dK, dV.  Workgroup = 128 keys (4 waves x 32 keys on lanes), loops over 32-query tiles.
 // ================================================================================================
-template <int DP, int NW = 4>   // NW waves x 32 rows per workgroup (2: twice the workgroups for short sequences)
+// RELBIAS (nk_attention_relbias_bwd): P = exp2((scale s + rel[h][key - query + Lq - 1]) log2 e - lse2) with the head's table in LDS behind the
+// two stages, as in the forward; dS = P (dP - delta) carries no bias term, dK carries `scale` as always.  Every use is `if constexpr`.
+template <int DP, int NW = 4, bool RELBIAS = false>   // NW waves x 32 rows per workgroup (2: twice the workgroups for short sequences)
 __global__ __launch_bounds__(NW * 64, 3) void attn_bwd_dkdv_kernel(const AttnParams p) {
   constexpr int RS = DP * 2 + 16, KS = DP / 16, DT = DP / 32, TILE = 32 * RS;
   constexpr int STAGE = 2 * TILE + 256;  // Q tile, dO tile, lse2[32], delta[32]
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages] (RELBIAS: + [Lq + Lk - 1] floats)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h5 = lane >> 5, kl = lane & 31;
   int bx, hd, b;
   attn_wg(p, bx, hd, b);
   const int kb = bx / p.qsplit, qs = bx - kb * p.qsplit;
   const int k0 = kb * (NW * 32) + wave * 32;
-  const float c = p.scale * LOG2E;
+  const float c = RELBIAS ? LOG2E : p.scale * LOG2E;
+  const float* relt = (const float*)(smem + 2 * STAGE);
+  if constexpr (RELBIAS) {      // (visible to every wave after the barrier that publishes the first query tile)
+    const int nrel = p.Lq + p.Lk - 1;
+    for (int i = tid; i < nrel; i += NW * 64) ((float*)(smem + 2 * STAGE))[i] = p.rel[(long)hd * nrel + i];
+  }
 
   const bf16_t* Qb = p.Q + (long)b * p.bq + (long)hd * p.D;
   const bf16_t* Kb = p.K + (long)b * p.bk + (long)hd * p.D;
@@ -1487,6 +1502,10 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_bwd_dkdv_kernel(const AttnPar
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int qr = acc_row(r, h5);
+      if constexpr (RELBIAS) {      // (key and query clamped into the table: such keys are never stored, such queries have P = 0)
+        const float* rk = relt + (p.Lq - 1 + min(k0 + kl, p.Lk - 1));
+        s[r] = fmaf(s[r], p.scale, rk[-min((t_lo + t) * 32 + qr, p.Lq - 1)]);
+      }
       float pv = EXP2(s[r] * c - s_lse[qr]);
       s[r] = pv;
       dp[r] = pv * (dp[r] - s_dl[qr]);          // (the softmax scale multiplies dK once, after the loop)
@@ -1588,20 +1607,56 @@ __global__ void attn_dkv_reduce_kernel(const AttnParams p) {
   }
 }
 
+// d_rel[h][i] (+)= sum over (batch, query wave) of the dQ kernel's partial rows, i = key - query + Lq - 1: wave w of the query range (queries
+// 32 w ...) keeps diagonal i at entry i - (Lq - 1) + 32 w + 31 of its row, where that is inside the row.  The single-writer reducer of
+// nk_reduce.h: rows = (batch, wave) in ascending order, one writer per entry -- bitwise reproducible.  Grid (ceil((Lq + Lk - 1) / 64), H).
+__global__ __launch_bounds__(1024) void attn_drel_reduce_kernel(const AttnParams p) {
+  const int nrel = p.Lq + p.Lk - 1, i = blockIdx.x * 64 + (threadIdx.x & 63), hd = blockIdx.y;
+  const int nqw = (p.Lq + ATTN_NW * 32 - 1) / (ATTN_NW * 32) * ATTN_NW, w = attn_drel_width(p.Lk);      // (attn_blocks(Lq) query blocks of ATTN_NW waves)
+  nk_reduce_rows<16, 64, 1, 0, 4>(
+      i < nrel, p.B * nqw,
+      [&](int r, float* a) {
+        const int b = r / nqw, qw = r - b * nqw;
+        const int e = i - (p.Lq - 1) + 32 * qw + 31;
+        if (e >= 0 && e < w) a[0] += p.drel_part[(((long)b * p.H + hd) * nqw + qw) * w + e];
+      },
+      [&](const float* a) {
+        float* out = p.d_rel + (long)hd * nrel + i;
+        *out = p.drel_acc ? *out + a[0] : a[0];
+      });
+}
+
 // ================================================================================================
 // backward: dQ.  Workgroup = 128 queries (on lanes), loops over 64-key tiles.
 // ================================================================================================
-template <int DP, int NW = 4>   // NW waves x 32 rows per workgroup (2: twice the workgroups for short sequences)
+__device__ __forceinline__ int gridDimQ(const AttnParams& p) { return p.gx ? p.gx : (int)gridDim.x; }      // query blocks of the launch
+// RELBIAS (nk_attention_relbias_bwd): P = exp2((scale s + rel[h][key - query + Lq - 1]) log2 e - lse2), the head's table in LDS behind the
+// ring as in the forward, and the gradient of the table, d_rel[h][key - query + Lq - 1] = sum over (batch, query) of the fp32 dS:
+// a lane owns one query row, so register r of a 32-key half holds, over lanes 0-31, 32 DIFFERENT diagonals key_r - ql, and over lanes
+// 32-63 the 32 diagonals of key_r + 4.  Each wave keeps two private LDS strips (one per lane half) indexed by key - ql + 31 and adds its
+// 16 values per half with plain read-modify-writes in program order (r ascending, tiles ascending; LDS operations of one wave execute in
+// order): no atomics, and a sum whose order is fixed by the shape alone.  At the end the wave writes strip 0 + strip 1 as one partial row;
+// attn_drel_reduce_kernel sums the rows over batch and query waves in a fixed order.  Every use is `if constexpr`.
+template <int DP, int NW = 4, bool RELBIAS = false>   // NW waves x 32 rows per workgroup (2: twice the workgroups for short sequences)
 __global__ __launch_bounds__(NW * 64, 3) void attn_bwd_dq_kernel(const AttnParams p) {
   constexpr int RS = DP * 2 + 16, KS = DP / 16, DT = DP / 32, TILE = 64 * RS;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // the ring (RELBIAS: + [Lq + Lk - 1] floats + [NW][2][attn_drel_width(Lk)] floats)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h5 = lane >> 5, ql = lane & 31;
   int bx, hd, b;
   attn_wg(p, bx, hd, b);
   const int q0 = bx * (NW * 32) + wave * 32;
   const int q = q0 + ql;
-  const float c = p.scale * LOG2E;
+  const float c = RELBIAS ? LOG2E : p.scale * LOG2E;
+  const int drel_w = attn_drel_width(p.Lk);
+  const float* relt = (const float*)(smem + 4 * TILE);
+  typedef __attribute__((address_space(3))) float lds_f;      // (LDS-typed: the strips' accesses are DS operations, which one wave executes in order)
+  lds_f* strip = (lds_f*)(float*)(smem + 4 * TILE + (((p.Lq + p.Lk - 1) * 4 + 15) & ~15)) + (wave * 2) * drel_w;      // this wave's two strips
+  if constexpr (RELBIAS) {      // (the table: visible to every wave after the barrier that publishes tile 0; the strips are the wave's own)
+    const int nrel = p.Lq + p.Lk - 1;
+    for (int i = tid; i < nrel; i += NW * 64) ((float*)(smem + 4 * TILE))[i] = p.rel[(long)hd * nrel + i];
+    for (int i = lane; i < 2 * drel_w; i += 64) ((volatile lds_f*)strip)[i] = 0.f;
+  }
 
   const bf16_t* Qb = p.Q + (long)b * p.bq + (long)hd * p.D;
   const bf16_t* Kb = p.K + (long)b * p.bk + (long)hd * p.D;
@@ -1676,12 +1731,24 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_bwd_dq_kernel(const AttnParam
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        if constexpr (RELBIAS) {      // (query and key clamped into the table: such queries have P = 0, such keys are masked below)
+          const float* rq = relt + (p.Lq - 1 - min(q, p.Lq - 1));
+          s[r] = fmaf(s[r], p.scale, rq[min(t * 64 + hf * 32 + acc_row(r, h5), p.Lk - 1)]);
+        }
         float pv = EXP2(s[r] * c - lse2);
         dp[r] = pv * (dp[r] - dlt);             // (the softmax scale multiplies dQ once, after the loop)
       }
       if constexpr (MASKED) {   // keys beyond Lk exist only in the last tile
 #pragma unroll
         for (int r = 0; r < 16; ++r) dp[r] = (t * 64 + hf * 32 + acc_row(r, h5)) < p.Lk ? dp[r] : 0.f;
+      }
+      if constexpr (RELBIAS) {
+        // d_rel: this lane half's strip, entry key - ql + 31 (>= 0, < drel_w: key < 64 nt).  For one r the 32 lanes of a half hit 32
+        // different entries; successive r may hit the same entry from another lane, so each read-modify-write is complete before the next
+        // (volatile accesses stay in program order).
+        volatile lds_f* sp = strip + h5 * drel_w + (t * 64 + hf * 32 + 31 - ql);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sp[acc_row(r, h5)] = sp[acc_row(r, h5)] + dp[r];
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
@@ -1711,6 +1778,10 @@ __global__ __launch_bounds__(NW * 64, 3) void attn_bwd_dq_kernel(const AttnParam
     for (; t < nt; ++t) iteration(t, T{}, F{});
   }
 
+  if constexpr (RELBIAS) {      // this wave's partial row: strip 0 + strip 1 (its own writes: no barrier)
+    float* row = p.drel_part + ((((long)b * p.H + hd) * gridDimQ(p) + bx) * NW + wave) * drel_w;
+    for (int i = lane; i < drel_w; i += 64) row[i] = ((volatile lds_f*)strip)[i] + ((volatile lds_f*)strip)[drel_w + i];
+  }
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -1774,6 +1845,8 @@ static AttnParams attn_params(const NkAttnDesc* d, const NkAttnPlan& pl, void* c
   p.causal = d->causal != 0;
   p.qsplit = pl.qsplit;
   p.dkv_part = pl.qsplit > 1 ? p.delta + pl.ws.part : nullptr;
+  p.d_rel = (float*)ptr[AP_DREL];
+  p.drel_part = p.d_rel ? p.delta + pl.ws.part : nullptr;      // (ATTN_PASS_BWD_RELBIAS: the partial rows behind delta)
   return p;
 }
 
@@ -1807,6 +1880,16 @@ static int attn_run(const NkAttnPlan& pl, AttnParams p, hipStream_t stream) {
       ATTN_KERNEL(AK_FWD_RELBIAS_DP64, attn_fwd_kernel<64, ATTN_NW, true>)
       ATTN_KERNEL(AK_FWD_RELBIAS_DP96, attn_fwd_kernel<96, ATTN_NW, true>)
       ATTN_KERNEL(AK_FWD_RELBIAS_DP160, attn_fwd_kernel<160, ATTN_NW, true>)
+      ATTN_KERNEL(AK_FWD_RELBIAS_LSE_DP64, attn_fwd_kernel<64, ATTN_NW, true, true>)
+      ATTN_KERNEL(AK_FWD_RELBIAS_LSE_DP96, attn_fwd_kernel<96, ATTN_NW, true, true>)
+      ATTN_KERNEL(AK_FWD_RELBIAS_LSE_DP160, attn_fwd_kernel<160, ATTN_NW, true, true>)
+      ATTN_KERNEL(AK_BWD_RELBIAS_DQ_DP64, attn_bwd_dq_kernel<64, ATTN_NW, true>)
+      ATTN_KERNEL(AK_BWD_RELBIAS_DQ_DP96, attn_bwd_dq_kernel<96, ATTN_NW, true>)
+      ATTN_KERNEL(AK_BWD_RELBIAS_DQ_DP160, attn_bwd_dq_kernel<160, ATTN_NW, true>)
+      ATTN_KERNEL(AK_BWD_RELBIAS_DKDV_DP64, attn_bwd_dkdv_kernel<64, ATTN_NW, true>)
+      ATTN_KERNEL(AK_BWD_RELBIAS_DKDV_DP96, attn_bwd_dkdv_kernel<96, ATTN_NW, true>)
+      ATTN_KERNEL(AK_BWD_RELBIAS_DKDV_DP160, attn_bwd_dkdv_kernel<160, ATTN_NW, true>)
+      ATTN_KERNEL(AK_DREL_REDUCE, attn_drel_reduce_kernel)
       ATTN_KERNEL(AK_DKV_REDUCE, attn_dkv_reduce_kernel)
       ATTN_KERNEL(AK_DELTA512, attn512_delta_kernel)
       ATTN_KERNEL(AK_BWD512_DQ, attn512_bwd_kernel<0>)
@@ -1820,7 +1903,7 @@ static int attn_run(const NkAttnPlan& pl, AttnParams p, hipStream_t stream) {
 
 // One pass: check the descriptor, plan, check what the plan says about shape and pointers, fill the parameters, launch.  In plan-only mode
 // (nk_debug_launch_log(3)) the plan is the answer: name and plan line per launch, and nothing touches the device or the pointers.
-static int attn_pass(const NkAttnDesc* d, int pass, void* const* ptr, void* stream) {
+static int attn_pass(const NkAttnDesc* d, int pass, void* const* ptr, void* stream, int drel_accumulate = 0) {
   if (int e = attn_check(d, pass)) return e;
   const NkAttnPlan pl = nk_attn_plan(d, pass, attn_env());
   if (pl.err) {
@@ -1839,7 +1922,9 @@ static int attn_pass(const NkAttnDesc* d, int pass, void* const* ptr, void* stre
     if (pl.need >> i & 1) NK_CHECK_ARG(ptr[i] != nullptr);
     if (pl.align16 >> i & 1) NK_CHECK_ARG(((uintptr_t)ptr[i] & 15) == 0);      // 16-byte loads and stores
   }
-  return attn_run(pl, attn_params(d, pl, ptr), (hipStream_t)stream);
+  AttnParams p = attn_params(d, pl, ptr);
+  p.drel_acc = drel_accumulate;
+  return attn_run(pl, p, (hipStream_t)stream);
 }
 
 extern "C" int nk_attention_fwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, void* o, float* lse,
@@ -1854,6 +1939,28 @@ extern "C" int nk_attention_relbias_fwd(const NkAttnDesc* d, const void* q, cons
                                         void* stream) {
   void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, o, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (void*)rel};
   return attn_pass(d, ATTN_PASS_FWD_RELBIAS, ptr, stream);
+}
+
+// ... and the log-sum-exp of the biased scores (natural log, fp32 [B][H][L]) for nk_attention_relbias_bwd; o has nk_attention_relbias_fwd's bits
+extern "C" int nk_attention_relbias_fwd_lse(const NkAttnDesc* d, const void* q, const void* k, const void* v, void* o, float* lse, const float* rel,
+                                            void* stream) {
+  void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, o, lse, nullptr, nullptr, nullptr, nullptr, nullptr, (void*)rel};
+  return attn_pass(d, ATTN_PASS_FWD_RELBIAS_LSE, ptr, stream);
+}
+
+// Backward of nk_attention_relbias_fwd_lse: dq, dk, dv (bf16, the caller's strides) and the gradient of the table, d_rel fp32 [H][2 L - 1]
+// (accumulate: added to, else overwritten), summed from the fp32 dS in a fixed order -- bitwise reproducible.  dq / dk carry d->scale, the
+// bias does not.  ws: nk_attention_relbias_bwd_ws_floats(d) floats.
+extern "C" long nk_attention_relbias_bwd_ws_floats(const NkAttnDesc* d) {
+  if (!d || d->B <= 0 || d->H <= 0 || d->Lq <= 0 || d->Lk <= 0) return -1;
+  return nk_attn_plan(d, ATTN_PASS_BWD_RELBIAS, AttnEnv{1, 1, 1}).ws.total;
+}
+extern "C" int nk_attention_relbias_bwd(const NkAttnDesc* d, const void* q, const void* k, const void* v, const void* o, const float* lse,
+                                        const void* d_o, void* dq, void* dk, void* dv, const float* rel, float* d_rel, float* ws, int accumulate,
+                                        void* stream) {
+  NK_CHECK_ARG(accumulate == 0 || accumulate == 1);
+  void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, (void*)o, (void*)lse, (void*)d_o, dq, dk, dv, ws, (void*)rel, d_rel};
+  return attn_pass(d, ATTN_PASS_BWD_RELBIAS, ptr, stream, accumulate);
 }
 
 extern "C" long nk_attention_bwd_ws_floats(const NkAttnDesc* d) { return attn_ws(d, d->D == 64).total; }
@@ -1871,4 +1978,25 @@ extern "C" int nk_attention_bwd_causal(const NkAttnDesc* d, const void* q, const
                                        const float* lse, const void* d_o, void* dq, void* dk, void* dv, void* stream) {
   void* const ptr[AP_N] = {(void*)q, (void*)k, (void*)v, (void*)o, (void*)lse, (void*)d_o, dq, dk, dv, nullptr};
   return attn_pass(d, ATTN_PASS_BWD_CAUSAL, ptr, stream);
+}
+
+// relative_attention_bias.weight's gradient from the table's: d_weight[bucket][h] (+)= sum over the table entries i with buckets[i] == bucket
+// of d_rel[h][i], i ascending (one thread per (bucket, head): a fixed order, bitwise reproducible).  accumulate as for the weight
+// gradients: 0 overwrite (a bucket no position pair maps to comes out exactly 0), 1 add, 2 write into a buffer the caller has zeroed.
+__global__ void relbias_bucket_sum_kernel(const float* __restrict__ d_rel, const int* __restrict__ buckets, float* __restrict__ d_weight, int H, int nrel,
+                                          int num_buckets, int accumulate) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= num_buckets * H) return;
+  const int bucket = t / H, h = t - bucket * H;
+  float acc = 0.f;
+  for (int i = 0; i < nrel; ++i)
+    if (buckets[i] == bucket) acc += d_rel[(long)h * nrel + i];
+  d_weight[t] = accumulate == 1 ? d_weight[t] + acc : acc;
+}
+extern "C" int nk_relbias_bucket_sum(const float* d_rel, const int* buckets, float* d_weight, int H, int L, int num_buckets, int accumulate, void* stream) {
+  NK_CHECK_ARG(d_rel && buckets && d_weight && H > 0 && L > 0 && L <= ATTN_RELBIAS_MAX_L && num_buckets > 0 && accumulate >= 0 && accumulate <= 2);
+  const int n = num_buckets * H;
+  hipLaunchKernelGGL(relbias_bucket_sum_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, d_rel, buckets, d_weight, H, 2 * L - 1, num_buckets,
+                     accumulate);
+  return nk_check_launch("relbias_bucket_sum_kernel");
 }

@@ -2,7 +2,7 @@
 //
 // Host-only: no kernel, no HIP call, no getenv, nothing but the descriptor (neurosis_hip.h), the constants below and libc, so a plan can be
 // computed (and is tested: tests/test_attn_plan_cpu.py) on a machine without a GPU, and a plain C++ program can include this file.  The entry
-// points (attention.hip: nk_attention_fwd, nk_attention_relbias_fwd, nk_attention_bwd, nk_attention_bwd_causal) check the descriptor, ask for the plan, check what the
+// points (attention.hip: nk_attention_fwd, nk_attention_relbias_fwd, nk_attention_relbias_fwd_lse, nk_attention_bwd, nk_attention_bwd_causal, nk_attention_relbias_bwd) check the descriptor, ask for the plan, check what the
 // plan says about the pointers, fill AttnParams once and walk the plan's launches; nk_attention_bwd_ws_floats answers from the same layout,
 // so the workspace a caller sizes and the offsets the kernels are given cannot disagree.  Every selection rule of the family lives here, in
 // the order nk_attn_plan applies them, with the measurements behind its thresholds; the switches arrive as an AttnEnv (attention.hip:
@@ -24,6 +24,11 @@ constexpr int attn_ring_smem(int dp) { return 2 * 2 * 64 * (dp * 2 + 16); }     
 #define ATTN_RELBIAS_MAX_L 1024                                           // nk_attention_relbias_fwd: tokens of the self-attention (an 8 KiB table at the limit)
 constexpr int attn_relbias_smem(int dp, int L) { return attn_ring_smem(dp) + (((2 * L - 1) * 4 + 15) & ~15); }      // attn_fwd_kernel<.., RELBIAS>: the ring + one head's table
 constexpr int attn_dkdv_smem(int dp) { return 2 * (2 * 32 * (dp * 2 + 16) + 256); } // attn_bwd_dkdv_kernel
+// attn_bwd_dq_kernel<.., RELBIAS>: behind the ring and the table, two strips of d_rel sums per wave (lanes 0-31 / 32-63), indexed by
+// key - query_in_wave + 31: attn_drel_width(L) floats each, a multiple of 64 so that every 64-key tile's rows stay inside
+constexpr int attn_drel_width(int L) { return ((L + 63) / 64) * 64 + 64; }
+constexpr int attn_relbias_dq_smem(int dp, int L) { return attn_relbias_smem(dp, L) + 4 * 2 * attn_drel_width(L) * 4; }
+constexpr int attn_relbias_dkdv_smem(int dp, int L) { return attn_dkdv_smem(dp) + (((2 * L - 1) * 4 + 15) & ~15); }
 #define SMALL_DSROW 72                               // bytes per row of the dS^T image [96 keys][32 queries] (64 + 8: conflict-free 8-byte writes)
 #define ATTN64_SMALL_SMEM (96 * 128 + 3 * (3 * 32 * 128 + 256 + 1024) + 2 * 96 * SMALL_DSROW)      // attn64_bwd_small_kernel: [K image][3 stages][2 dS^T buffers]
 #define ATTN512_FWD_SMEM (5 * 32 * 1024)             // attn512.h: K stages 0-2, V stages 0-1: all 160 KiB of the CU's LDS
@@ -47,17 +52,20 @@ struct AttnEnv {
   int attn64;    // NK_ATTN64: 0 = the generic kernels for head dim 64 as well (A/B switch of round 4)
   int small;     // NK_ATTN64_SMALL: 0 = cross-attention backward through the two-kernel path (A/B switch of round 4)
 };
-enum AttnPass { ATTN_PASS_FWD = 0, ATTN_PASS_BWD = 1, ATTN_PASS_BWD_CAUSAL = 2, ATTN_PASS_FWD_RELBIAS = 3 };
+enum AttnPass { ATTN_PASS_FWD = 0, ATTN_PASS_BWD = 1, ATTN_PASS_BWD_CAUSAL = 2, ATTN_PASS_FWD_RELBIAS = 3, ATTN_PASS_FWD_RELBIAS_LSE = 4, ATTN_PASS_BWD_RELBIAS = 5 };
 // the kernels and template instances the dispatch can select
 enum AttnKernel {
   AK_FWD64, AK_FWD_DP64, AK_FWD_DP96, AK_FWD_DP160, AK_FWD512,
   AK_BWD64_SMALL, AK_BWD64_SMALL_CAUSAL, AK_BWD64_DQ, AK_BWD64_DKDV,
   AK_BWD_DQ_DP64, AK_BWD_DQ_DP96, AK_BWD_DQ_DP160, AK_BWD_DKDV_DP64, AK_BWD_DKDV_DP96, AK_BWD_DKDV_DP160,
   AK_DKV_REDUCE, AK_DELTA512, AK_BWD512_DQ, AK_BWD512_DKDV,
-  AK_FWD_RELBIAS_DP64, AK_FWD_RELBIAS_DP96, AK_FWD_RELBIAS_DP160
+  AK_FWD_RELBIAS_DP64, AK_FWD_RELBIAS_DP96, AK_FWD_RELBIAS_DP160,
+  AK_FWD_RELBIAS_LSE_DP64, AK_FWD_RELBIAS_LSE_DP96, AK_FWD_RELBIAS_LSE_DP160,
+  AK_BWD_RELBIAS_DQ_DP64, AK_BWD_RELBIAS_DQ_DP96, AK_BWD_RELBIAS_DQ_DP160, AK_BWD_RELBIAS_DKDV_DP64, AK_BWD_RELBIAS_DKDV_DP96, AK_BWD_RELBIAS_DKDV_DP160,
+  AK_DREL_REDUCE
 };
 // the caller's pointers, as bits of NkAttnPlan::need / ::align16 and as indices of the array attn_params() takes
-enum AttnPtr { AP_Q = 0, AP_K, AP_V, AP_O, AP_LSE, AP_DO, AP_DQ, AP_DK, AP_DV, AP_WS, AP_REL, AP_N };
+enum AttnPtr { AP_Q = 0, AP_K, AP_V, AP_O, AP_LSE, AP_DO, AP_DQ, AP_DK, AP_DV, AP_WS, AP_REL, AP_DREL, AP_N };
 
 struct NkAttnLaunch {
   int kernel;             // AttnKernel
@@ -188,6 +196,33 @@ static NkAttnPlan nk_attn_plan(const NkAttnDesc* d, int pass, const AttnEnv& env
     if (!(d->Lq == d->Lk && d->Lk <= ATTN_RELBIAS_MAX_L)) { pl.err = "d->Lq == d->Lk && d->Lk <= ATTN_RELBIAS_MAX_L (relative-bias attention: self-attention over at most 1024 tokens)"; return pl; }
     attn_launch(pl, dp == 64 ? AK_FWD_RELBIAS_DP64 : dp == 96 ? AK_FWD_RELBIAS_DP96 : AK_FWD_RELBIAS_DP160, "attn_fwd_kernel<relbias>", attn_blocks(d->Lq), H, B,
                 ATTN_NW * 64, attn_relbias_smem(dp, d->Lk), xcd);
+    return pl;
+  }
+
+  if (pass == ATTN_PASS_FWD_RELBIAS_LSE || pass == ATTN_PASS_BWD_RELBIAS) {
+    // The T5 encoders under training.  Forward: the RELBIAS instance that also writes the log-sum-exp of the biased scores (same launch shape
+    // as ATTN_PASS_FWD_RELBIAS, same output bits).  Backward: the RELBIAS instances of the generic dQ and dK / dV kernels at every head dim
+    // (64 as well), then the fixed-order sum of the dQ kernel's d_rel partial rows.  Self-attention over at most 1024 tokens, so
+    // attn_qsplit() is 1: dK / dV leave directly.  Workspace: delta [B H L] | d_rel partials [B][H][query waves][attn_drel_width(L)].
+    const bool fwd = pass == ATTN_PASS_FWD_RELBIAS_LSE;
+    pl.need = ATTN_BITS_QKVO | attn_bits(AP_REL, AP_LSE) | (fwd ? 0 : ATTN_BITS_GRADS | attn_bits(AP_DO, AP_WS, AP_DREL));
+    if (d->causal) { pl.err = "!d->causal"; return pl; }
+    if (d->D > 160) { pl.err = "d->D <= 160"; return pl; }
+    if (!(d->Lq == d->Lk && d->Lk <= ATTN_RELBIAS_MAX_L)) { pl.err = "d->Lq == d->Lk && d->Lk <= ATTN_RELBIAS_MAX_L (relative-bias attention: self-attention over at most 1024 tokens)"; return pl; }
+    if (fwd) {
+      attn_launch(pl, dp == 64 ? AK_FWD_RELBIAS_LSE_DP64 : dp == 96 ? AK_FWD_RELBIAS_LSE_DP96 : AK_FWD_RELBIAS_LSE_DP160, "attn_fwd_kernel<relbias,lse>",
+                  attn_blocks(d->Lq), H, B, ATTN_NW * 64, attn_relbias_smem(dp, d->Lk), xcd);
+      return pl;
+    }
+    const long rows = (long)d->B * d->H * d->Lq;
+    pl.qsplit = 1;
+    pl.ws = NkAttnWs{0, -1, -1, (rows + 3) & ~3l, 0};
+    pl.ws.total = pl.ws.part + (long)d->B * d->H * attn_blocks(d->Lq) * ATTN_NW * attn_drel_width(d->Lk) + 64;
+    attn_launch(pl, dp == 64 ? AK_BWD_RELBIAS_DQ_DP64 : dp == 96 ? AK_BWD_RELBIAS_DQ_DP96 : AK_BWD_RELBIAS_DQ_DP160, "attn_bwd_dq_kernel<relbias>",
+                attn_blocks(d->Lq), H, B, ATTN_NW * 64, attn_relbias_dq_smem(dp, d->Lk), xcd);
+    attn_launch(pl, dp == 64 ? AK_BWD_RELBIAS_DKDV_DP64 : dp == 96 ? AK_BWD_RELBIAS_DKDV_DP96 : AK_BWD_RELBIAS_DKDV_DP160, "attn_bwd_dkdv_kernel<relbias>",
+                attn_blocks(d->Lk), H, B, ATTN_NW * 64, attn_relbias_dkdv_smem(dp, d->Lk), xcd);
+    attn_launch(pl, AK_DREL_REDUCE, "attn_drel_reduce_kernel", (unsigned)((2 * d->Lk - 1 + 63) / 64), H, 1, 1024, 0, false);
     return pl;
   }
 

@@ -174,9 +174,13 @@ struct GeluBwd {
       float d;
       if (MODE == 0) {
         d = 0.5f * (1.0f + erff(f[e] * 0.70710678118654752f)) + f[e] * 0.39894228040143268f * __expf(-0.5f * f[e] * f[e]);
-      } else {
+      } else if (MODE == 1) {
         const float sg = 1.0f / (1.0f + __expf(-1.702f * f[e]));
         d = sg + 1.702f * f[e] * sg * (1.0f - sg);
+      } else if (MODE == 2) {
+        d = dgelu_tanh(f[e]);
+      } else {
+        d = f[e] > 0.f ? 1.0f : 0.f;      // ReLU: dx = dy where x > 0, exactly
       }
       g[e] *= d;
     }
@@ -189,6 +193,39 @@ extern "C" int nk_gelu_bwd(const void* dy, const void* x, void* dx, long n, int 
   return nk_ew_mode<0, 1>(mode, [&](auto m) {
     return nk_ew_flat("gelu_bwd", stream, n >> 3, GeluBwd<decltype(m)::value>{(const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx});
   });
+}
+
+// The activations of the T5 FeedForwards under training: the same functor in all four modes of nk_gelu_fwd (2: "gelu_new", 3: ReLU).
+// (nk_gelu_bwd keeps its two modes: the CLIP towers' contract.)
+extern "C" int nk_act_bwd(const void* dy, const void* x, void* dx, long n, int mode, void* stream) {
+  NK_CHECK_ARG(dy && x && dx && n > 0 && (n & 7) == 0 && mode >= 0 && mode <= 3);
+  NK_CHECK_ARG(nk_aligned16(dy) && nk_aligned16(x) && nk_aligned16(dx));     // 16-byte accesses
+  return nk_ew_mode<0, 3>(mode, [&](auto m) {
+    return nk_ew_flat("act_bwd", stream, n >> 3, GeluBwd<decltype(m)::value>{(const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx});
+  });
+}
+// backward of nk_gated_gelu_tanh_fwd: du [M][2 I] = [dy b gelu_new'(a) | dy gelu_new(a)] from dy [M][I] and u = [a | b]; fp32 arithmetic, one
+// rounding to bf16 per element
+struct GatedGeluTanhBwd {
+  const bf16_t *dy, *u; bf16_t* du; int I;
+  __device__ void operator()(long, long row, int ch) const {
+    float g[8], a[8], b[8], da[8];
+    ew_load(dy + row * I + ch * 8, g);
+    ew_load(u + row * 2 * I + ch * 8, a);
+    ew_load(u + row * 2 * I + I + ch * 8, b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      da[e] = g[e] * b[e] * dgelu_tanh(a[e]);
+      b[e] = g[e] * gelu_tanh(a[e]);
+    }
+    ew_store(du + row * 2 * I + ch * 8, da);
+    ew_store(du + row * 2 * I + I + ch * 8, b);
+  }
+};
+extern "C" int nk_gated_gelu_tanh_bwd(const void* dy, const void* u, void* du, long M, int I, void* stream) {
+  NK_CHECK_ARG(dy && u && du && M > 0 && I > 0 && (I & 7) == 0);
+  NK_CHECK_ARG(nk_aligned16(dy) && nk_aligned16(u) && nk_aligned16(du));     // 16-byte accesses
+  return nk_ew_rows("gated_gelu_tanh_bwd_kernel", stream, M, I >> 3, GatedGeluTanhBwd{(const bf16_t*)dy, (const bf16_t*)u, (bf16_t*)du, I});
 }
 
 // ---- token + position embedding backward (trainable text towers) --------------------------------
@@ -241,15 +278,17 @@ __global__ void embedding_bwd_kernel(const long long* __restrict__ ids, const bf
 }
 extern "C" int nk_embedding_bwd(const long long* ids, const void* dx, long ldx, float* dtable, float* dpos, int B, int L, int V, int P, int C,
                                 int accumulate, void* stream_) {
-  NK_CHECK_ARG(ids && dx && dtable && dpos && B > 0 && L > 0 && L <= P && V > 0 && C > 0 && (C & 7) == 0 && (ldx & 7) == 0 && ldx >= C);
+  // (dpos == NULL with P == 0: an embedding without a position table -- the T5 encoders -- so no position workgroups are launched)
+  NK_CHECK_ARG(ids && dx && dtable && B > 0 && L > 0 && V > 0 && C > 0 && (C & 7) == 0 && (ldx & 7) == 0 && ldx >= C);
+  NK_CHECK_ARG(dpos ? L <= P : P == 0);
   NK_CHECK_ARG(nk_aligned16(dx) && nk_aligned16(dtable) && nk_aligned16(dpos));
   NK_CHECK_ARG((long)B * L <= NK_EMBEDDING_BWD_MAX_TOKENS && accumulate >= 0 && accumulate <= 2);     // (the id scans are quadratic in B * L)
   hipStream_t stream = (hipStream_t)stream_;
   if (accumulate == 0) {     // overwrite: rows no token (no position) hit are zero; (2: the caller's buffers are zero already)
     if (hipMemsetAsync(dtable, 0, (size_t)V * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
-    if (hipMemsetAsync(dpos, 0, (size_t)P * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
+    if (dpos && hipMemsetAsync(dpos, 0, (size_t)P * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
   }
-  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(B * L + L), dim3(128), 0, stream, ids, (const bf16_t*)dx, ldx, dtable, dpos, B * L, L, V, C,
+  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(B * L + (dpos ? L : 0)), dim3(128), 0, stream, ids, (const bf16_t*)dx, ldx, dtable, dpos, B * L, L, V, C,
                      accumulate == 1);
   return nk_check_launch("embedding_bwd");
 }

@@ -135,6 +135,12 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   const float z2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);      // 2 sqrt(2 / pi) (x + 0.044715 x^3)
   return x / (1.0f + __expf(-z2));
 }
+// its derivative: sg + x sg (1 - sg) z2'(x), sg = 1 / (1 + exp(-z2)), z2' = 2 sqrt(2 / pi) (1 + 3 * 0.044715 x^2)
+__device__ __forceinline__ float dgelu_tanh(float x) {
+  const float z2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);
+  const float sg = 1.0f / (1.0f + __expf(-z2));
+  return sg + x * sg * (1.0f - sg) * (1.5957691216057308f * (1.0f + 0.134145f * x * x));
+}
 
 // ---- for the entry points that run a plan of norm_plan.h (norm.hip, elementwise.hip) ----------------------------------------------------------
 // a refused shape is an argument error; in plan-only mode (nk_debug_launch_log(3)) the plan is the answer: name and plan line per launch,

@@ -836,9 +836,10 @@ __global__ __launch_bounds__(1024) void colpart_reduce_batch_kernel(const NkColp
 // One wavefront per row as in ln_fwd_kernel.  The sum of squares is a per-lane sum over the lane's chunks in chunk order, then the xor
 // butterfly: a fixed order that depends on C alone, so a row's bits do not depend on M or on which wave got the row.
 // ------------------------------------------------------------------------------------------------
-template <int NCH>
+// STAT (nk_rmsnorm_fwd_rstd: the T5 encoders under training) also keeps the row's rstd for the backward; y has the same bits.
+template <int NCH, bool STAT = false>
 __global__ __launch_bounds__(256) void rms_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma, bf16_t* __restrict__ y, int M, int C,
-                                                      float eps) {
+                                                      float eps, float* __restrict__ rstd) {
   const int lane = threadIdx.x & 63;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
@@ -859,6 +860,9 @@ __global__ __launch_bounds__(256) void rms_fwd_kernel(const bf16_t* __restrict__
       }
     }
     const float rs = rsqrtf(wave_sum(s) * invC + eps);
+    if constexpr (STAT) {
+      if (lane == 0) rstd[row] = rs;
+    }
 #pragma unroll
     for (int j = 0; j < NCH; ++j) {
       const int ch = lane + 64 * j;
@@ -875,6 +879,88 @@ __global__ __launch_bounds__(256) void rms_fwd_kernel(const bf16_t* __restrict__
       }
     }
   }
+}
+
+// RMSNorm backward: dx = rstd (g o dy - xhat mean_c(g o dy o xhat)) (+ dx_add), xhat = x rstd, in fp32 with ONE rounding to bf16 at the store
+// (dx_add is added in fp32 before it), and dgamma[c] = sum_m dy xhat.  One wavefront per row; wave w of `nw` walks rows w, w + nw, ... and
+// keeps its column sums of dy xhat in registers (rows ascending), then writes them as partial row w: rms_colpart_reduce_kernel sums the rows
+// in a fixed order.  The row mean is a per-lane sum in chunk order then the xor butterfly, as in the forward: a row's dx does not depend on M.
+template <int NCH>
+__global__ __launch_bounds__(256) void rms_bwd_rows_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const float* __restrict__ gamma,
+                                                           const float* __restrict__ rstd, const bf16_t* __restrict__ dx_add, bf16_t* __restrict__ dx,
+                                                           float* __restrict__ part, int M, int C, int nw) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (wave >= nw) return;
+  const int cpr = C >> 3;
+  const float invC = 1.0f / (float)C;
+  float gm[NCH][8], sg[NCH][8];
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+    const int ch = lane + 64 * j;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { gm[j][e] = 0.f; sg[j][e] = 0.f; }
+    if (ch < cpr) {
+      const float4_t g0 = *(const float4_t*)(gamma + ch * 8), g1 = *(const float4_t*)(gamma + ch * 8 + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { gm[j][e] = g0[e]; gm[j][4 + e] = g1[e]; }
+    }
+  }
+  for (int row = wave; row < M; row += nw) {
+    uint4_t rx[NCH], rd[NCH];
+    const float rs = rstd[row];
+    float s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int ch = lane + 64 * j;
+      rx[j] = rd[j] = (uint4_t){0u, 0u, 0u, 0u};
+      if (ch < cpr) {
+        rx[j] = *(const uint4_t*)(x + (long)row * C + ch * 8);
+        rd[j] = *(const uint4_t*)(dy + (long)row * C + ch * 8);
+      }
+      float fx[8], fd[8];
+      unpack8(rx[j], fx);
+      unpack8(rd[j], fd);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {      // lanes past the row hold zeros, so they add nothing
+        const float xh = fx[e] * rs;
+        s2 += fd[e] * gm[j][e] * xh;
+        sg[j][e] += fd[e] * xh;
+      }
+    }
+    s2 = wave_sum(s2) * invC;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      const int ch = lane + 64 * j;
+      if (ch < cpr) {
+        float fx[8], fd[8], o[8];
+        unpack8(rx[j], fx);
+        unpack8(rd[j], fd);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = 0.f;
+        if (dx_add) unpack8(*(const uint4_t*)(dx_add + (long)row * C + ch * 8), o);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] += rs * (fd[e] * gm[j][e] - fx[e] * rs * s2);
+        *(uint4_t*)(dx + (long)row * C + ch * 8) = pack8(o);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+    const int ch = lane + 64 * j;
+    if (ch < cpr) {
+      float* out = part + (long)wave * C + ch * 8;
+      *(float4_t*)out = (float4_t){sg[j][0], sg[j][1], sg[j][2], sg[j][3]};
+      *(float4_t*)(out + 4) = (float4_t){sg[j][4], sg[j][5], sg[j][6], sg[j][7]};
+    }
+  }
+}
+// dgamma[c] (+)= sum_rows part[row][c]: colpart_reduce_kernel's block shape and order (nk_reduce_rows) for one value per column
+__global__ __launch_bounds__(1024) void rms_colpart_reduce_kernel(const float* __restrict__ part, float* __restrict__ dgamma, int nrows, int C, int accumulate) {
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  nk_reduce_rows<16, 64, 1, 0, 4>(
+      c < C, nrows, [&](int r, float* a) { a[0] += part[(long)r * C + c]; },
+      [&](const float* a) { dgamma[c] = accumulate ? dgamma[c] + a[0] : a[0]; });
 }
 
 // ---- LayerNorm / RMSNorm / column partials, host side: one runner -- plan (norm_plan.h: nk_rownorm_plan), check the pointers the kind needs,
@@ -896,7 +982,9 @@ static int rownorm_run(int kind, bool ptrs, const RowNormArgs& a, int M, int C, 
   const NkRowNormPlan p = nk_rownorm_plan(M, C, kind);
   NORM_PLAN_OR_RETURN(p);
   NK_CHECK_ARG(ptrs && "a required pointer argument is null");
-  if (kind == RMS_FWD) NK_CHECK_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.out & 15) == 0 && ((uintptr_t)a.gamma & 15) == 0);     // 16-byte accesses
+  if (kind == RMS_FWD || kind == RMS_FWD_RSTD || kind == RMS_BWD)
+    NK_CHECK_ARG(((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.out & 15) == 0 && ((uintptr_t)a.gamma & 15) == 0 && ((uintptr_t)a.dy & 15) == 0 &&
+                 ((uintptr_t)a.dx_add & 15) == 0 && ((uintptr_t)a.part & 15) == 0);     // 16-byte accesses
   const bf16_t *dy = (const bf16_t*)a.dy, *x = (const bf16_t*)a.x, *dx_add = (const bf16_t*)a.dx_add;
   bf16_t* out = (bf16_t*)a.out;
   float* part = a.part + p.part.off;
@@ -906,7 +994,17 @@ static int rownorm_run(int kind, bool ptrs, const RowNormArgs& a, int M, int C, 
       case NK_LN_FWD:
         nch_dispatch<2, 3, 4>(p.nch, [&](auto n) { NORM_LAUNCH(L, ln_fwd_kernel<decltype(n)::value>, x, a.gamma, a.beta, out, (float*)a.mean, (float*)a.rstd, M, C, eps); });
         break;
-      case NK_RMS_FWD: nch_dispatch<2, 4, 8>(p.nch, [&](auto n) { NORM_LAUNCH(L, rms_fwd_kernel<decltype(n)::value>, x, a.gamma, out, M, C, eps); }); break;
+      case NK_RMS_FWD:
+        if (kind == RMS_FWD_RSTD) nch_dispatch<2, 4, 8>(p.nch, [&](auto n) {
+          auto kern = rms_fwd_kernel<decltype(n)::value, true>;
+          NORM_LAUNCH(L, kern, x, a.gamma, out, M, C, eps, (float*)a.rstd);
+        });
+        else nch_dispatch<2, 4, 8>(p.nch, [&](auto n) { NORM_LAUNCH(L, rms_fwd_kernel<decltype(n)::value>, x, a.gamma, out, M, C, eps, (float*)nullptr); });
+        break;
+      case NK_RMS_BWD_ROWS:
+        nch_dispatch<2, 4, 8>(p.nch, [&](auto n) { NORM_LAUNCH(L, rms_bwd_rows_kernel<decltype(n)::value>, dy, x, a.gamma, a.rstd, dx_add, out, part, M, C, p.nrows); });
+        break;
+      case NK_RMS_COLPART: NORM_LAUNCH(L, rms_colpart_reduce_kernel, part, a.dgamma, p.nrows, C, accumulate); break;
       case NK_LN_BWD_DX:
         // input gradient: one wavefront per row.  (Fewer, longer-lived workgroups -- a grid capped at 256 / 512 / 1024 blocks with the rows
         // strided over them -- make no difference beside the weight-gradient stream: 180.4 / 180.3 / 180.2 vs 180.1 ms per step.)
@@ -935,6 +1033,16 @@ extern "C" int nk_layernorm_fwd(const void* x, const float* gamma, const float* 
 }
 extern "C" int nk_rmsnorm_fwd(const void* x, const float* gamma, void* y, int M, int C, float eps, void* stream) {
   return rownorm_run(RMS_FWD, x && gamma && y, {nullptr, x, nullptr, gamma, nullptr, nullptr, nullptr, y}, M, C, eps, 0, stream);
+}
+// ... keeping rstd [M] for nk_rmsnorm_bwd (y: nk_rmsnorm_fwd's bits)
+extern "C" int nk_rmsnorm_fwd_rstd(const void* x, const float* gamma, void* y, float* rstd, int M, int C, float eps, void* stream) {
+  return rownorm_run(RMS_FWD_RSTD, x && gamma && y && rstd, {nullptr, x, nullptr, gamma, nullptr, nullptr, rstd, y}, M, C, eps, 0, stream);
+}
+extern "C" long nk_rmsnorm_bwd_ws_floats(int M, int C) { return nk_rownorm_plan(M, C, RMS_BWD).ws_floats; }
+extern "C" int nk_rmsnorm_bwd(const void* dy, const void* x, const float* gamma, const float* rstd, const void* dx_add, void* dx, float* dgamma, float* ws, int M,
+                              int C, int accumulate, void* stream) {
+  return rownorm_run(RMS_BWD, dy && x && gamma && rstd && dx && dgamma && ws, {dy, x, dx_add, gamma, nullptr, nullptr, rstd, dx, dgamma, nullptr, ws}, M, C, 0.f,
+                     accumulate, stream);
 }
 /* The backward in two parts, so the caller can run the parameter gradients (off the critical path) on another stream ... */
 extern "C" int nk_layernorm_bwd_dx(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, const void* dx_add, void* dx, int M, int C,

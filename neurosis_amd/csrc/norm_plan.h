@@ -23,6 +23,7 @@
 #define LNR_WAVES 4                  // ln_bwd_rows_kernel: waves per block (8 waves x 2 rows: 10.2 vs 11.1 us alone at 4096 x 1280, 20.5 vs 18.0 at 16384 x 640, and the smaller A/B gain in the step)
 #define LNR_MAX_BLOCKS 512           // ... and its grid limit: one partial row per block
 #define LNR_MAX_SMEM (2 * 2 * 2048 * 4)
+#define RMSB_MAX_ROWS 512            // rms_bwd_rows_kernel: one partial row of dgamma per wave, at most this many waves
 #define CS_ROWS 64                   // colsum_partial_kernel: rows per block up to CS_MAX_SPLIT * 64 rows
 #define CS_MAX_SPLIT 1024
 #define NORM_WS_PAD 64               // floats every workspace query adds behind the layout
@@ -30,7 +31,8 @@
 // the kernels the runners can launch
 enum NormKernel {
   NK_GN_STATS, NK_GN_REDUCE, NK_GN_REDUCE_L1, NK_GN_APPLY, NK_GN_BWD_STATS, NK_GN_COLPART, NK_GN_COLPART_MOD, NK_GN_DMOD, NK_GN_BWD_APPLY,
-  NK_LN_FWD, NK_LN_BWD_DX, NK_LN_BWD_PARAM, NK_LN_BWD_ROWS, NK_LN_COLPART, NK_RMS_FWD, NK_COLPART_BATCH, NK_CS_PARTIAL, NK_CS_REDUCE
+  NK_LN_FWD, NK_LN_BWD_DX, NK_LN_BWD_PARAM, NK_LN_BWD_ROWS, NK_LN_COLPART, NK_RMS_FWD, NK_COLPART_BATCH, NK_CS_PARTIAL, NK_CS_REDUCE,
+  NK_RMS_BWD_ROWS, NK_RMS_COLPART
 };
 struct NkNormRegion { const char* name; long off, len; };      // floats of the workspace; len 0: not used
 struct NkNormLaunch {
@@ -141,7 +143,7 @@ static inline NkGnSumsPlan nk_gn_sums_plan(int N, int nparts, int G) {
 }
 
 // ---- LayerNorm and RMSNorm over the last dim of [M][C] -----------------------------------------------------------------------------------------
-enum RowNormKind { LN_FWD, LN_BWD_DX, LN_BWD_PARAMS, LN_BWD_ROWS, LN_BWD, RMS_FWD };
+enum RowNormKind { LN_FWD, LN_BWD_DX, LN_BWD_PARAMS, LN_BWD_ROWS, LN_BWD, RMS_FWD, RMS_FWD_RSTD, RMS_BWD };
 struct NkRowNormPlan : NkNormPlan {
   int nch;                // the chunks-per-lane instance: 2, 3 or 4 (LayerNorm), 2, 4 or 8 (RMSNorm); 0: ln_bwd_param_kernel has none
   int part_rows;          // partial rows of ln_bwd_rows_kernel (one per block)
@@ -151,11 +153,12 @@ struct NkRowNormPlan : NkNormPlan {
 };
 static inline NkRowNormPlan nk_rownorm_plan(int M, int C, int kind) {
   NkRowNormPlan p = {};
-  const int maxch = kind == RMS_FWD ? RMS_MAXCH : LN_MAXCH;
+  const bool rms = kind == RMS_FWD || kind == RMS_FWD_RSTD || kind == RMS_BWD;
+  const int maxch = rms ? RMS_MAXCH : LN_MAXCH;
   if (!(M > 0 && C > 0 && (C & 7) == 0)) { p.err = "M > 0 && C > 0 && (C & 7) == 0"; return p; }
   const int need = ((C >> 3) + 63) / 64;
   if (kind == LN_BWD_PARAMS) p.nch = 0;
-  else if (kind == RMS_FWD) p.nch = need <= 2 ? 2 : (need <= 4 ? 4 : 8);
+  else if (rms) p.nch = need <= 2 ? 2 : (need <= 4 ? 4 : 8);
   else p.nch = need <= 2 ? 2 : need;
   p.param_split = (M + LNP_ROWS - 1) / LNP_ROWS;
   // one block per 16 rows (four per wave), at most 512 blocks (two per CU; 8 rows per wave at M = 16384)
@@ -168,9 +171,19 @@ static inline NkRowNormPlan nk_rownorm_plan(int M, int C, int kind) {
   p.nrows = !has_ws ? 0 : (kind == LN_BWD_PARAMS ? p.param_split : p.part_rows);
   p.part = {"part", 0, (long)p.nrows * 2 * C};
   p.ws_floats = !has_ws ? 0 : kind == LN_BWD_ROWS ? p.part.len : (long)(p.param_split > LNR_MAX_BLOCKS ? p.param_split : LNR_MAX_BLOCKS) * 2 * C + NORM_WS_PAD;
-  if (kind != LN_BWD_PARAMS && (C >> 3) > 64 * maxch) { p.err = kind == RMS_FWD ? "(C >> 3) <= 64 * RMS_MAXCH" : "(C >> 3) <= 64 * LN_MAXCH"; return p; }
+  if (kind != LN_BWD_PARAMS && (C >> 3) > 64 * maxch) { p.err = rms ? "(C >> 3) <= 64 * RMS_MAXCH" : "(C >> 3) <= 64 * LN_MAXCH"; return p; }
+  if (kind == RMS_BWD) {
+    // RMSNorm backward (nk_rmsnorm_bwd): one wave per row, wave w walks rows w, w + nrows, ...; each wave leaves ONE partial row [C] of dgamma
+    // in the workspace, and the single-writer reducer sums the rows in ascending order
+    p.nrows = M < RMSB_MAX_ROWS ? M : RMSB_MAX_ROWS;
+    p.part = {"part", 0, (long)p.nrows * C};
+    p.ws_floats = p.part.len + NORM_WS_PAD;
+    norm_launch(p, NK_RMS_BWD_ROWS, "rms_bwd_rows_kernel", (unsigned)((p.nrows + 3) / 4), 1, 1, 256, 0, p.part);
+    norm_launch(p, NK_RMS_COLPART, "rms_colpart_reduce_kernel", cb, 1, 1, 1024, 0, p.part);
+    return p;
+  }
   if (kind == LN_FWD) norm_launch(p, NK_LN_FWD, "ln_fwd_kernel", rowgrid, 1, 1, 256, 0);
-  if (kind == RMS_FWD) norm_launch(p, NK_RMS_FWD, "rms_fwd_kernel", rowgrid, 1, 1, 256, 0);
+  if (kind == RMS_FWD || kind == RMS_FWD_RSTD) norm_launch(p, NK_RMS_FWD, "rms_fwd_kernel", rowgrid, 1, 1, 256, 0);
   if (kind == LN_BWD_DX) norm_launch(p, NK_LN_BWD_DX, "ln_bwd_dx_kernel", rowgrid, 1, 1, 256, 0);
   if (kind == LN_BWD_PARAMS) norm_launch(p, NK_LN_BWD_PARAM, "ln_bwd_param_kernel", (unsigned)p.param_split, (unsigned)((C + 127) / 128), 1, 256, 0, p.part);
   if (kind == LN_BWD_ROWS || kind == LN_BWD)

@@ -64,6 +64,9 @@ SIGNATURES: dict[str, list] = {
     "nk_attention_bwd": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "nk_attention_bwd_causal": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "nk_attention_relbias_fwd": [adp, vp, vp, vp, vp, vp, vp],
+    "nk_attention_relbias_fwd_lse": [adp, vp, vp, vp, vp, vp, vp, vp],
+    "nk_attention_relbias_bwd": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
+    "nk_relbias_bucket_sum": [vp, vp, vp, i32, i32, i32, i32, vp],
     "nk_softmax_rows": [vp, i64, i32, vp],
     "nk_softmax_rows_bwd": [vp, vp, i64, i32, f32, vp],
     "nk_groupnorm_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
@@ -76,6 +79,8 @@ SIGNATURES: dict[str, list] = {
     "nk_groupnorm_mod_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "nk_layernorm_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp],
     "nk_rmsnorm_fwd": [vp, vp, vp, i32, i32, f32, vp],
+    "nk_rmsnorm_fwd_rstd": [vp, vp, vp, vp, i32, i32, f32, vp],
+    "nk_rmsnorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "nk_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "nk_layernorm_bwd_dx": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
     "nk_layernorm_bwd_rows": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
@@ -89,6 +94,8 @@ SIGNATURES: dict[str, list] = {
     "nk_gelu_fwd": [vp, vp, i64, i32, vp],
     "nk_gated_gelu_tanh_fwd": [vp, vp, i64, i32, vp],
     "nk_gelu_bwd": [vp, vp, vp, i64, i32, vp],
+    "nk_act_bwd": [vp, vp, vp, i64, i32, vp],
+    "nk_gated_gelu_tanh_bwd": [vp, vp, vp, i64, i32, vp],
     "nk_embedding_bwd": [vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "nk_gather_rows_bwd": [vp, i64, vp, vp, i32, i32, i32, vp],
     "nk_wgrad_few_rows": [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
@@ -171,6 +178,8 @@ SIZE_QUERIES: dict[str, list] = {
     "nk_batchnorm_ws_floats": [i64, i32],
     "nk_lpips_layer_ws_floats": [i32, i32],
     "nk_attention_bwd_ws_floats": [adp],
+    "nk_attention_relbias_bwd_ws_floats": [adp],
+    "nk_rmsnorm_bwd_ws_floats": [i32, i32],
     "nk_vq_search_ws_floats": [i64, i32],
     "nk_vq_quantize_ws_floats": [i64],
     "nk_gumbel_softmax_ws_floats": [i64],

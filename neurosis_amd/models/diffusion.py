@@ -134,7 +134,7 @@ class DiffusionEngine(nn.Module):
             return
         for e in tr:
             if not hasattr(e, "trained_parameters"):
-                raise NotImplementedError(f"trainable embedder {type(e).__name__}: only the CLIP text towers have a training chain")
+                raise NotImplementedError(f"trainable embedder {type(e).__name__}: it has no training chain (no trained_parameters): the CLIP text towers and the T5 / ByT5 embedders have one")
         if self.stream_optimizer:
             raise NotImplementedError("stream_optimizer (the update streamed block by block behind backward) does not drive the text towers' groups")
         import torch.distributed as dist

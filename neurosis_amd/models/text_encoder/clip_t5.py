@@ -23,7 +23,8 @@ class FrozenCLIPT5Encoder(AbstractEmbModel):
                  clip_config: Optional[dict] = None, t5_config: Optional[dict] = None, **kwargs):
         super().__init__(**kwargs)
         if self.is_trainable:
-            raise NotImplementedError("FrozenCLIPT5Encoder(is_trainable=True): its T5 encoder is frozen only (no training chain)")
+            raise NotImplementedError("FrozenCLIPT5Encoder(is_trainable=True): its two encoders freeze themselves whatever the flag (as in the reference); "
+                                      "train a FrozenT5Embedder / FrozenByT5Embedder (is_trainable=True, freeze=False) or a FrozenCLIPEmbedder instead")
         self.clip_encoder = FrozenCLIPEmbedder(clip_version, device, max_length=clip_max_length, config=clip_config)
         self.t5_encoder = FrozenT5Embedder(t5_version, max_length=t5_max_length, config=t5_config)
         count = lambda m: sum(p.numel() for p in m.parameters())      # noqa: E731

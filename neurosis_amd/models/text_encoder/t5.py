@@ -18,9 +18,17 @@ Projections carry no bias; num_heads * d_kv need not equal d_model (t5-v1.1-smal
     encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight, encoder.block.N.layer.1.{DenseReluDense.{wi_0,wi_1,wo}.weight
     (or wi), layer_norm.weight}, encoder.final_layer_norm.weight
 
-The towers are frozen only: the forward runs under no_grad (replayed from hipGraphs under NK_GRAPH "te", as the frozen CLIP towers), there
-is no training chain, and is_trainable=True is refused.  A frozen tower keeps its fp32 parameters plus one bf16 copy of every matrix the
-kernels read (6 bytes per parameter: ~28 GB at T5-v1.1-XXL's 4.7 B encoder parameters).
+Frozen (the default), the forward runs under no_grad (replayed from hipGraphs under NK_GRAPH "te", as the frozen CLIP towers).  A frozen
+tower keeps its fp32 parameters plus one bf16 copy of every matrix the kernels read (6 bytes per parameter: ~28 GB at T5-v1.1-XXL's 4.7 B
+encoder parameters).
+
+Trained with the UNet (`is_trainable: true` and `freeze: false` in the conditioner config, the reference's condition), the embedder's forward
+runs `T5EncoderTower.train_outputs`: the same kernels and the same bits as the frozen forward, autograd-connected through nn.apply_module to
+one closure chain -- per block rmsnorm_fwd, the stacked q / k / v projection, attention_relbias_train, the o projection with residual,
+rmsnorm_fwd, the stacked wi projection, gated_act_fwd, wo with residual; then the final rmsnorm.  Every layer's backward adds its gradient
+of the bias table into ONE d_rel [heads, 2 L - 1]; after block 0's backward ops.relbias_bucket_sum folds it into
+relative_attention_bias.weight's gradient, once, and ops.embedding_bwd writes the (tied) embedding's.  DiffusionEngine gives the tower a
+FlatParamStore and an optimizer group of its own, as it does for the CLIP towers.
 """
 from __future__ import annotations
 
@@ -36,7 +44,8 @@ from torch import Tensor, nn
 from ... import ops
 from ...graphs import frozen_stamp
 from ...modules.encoders.embedding import AbstractEmbModel
-from .clip import _check_ids, _decode_text, _forward_graphs, _graphable
+from ...nn import apply_module
+from .clip import _chain_train, _check_ids, _decode_text, _forward_graphs, _graphable, _out_grads, _trainable
 
 logger = logging.getLogger(__name__)
 
@@ -78,6 +87,27 @@ class _Stacked:
         if self.weight is None or self.stamp != stamp:
             self.weight, self.stamp = _bf16_rows([l.weight for l in self.layers]), stamp
         return self.weight
+
+
+def _stacked_train(h: Tensor, stacked: _Stacked):
+    """(h @ stacked^T, bwd(dy) -> dh) for the projections `stacked` holds by rows: ONE GEMM on the frozen forward's stacked bf16 matrix (so
+    the same bits), the input gradient through the same matrix, and each projection's weight gradient from its column slice of dy, written
+    to its own .grad in the parameter's engine mode"""
+    w = stacked()
+    y = ops.gemm_nt(h, w)
+
+    def bwd(dy: Tensor) -> Tensor:
+        def wgrads():
+            off = 0
+            for lin in stacked.layers:
+                n = lin.weight.shape[0]
+                ops.gemm_tn_f32(dy[:, off:off + n], h, ops.g2d(lin.weight), ops.wgrad_mode(lin.weight))
+                off += n
+
+        ops.on_wgrad_stream(wgrads, dy, h, owner=stacked.layers[0].weight)
+        return ops.gemm_nn(dy, w)
+
+    return y, bwd
 
 
 class T5LayerNorm(nn.Module):
@@ -198,6 +228,61 @@ class T5EncoderTower(nn.Module):
             x = ops.gemm_nt(hidden, dense._wo(), residual=x)
         return {"last_hidden_state": self.encoder.final_layer_norm(x).float().reshape(B, L, -1)}
 
+    def _block_train(self, x: Tensor, block: _Block, B: int, rel: Tensor, d_rel: Tensor):
+        """one block of _forward_ids with its backward: (x', bwd(dx') -> dx); the attention's backward adds into d_rel"""
+        att, ff = block.layer[0], block.layer[1]
+        sa, dense = att.SelfAttention, ff.DenseReluDense
+        inner = self.heads * self.d_kv
+        h1, b_ln1 = ops.rmsnorm_fwd(x, att.layer_norm.weight, att.layer_norm.variance_epsilon)
+        fused, b_qkv = _stacked_train(h1, sa._qkv)
+        attended, b_att = ops.attention_relbias_train(fused[:, :inner], fused[:, inner:2 * inner], fused[:, 2 * inner:], B, self.heads, self.d_kv, rel, 1.0, d_rel)
+        x1, b_o = ops.linear_fwd(attended, sa.o.weight, None, residual=x)
+        h2, b_ln2 = ops.rmsnorm_fwd(x1, ff.layer_norm.weight, ff.layer_norm.variance_epsilon)
+        u, b_wi = _stacked_train(h2, dense._wi)
+        hidden, b_act = ops.gated_act_fwd(u, self.act)
+        x2, b_wo = ops.linear_fwd(hidden, dense.wo.weight, None, residual=x1)
+
+        def bwd(dx2: Tensor) -> Tensor:
+            dx1 = b_ln2(b_wi(b_act(b_wo(dx2))), dx_add=dx2)
+            dfused = torch.empty_like(fused)
+            b_att(b_o(dx1), dq=dfused[:, :inner], dk=dfused[:, inner:2 * inner], dv=dfused[:, 2 * inner:])
+            return b_ln1(b_qkv(dfused), dx_add=dx1)
+
+        return x2, bwd
+
+    def train_outputs(self, input_ids: Tensor) -> Tensor:
+        """The training forward, autograd-connected through nn.apply_module: fp32 [B, L, d_model] with forward()'s values (the same kernels
+        on the same bf16 matrices).  Its backward writes every parameter's .grad in the parameter's engine mode; the tied embedding
+        (shared.weight = encoder.embed_tokens.weight) is one parameter with one gradient."""
+        ids = _check_ids(input_ids, self.shared.weight.device)
+        if ids.dim() != 2:
+            raise ValueError(f"token ids must be [batch, length], got {tuple(ids.shape)}")
+        if ids.numel() > ops.EMBEDDING_BWD_MAX_TOKENS:
+            raise NotImplementedError(f"T5EncoderTower.train_outputs: at most {ops.EMBEDDING_BWD_MAX_TOKENS} tokens per batch (the embedding backward's "
+                                      f"limit), got {tuple(ids.shape)}")
+
+        def run(ids):
+            B, L = ids.shape
+            rel = self.rel_table(L)
+            d_rel = torch.zeros_like(rel)      # every layer's backward adds into it
+            table = self.shared.weight
+            x = ops.cast_bf16(table[ids].reshape(-1, table.shape[1]).float())
+            blocks = [lambda h, blk=blk: self._block_train(h, blk, B, rel, d_rel) for blk in self.encoder.block]
+            _, top, b_chain = _chain_train(x, blocks, set())
+            norm = self.encoder.final_layer_norm
+            y, b_final = ops.rmsnorm_fwd(top, norm.weight, norm.variance_epsilon)
+
+            def bwd(gout):
+                dx = b_chain({}, b_final(_out_grads([gout], 1)[0]))
+                bias = self.encoder.block[0].layer[0].SelfAttention.relative_attention_bias.weight
+                ops.relbias_bucket_sum(d_rel, relative_buckets(L, self.num_buckets, self.max_distance), bias)
+                ops.embedding_bwd(ids.contiguous(), dx, table, None)
+                return None
+
+            return y.float().reshape(B, L, -1), bwd
+
+        return apply_module(run, [ids], self)
+
 
 # ---------------------------------------------------------------------------------------------------
 # embedders
@@ -218,9 +303,9 @@ class _T5Embedder(AbstractEmbModel):
     def __init__(self, model_name_or_path="", max_length: int = 256, model_kwargs: Optional[dict] = None, freeze: bool = True,
                  config: Optional[dict] = None, **kwargs):
         super().__init__(**kwargs)
-        if self.is_trainable:
-            raise NotImplementedError(f"{type(self).__name__}(is_trainable=True): the T5 encoders are frozen only (no training chain; only the CLIP "
-                                      "text towers have one)")
+        if self.is_trainable and freeze:
+            raise NotImplementedError(f"{type(self).__name__}(is_trainable=True) with freeze=True: pass freeze=False to train the tower with the UNet "
+                                      "(the reference would freeze every parameter and silently train nothing)")
         if config is None:
             config = _local_config(model_name_or_path)
         if config is None:
@@ -257,11 +342,21 @@ class _T5Embedder(AbstractEmbModel):
     def _ids_for(self, text) -> Tensor:
         raise NotImplementedError
 
-    @torch.no_grad()
+    def trained_parameters(self) -> list:
+        """Every parameter of the tower, once (the tied embedding is one parameter): what one step gives a gradient, and what the engine puts
+        in the tower's store and optimizer group."""
+        return list(self.model.parameters())
+
     def forward(self, text: Union[str, list, Tensor]) -> Tensor:
         """fp32 [B, L, d_model] last hidden state; L = max_length when text is given (padded, and the padding attended to: the
-        reference passes no mask)"""
+        reference passes no mask).  Trainable (is_trainable and freeze=False) under grad mode: the autograd-connected training chain."""
         ids = text if torch.is_tensor(text) else self._ids_for(_decode_text(text))
+        if _trainable(self, self.model):
+            return self.model.train_outputs(ids.to(self.device))
+        return self._forward_frozen(ids)
+
+    @torch.no_grad()
+    def _forward_frozen(self, ids: Tensor) -> Tensor:
         return self.model(ids.to(self.device))["last_hidden_state"]
 
     def encode(self, text):

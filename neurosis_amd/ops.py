@@ -805,7 +805,51 @@ def rmsnorm(x: Tensor, weight: Tensor, eps: float = 1e-6) -> Tensor:
     return y
 
 
+def rmsnorm_fwd(x: Tensor, weight: Tensor, eps: float = 1e-6):
+    """rmsnorm with its backward (the T5 towers under training): (y, bwd(dy, dx_add=None) -> dx), y with rmsnorm()'s bits.  bwd writes
+    weight.grad in the parameter's engine mode (nk_rmsnorm_bwd: partial rows and the fixed-order column reducer)."""
+    _check2d(x, "x")
+    if not x.is_contiguous():
+        raise ValueError("rmsnorm: x must be dense")
+    M, Cc = x.shape
+    if weight.dtype != torch.float32 or weight.numel() != Cc or not weight.is_contiguous():
+        raise ValueError(f"rmsnorm: weight must be a dense fp32 vector of {Cc} elements, got {weight.dtype} {tuple(weight.shape)}")
+    y = torch.empty_like(x)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    call("nk_rmsnorm_fwd_rstd", x.data_ptr(), weight.data_ptr(), y.data_ptr(), rstd.data_ptr(), M, Cc, float(eps), _stream())
+
+    def bwd(dy: Tensor, dx_add: Optional[Tensor] = None) -> Tensor:
+        if dy.shape != x.shape or dy.dtype != BF16 or not dy.is_contiguous():
+            raise ValueError("rmsnorm bwd: dy must be a dense bf16 tensor of x's shape")
+        if dx_add is not None and (dx_add.shape != x.shape or dx_add.dtype != BF16 or not dx_add.is_contiguous()):
+            raise ValueError("rmsnorm bwd: dx_add must be a dense bf16 tensor of x's shape")
+        dx = torch.empty_like(x)
+        ws = _ws(query("nk_rmsnorm_bwd_ws_floats", M, Cc), x.device)
+        call("nk_rmsnorm_bwd", dy.data_ptr(), x.data_ptr(), weight.data_ptr(), rstd.data_ptr(), _p(dx_add), dx.data_ptr(), grad_flat(weight).data_ptr(),
+             ws.data_ptr(), M, Cc, int(state_of(weight).grad_accumulate), _stream())
+        return dx
+
+    return y, bwd
+
+
 GATED_ACT_KINDS = ("gated-gelu", "gelu_new", "relu")
+
+
+def gated_act_fwd(u: Tensor, kind: str):
+    """gated_act with its backward: (y, bwd(dy) -> du), du of u's shape (nk_gated_gelu_tanh_bwd; nk_act_bwd modes 2 / 3 for the ungated kinds)"""
+    y = gated_act(u, kind)
+
+    def bwd(dy: Tensor) -> Tensor:
+        if dy.shape != y.shape or dy.dtype != BF16 or not dy.is_contiguous():
+            raise ValueError(f"gated_act bwd: dy must be a dense bf16 {tuple(y.shape)} tensor")
+        du = torch.empty_like(u)
+        if kind == "gated-gelu":
+            call("nk_gated_gelu_tanh_bwd", dy.data_ptr(), u.data_ptr(), du.data_ptr(), u.shape[0], u.shape[1] // 2, _stream())
+        else:
+            call("nk_act_bwd", dy.data_ptr(), u.data_ptr(), du.data_ptr(), u.numel(), 2 if kind == "gelu_new" else 3, _stream())
+        return du
+
+    return y, bwd
 
 
 def gated_act(u: Tensor, kind: str) -> Tensor:
@@ -866,18 +910,23 @@ def gelu_fwd(x: Tensor, quick: bool = False):
     return y, bwd
 
 
-def embedding_bwd(ids: Tensor, dx: Tensor, table: Tensor, positions: Tensor) -> None:
+EMBEDDING_BWD_MAX_TOKENS = 8192      # include/neurosis_hip.h: NK_EMBEDDING_BWD_MAX_TOKENS
+
+
+def embedding_bwd(ids: Tensor, dx: Tensor, table: Tensor, positions: Optional[Tensor]) -> None:
     """Gradients of x[b * L + l] = table[ids[b, l]] + positions[l] (the text towers' embedding) written into table.grad / positions.grad
     (fp32), in the parameters' engine mode: the first micro-batch overwrites (rows nothing hit come out zero), later ones add.  Deterministic
-    (nk_embedding_bwd: fixed-order sums, no atomics).  ids [B, L] int64; dx [B * L, C] bf16."""
+    (nk_embedding_bwd: fixed-order sums, no atomics).  ids [B, L] int64; dx [B * L, C] bf16.  positions=None: no position table (T5)."""
     _check2d(dx, "dx")
     B, L = ids.shape
     V, Cc = table.shape
-    P = positions.shape[0]
-    if ids.dtype != torch.int64 or not ids.is_contiguous() or dx.shape != (B * L, Cc) or positions.shape[1] != Cc:
+    P = positions.shape[0] if positions is not None else 0
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or dx.shape != (B * L, Cc) or (positions is not None and positions.shape[1] != Cc):
         raise ValueError(f"embedding_bwd: ids [B, L] int64 and dx [B * L, {Cc}] expected, got {tuple(ids.shape)} {ids.dtype}, {tuple(dx.shape)}")
-    call("nk_embedding_bwd", ids.data_ptr(), dx.data_ptr(), dx.stride(0), grad_flat(table).data_ptr(), grad_flat(positions).data_ptr(), B, L, V, P,
-         Cc, wgrad_mode(table), _stream())
+    if B * L > EMBEDDING_BWD_MAX_TOKENS:
+        raise NotImplementedError(f"embedding_bwd: at most {EMBEDDING_BWD_MAX_TOKENS} tokens per call (the duplicate-id scans are quadratic), got {B} x {L}")
+    call("nk_embedding_bwd", ids.data_ptr(), dx.data_ptr(), dx.stride(0), grad_flat(table).data_ptr(),
+         grad_flat(positions).data_ptr() if positions is not None else None, B, L, V, P, Cc, wgrad_mode(table), _stream())
 
 
 def gather_rows_bwd(dsel: Tensor, idx: Tensor, L: int) -> Tensor:
@@ -1277,6 +1326,65 @@ def attention_relbias_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, d
     d.causal = 0
     call("nk_attention_relbias_fwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), rel.data_ptr(), _stream())
     return o
+
+
+def attention_relbias_train(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head: int, rel: Tensor, scale: float, d_rel: Tensor):
+    """attention_relbias_fwd with its backward (the T5 towers under training): (o, bwd(do, dq=None, dk=None, dv=None) -> (dq, dk, dv)), o with
+    attention_relbias_fwd's bits.  bwd ADDS the table's gradient into d_rel, fp32 [heads, 2 L - 1] (zeroed by the caller: one tower sums
+    every layer into one buffer; bwd(..., accumulate=False) overwrites it); dq / dk / dv may be given as column slices of one buffer.
+    Every output is bitwise reproducible."""
+    for n, t in (("q", q), ("k", k), ("v", v)):
+        _check2d(t, n)
+    L = q.shape[0] // B
+    HD = heads * dim_head
+    if k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
+        raise ValueError("attention_relbias_train: self-attention (q, k and v over the same tokens)")
+    if L > ATTN_RELBIAS_MAX_L:
+        raise NotImplementedError(f"attention_relbias_train: at most {ATTN_RELBIAS_MAX_L} tokens per sequence (the head's bias table lives in LDS), got L = {L}")
+    for n, t in (("rel", rel), ("d_rel", d_rel)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (heads, 2 * L - 1) or not t.is_contiguous() or t.device != q.device:
+            raise ValueError(f"attention_relbias_train: {n} must be a dense fp32 [{heads}, {2 * L - 1}] tensor on {q.device}, got {t.dtype} {tuple(t.shape)}")
+    o = torch.empty(B * L, HD, dtype=BF16, device=q.device)
+    lse = torch.empty(B, heads, L, dtype=torch.float32, device=q.device)
+    d = NkAttnDesc()
+    d.B, d.H, d.Lq, d.Lk, d.D = B, heads, L, L, dim_head
+    d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
+    d.bq, d.bk, d.bv, d.bo = L * q.stride(0), L * k.stride(0), L * v.stride(0), L * o.stride(0)
+    d.scale = float(scale)
+    d.causal = 0
+    call("nk_attention_relbias_fwd_lse", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), rel.data_ptr(), _stream())
+
+    def bwd(do: Tensor, dq: Optional[Tensor] = None, dk: Optional[Tensor] = None, dv: Optional[Tensor] = None, accumulate: bool = True):
+        _check2d(do, "do")
+        dq = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dq is None else dq
+        dk = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dk is None else dk
+        dv = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dv is None else dv
+        for n, t in (("do", do), ("dq", dq), ("dk", dk), ("dv", dv)):
+            _check2d(t, n)
+            if t.shape != (B * L, HD):
+                raise ValueError(f"attention_relbias_train bwd: {n} must be [{B * L}, {HD}], got {tuple(t.shape)}")
+        d.sdq, d.sdk, d.sdv, d.sdo = dq.stride(0), dk.stride(0), dv.stride(0), do.stride(0)
+        d.bdq, d.bdk, d.bdv, d.bdo = L * dq.stride(0), L * dk.stride(0), L * dv.stride(0), L * do.stride(0)
+        ws = _ws(query("nk_attention_relbias_bwd_ws_floats", C.byref(d)), do.device)
+        call("nk_attention_relbias_bwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(),
+             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), rel.data_ptr(), d_rel.data_ptr(), ws.data_ptr(), int(accumulate), _stream())
+        return dq, dk, dv
+
+    bwd.lse = lse      # (tests read it)
+    return o, bwd
+
+
+def relbias_bucket_sum(d_rel: Tensor, buckets: Tensor, weight: Tensor) -> None:
+    """relative_attention_bias.weight's gradient [num_buckets, heads] from the table's, d_rel fp32 [heads, 2 L - 1]: every table entry added
+    to its bucket's row in a fixed order, into weight.grad in the parameter's engine mode (ops.wgrad_mode, as embedding_bwd).  buckets:
+    the int tensor [2 L - 1] of relative_buckets()."""
+    heads, nrel = d_rel.shape
+    if d_rel.dtype != torch.float32 or not d_rel.is_contiguous() or tuple(weight.shape[1:]) != (heads,) or buckets.numel() != nrel or nrel % 2 == 0:
+        raise ValueError(f"relbias_bucket_sum: d_rel fp32 [heads, 2 L - 1], buckets [2 L - 1] and weight [num_buckets, heads] expected, got "
+                         f"{tuple(d_rel.shape)} {tuple(buckets.shape)} {tuple(weight.shape)}")
+    b32 = buckets.to(device=d_rel.device, dtype=torch.int32).contiguous()
+    call("nk_relbias_bucket_sum", d_rel.data_ptr(), b32.data_ptr(), grad_flat(weight).data_ptr(), heads, (nrel + 1) // 2, weight.shape[0],
+         wgrad_mode(weight), _stream())
 
 
 def attention_causal_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head: int = 64):
