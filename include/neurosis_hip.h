@@ -162,6 +162,30 @@ int nk_conv2d_wgrad(const NkConvDesc* d, const void* dy, const void* x, float* d
 /* ... with the bias gradient dbias[Cout] (+)= sum over pixels of dy from the same launch */
 int nk_conv2d_wgrad_bias(const NkConvDesc* d, const void* dy, const void* x, float* dw, float* dbias, int accumulate, void* stream);
 
+/* conv3x3(nearest_upsample_2x(x)) (Upsample.conv, openaimodel.py:124-143) as four 2 x 2 phase convolutions of x: 16 products per input pixel
+ * and channel pair where the fused-upsample gather of nk_conv2d_fwd(upsample = 1) computes 36.  d is that call's descriptor (3 x 3, stride 1,
+ * padding 1, upsample = 1, Ho = 2H, Wo = 2W; anything else is refused); no rowvec, residual or statistics epilogue.
+ *   nk_up2_phase_weights   w bf16 [Cout][9][Cin] -> wp bf16 [4][Cout][4][Cin] (phase a*2+b, tap u*2+v: the taps of w that output pixel
+ *                          (2i+a, 2j+b) applies to x[i+a-1+u][j+b-1+v], summed in fp32 and rounded once) and, unless NULL, wd bf16
+ *                          [Cin][16][Cout], the same sums as the 4 x 4 / stride 2 / padding 1 convolution of dy that is the input gradient
+ *   nk_conv2d_up2_fwd      y [N][2H][2W][Cout] = the four phase convolutions (+ bias), pixel-shuffled
+ *   nk_conv2d_up2_dgrad    dx [N][H][W][Cin] from dy [N][2H][2W][Cout] and wd, one launch (no nk_upsample2x_bwd behind it)
+ *   nk_conv2d_up2_wgrad    dw fp32 [Cout][9][Cin] (+)= the four phase weight gradients folded onto the nine taps; _bias: and dbias[Cout]
+ * ws: nk_conv2d_up2_ws_bytes(d, direction) bytes, 16-byte aligned; direction 0 = fwd, 1 = dgrad (none), 2 = wgrad; -1: refused descriptor.
+ * accumulate as in nk_conv2d_wgrad. */
+int nk_up2_phase_weights(const void* w, void* wp, void* wd, int Cout, int Cin, void* stream);
+long nk_conv2d_up2_ws_bytes(const NkConvDesc* d, int direction);
+int nk_conv2d_up2_fwd(const NkConvDesc* d, const void* x, const void* wp, const float* bias, void* y, void* ws, void* stream);
+int nk_conv2d_up2_dgrad(const NkConvDesc* d, const void* dy, const void* wd, void* dx, void* stream);
+int nk_conv2d_up2_wgrad(const NkConvDesc* d, const void* dy, const void* x, float* dw, int accumulate, void* ws, void* stream);
+int nk_conv2d_up2_wgrad_bias(const NkConvDesc* d, const void* dy, const void* x, float* dw, float* dbias, int accumulate, void* ws, void* stream);
+/* the four phase images [4][N][H][W][C] (phase a*2+b = the pixels (2h+a, 2w+b)) -> y [N][2H][2W][C], and back */
+int nk_pixel_shuffle2x(const void* phases, void* y, int N, int H, int W, int C, void* stream);
+int nk_pixel_unshuffle2x(const void* y, void* phases, int N, int H, int W, int C, void* stream);
+/* dw[co][kh][kw][ci] (+)= sum over the phases, in the order 0..3, of dwp fp32 [4][Cout][4][Cin] at tap (kh > a)*2 + (kw > b); dbias[Cout] (+)= the
+ * sum of dbias_p [4][Cout] (both NULL: no bias).  accumulate: 1 = add, 0 / 2 = store */
+int nk_up2_fold_wgrad(const float* dwp, const float* dbias_p, float* dw, float* dbias, int Cout, int Cin, int accumulate, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused attention  softmax(q k^T * scale) v, no dropout; no mask
  * (modules/attention.py:410-412 TorchSDPCrossAttention, :337-352 MemoryEfficientCrossAttention) or, forward only, the causal

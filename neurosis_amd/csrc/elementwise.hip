@@ -540,6 +540,126 @@ extern "C" int nk_conv_weight_flip(const void* w, void* wt, int Cout, int Cin, i
 }
 
 // ------------------------------------------------------------------------------------------------
+// conv3x3(nearest_upsample_2x(x)) as four 2 x 2 phase convolutions of x (ops_gemm.hip: nk_conv2d_up2_*).  Output row 2i + a reads the
+// upsampled rows 2i + a + kh - 1 = low-resolution rows i + a - 1 + u: for a = 0, u = 0 holds tap kh = 0 and u = 1 taps {1, 2}; for a = 1,
+// u = 0 holds {0, 1} and u = 1 tap 2 -- taps kh = (u ? 1 + a : 0) .. + (u ^ a); columns alike with (b, v, kw).
+//   wp[a*2+b][co][u*2+v][ci] = the sum of the taps of w[co][3][3][ci] that fall on (u, v): fp32 sum, rounded once
+//   wd[ci][r*4+s][co]        = wp[(r+1)&1][(s+1)&1][co][1-(r>>1)][1-(s>>1)][ci]: the 4 x 4 / stride 2 / padding 1 convolution of dy that is
+//                              the input gradient (the same rounded values, channel roles swapped)
+// One 64 x 64 (co, ci) tile of one (phase, u, v) per block, transposed through LDS like conv_weight_flip_kernel.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void up2_phase_weights_kernel(const bf16_t* __restrict__ w, bf16_t* __restrict__ wp, bf16_t* __restrict__ wd, int Cout,
+                                                                int Cin) {
+  __shared__ bf16_t tile[64][64 + 8];          // [ci][co], rows padded by 16 B
+  const int z = blockIdx.z, co0 = blockIdx.y * 64, ci0 = blockIdx.x * 64;
+  const int a = z >> 3, b = (z >> 2) & 1, u = (z >> 1) & 1, v = z & 1;
+  const int kh0 = u ? 1 + a : 0, khn = 1 + (u ^ a), kw0 = v ? 1 + b : 0, kwn = 1 + (v ^ b);
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int idx = tid + 256 * it;            // 64 rows (co) x 8 chunks (ci)
+    const int r = idx >> 3, ch = idx & 7;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const bool in = co0 + r < Cout && ci0 + ch * 8 < Cin;
+    if (in) {
+      for (int kh = kh0; kh < kh0 + khn; ++kh)
+        for (int kw = kw0; kw < kw0 + kwn; ++kw) {
+          float f[8];
+          ew_load(w + ((long)(co0 + r) * 9 + kh * 3 + kw) * Cin + ci0 + ch * 8, f);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) acc[k] += f[k];
+        }
+    }
+    const uint4_t o = pack8(acc);
+    if (in) *(uint4_t*)(wp + (((long)(z >> 2) * Cout + co0 + r) * 4 + (z & 3)) * Cin + ci0 + ch * 8) = o;
+    const bf16_t* e = (const bf16_t*)&o;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) tile[ch * 8 + k][r] = e[k];
+  }
+  if (!wd) return;
+  __syncthreads();
+  const int tap = (2 * (1 - u) + (1 - a)) * 4 + 2 * (1 - v) + (1 - b);
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int idx = tid + 256 * it;            // 64 rows (ci) x 8 chunks (co)
+    const int r = idx >> 3, ch = idx & 7;
+    if (ci0 + r < Cin && co0 + ch * 8 < Cout)
+      *(uint4_t*)(wd + ((long)(ci0 + r) * 16 + tap) * Cout + co0 + ch * 8) = *(const uint4_t*)&tile[r][ch * 8];
+  }
+}
+extern "C" int nk_up2_phase_weights(const void* w, void* wp, void* wd, int Cout, int Cin, void* stream) {
+  NK_CHECK_ARG(w && wp && Cout > 0 && Cin > 0 && (Cout & 7) == 0 && (Cin & 7) == 0 && (Cout + 63) / 64 <= 65535);
+  NK_CHECK_ARG(nk_aligned16(w) && nk_aligned16(wp) && nk_aligned16(wd));
+  hipLaunchKernelGGL(up2_phase_weights_kernel, dim3((Cin + 63) / 64, (Cout + 63) / 64, 16), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)w,
+                     (bf16_t*)wp, (bf16_t*)wd, Cout, Cin);
+  return nk_check_launch("up2_phase_weights_kernel");
+}
+
+// the four phase images [4][N][H][W][C] (phase a*2+b holds the pixels (2h + a, 2w + b)) <-> the image [N][2H][2W][C]; each runs over its output
+struct PixelShuffle2x {
+  const bf16_t* ph; bf16_t* y; int N, H, W, C;
+  __device__ void operator()(long i, int n, int h, int w, int ch) const {
+    const int p = (h & 1) * 2 + (w & 1);
+    *(uint4_t*)(y + i * 8) = *(const uint4_t*)(ph + ((((long)p * N + n) * H + (h >> 1)) * W + (w >> 1)) * C + ch * 8);
+  }
+};
+struct PixelUnshuffle2x {
+  const bf16_t* y; bf16_t* ph; int N, H, W, C;
+  __device__ void operator()(long i, int pn, int h, int w, int ch) const {
+    const int p = pn / N, n = pn - p * N;
+    *(uint4_t*)(ph + i * 8) = *(const uint4_t*)(y + (((long)n * 2 * H + 2 * h + (p >> 1)) * 2 * W + 2 * w + (p & 1)) * C + ch * 8);
+  }
+};
+extern "C" int nk_pixel_shuffle2x(const void* phases, void* y, int N, int H, int W, int C, void* stream) {
+  NK_CHECK_ARG(phases && y && N > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0 && nk_aligned16(phases) && nk_aligned16(y));
+  NK_CHECK_ARG(4l * N < (1l << 31) && 2l * H < (1l << 31) && 2l * W < (1l << 31));
+  return nk_ew_pixels("pixel_shuffle2x", stream, N, 2 * H, 2 * W, C >> 3, PixelShuffle2x{(const bf16_t*)phases, (bf16_t*)y, N, H, W, C});
+}
+extern "C" int nk_pixel_unshuffle2x(const void* y, void* phases, int N, int H, int W, int C, void* stream) {
+  NK_CHECK_ARG(phases && y && N > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0 && nk_aligned16(phases) && nk_aligned16(y));
+  NK_CHECK_ARG(4l * N < (1l << 31) && 2l * H < (1l << 31) && 2l * W < (1l << 31));
+  return nk_ew_pixels("pixel_unshuffle2x", stream, 4 * N, H, W, C >> 3, PixelUnshuffle2x{(const bf16_t*)y, (bf16_t*)phases, N, H, W, C});
+}
+
+// the phase weight gradients dwp fp32 [4][Cout][4][Cin] back onto the nine taps: dw[co][kh][kw][ci] (+)= sum over the phases (a, b), in that
+// fixed order, of dwp[a*2+b][co][(kh > a)*2 + (kw > b)][ci]; dbias[co] (+)= the four phases' bias gradients.  Four floats per item; the
+// bias items follow the weight items.  accumulate: 1 = add to what is there, 0 / 2 = store (see nk_conv2d_wgrad)
+struct Up2FoldWgrad {
+  const float* dwp; const float* dbp; float* dw; float* dbias; int Cout, Cin, add; long nw;
+  __device__ void operator()(long i) const {
+    float4_t s = {0.f, 0.f, 0.f, 0.f};
+    float* dst;
+    if (i < nw) {
+      const int c4 = Cin >> 2;
+      const long row = i / c4;                 // co * 9 + tap
+      const int ci = (int)(i - row * c4) * 4;
+      const long co = row / 9;
+      const int tap = (int)(row - co * 9), kh = tap / 3, kw = tap - kh * 3;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int uv = (kh > (p >> 1)) * 2 + (kw > (p & 1));
+        s += *(const float4_t*)(dwp + (((long)p * Cout + co) * 4 + uv) * Cin + ci);
+      }
+      dst = dw + row * Cin + ci;
+    } else {
+      const long co = (i - nw) * 4;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) s += *(const float4_t*)(dbp + (long)p * Cout + co);
+      dst = dbias + co;
+    }
+    if (add) s += *(const float4_t*)dst;
+    *(float4_t*)dst = s;
+  }
+};
+extern "C" int nk_up2_fold_wgrad(const float* dwp, const float* dbias_p, float* dw, float* dbias, int Cout, int Cin, int accumulate, void* stream) {
+  NK_CHECK_ARG(dwp && dw && Cout > 0 && Cin > 0 && (Cout & 7) == 0 && (Cin & 7) == 0 && accumulate >= 0 && accumulate <= 2);
+  NK_CHECK_ARG((dbias == nullptr) == (dbias_p == nullptr));
+  NK_CHECK_ARG(nk_aligned16(dwp) && nk_aligned16(dw) && nk_aligned16(dbias_p) && nk_aligned16(dbias));
+  const long nw = (long)Cout * 9 * (Cin >> 2);
+  return nk_ew_flat("up2_fold_wgrad", stream, nw + (dbias ? Cout >> 2 : 0), Up2FoldWgrad{dwp, dbias_p, dw, dbias, Cout, Cin, accumulate == 1, nw});
+}
+
+// ------------------------------------------------------------------------------------------------
 // 3 x 3 / stride 1 / padding 1 convolution of an image with 3 or 4 REAL channels (stored padded to 8): the VAE's conv_in
 // (modules/diffusion/model.py:519, 3 -> 128 at 1024^2) and the UNet's (openaimodel.py:622-624, 4 -> 320).  As an implicit GEMM with K = 72
 // the gather kernel spent 1.5 ms decoding taps for a 1 GB output, and a plain FMA kernel (a thread = 4 output channels, 108 FMAs and 9 unpacked

@@ -319,3 +319,87 @@ extern "C" int nk_conv2d_wgrad_bias(const NkConvDesc* d, const void* dy, const v
   NK_CHECK_ARG(dbias != nullptr);
   return conv_wgrad(d, dy, x, dw, dbias, accumulate, stream);
 }
+
+// ---- conv3x3(nearest_upsample_2x(x)) without the duplicated products -----------------------------------------------------------------------
+// The fused-upsample gather multiplies every input pixel four times: 36 products per (input pixel, ci, co).  Output pixel (2i + a, 2j + b)
+// only sees the 2 x 2 low-resolution neighbourhood (i + a - 1 + u, j + b - 1 + v), so each of the four output phases (a, b) is an ordinary
+// 2 x 2 / stride 1 convolution of x with top / left padding (1 - a, 1 - b) and the summed weights wp of nk_up2_phase_weights: 16 products.
+// Its input gradient is ONE 4 x 4 / stride 2 / padding 1 convolution of dy with wd (16 products, no 2 x 2 sum pass behind it), its weight
+// gradient the four phase convolutions' weight gradients folded back onto the nine taps (nk_up2_fold_wgrad).  These entry points issue
+// exactly those launches, on the tile engine's general gather kernels, and take the 3 x 3 descriptor of nk_conv2d_fwd(upsample = 1).
+static int check_up2(const NkConvDesc* d) {
+  if (int e = check_conv(d)) return e;
+  NK_CHECK_ARG(d->upsample == 1 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1);
+  NK_CHECK_ARG(d->Ho == 2 * d->H && d->Wo == 2 * d->W);
+  return NK_OK;
+}
+static NkConvDesc up2_phase_desc(const NkConvDesc* d, int phase) {
+  NkConvDesc t = *d;
+  t.KH = t.KW = 2; t.pad_t = 1 - (phase >> 1); t.pad_l = 1 - (phase & 1);
+  t.Ho = d->H; t.Wo = d->W; t.upsample = 0;
+  return t;
+}
+static size_t up2_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static size_t up2_phase_image_bytes(const NkConvDesc* d) { return up2_align((size_t)4 * d->N * d->H * d->W * d->Cout * sizeof(bf16_t)); }
+static size_t up2_phase_wgrad_bytes(const NkConvDesc* d) { return up2_align((size_t)16 * d->Cout * d->Cin * sizeof(float)); }
+
+extern "C" long nk_conv2d_up2_ws_bytes(const NkConvDesc* d, int direction) {
+  // workspace of nk_conv2d_up2_fwd (direction 0), _dgrad (1: none) and _wgrad / _wgrad_bias (2); -1: not a convolution they take
+  if (check_up2(d) || direction < 0 || direction > 2) return -1;
+  if (direction == 0) return (long)up2_phase_image_bytes(d);
+  if (direction == 1) return 0;
+  return (long)(up2_phase_image_bytes(d) + up2_phase_wgrad_bytes(d) + up2_align((size_t)4 * d->Cout * sizeof(float)));
+}
+
+extern "C" int nk_conv2d_up2_fwd(const NkConvDesc* d, const void* x, const void* wp, const float* bias, void* y, void* ws, void* stream) {
+  // y[N][2H][2W][Cout] = conv3x3(up2(x)) + bias: four phase convolutions into ws, one pixel shuffle into y.  wp: nk_up2_phase_weights
+  if (int e = check_up2(d)) return e;
+  NK_CHECK_ARG(x && wp && y && ws && nk_aligned16(ws));
+  const size_t img = (size_t)d->N * d->H * d->W * d->Cout;
+  for (int ph = 0; ph < 4; ++ph) {
+    const NkConvDesc t = up2_phase_desc(d, ph);
+    NkGemmParams p = conv_fwd_params(&t, x, (const bf16_t*)wp + (size_t)ph * d->Cout * 4 * d->Cin, bias, nullptr, nullptr, (bf16_t*)ws + ph * img);
+    if (int e = nk_gemm_dispatch(p, NK_OP_KCG, NK_OP_KC, 0, 0, (hipStream_t)stream)) return e;
+  }
+  if (nk_launch_log_mode() == 3) return NK_OK;      // plan-only: the elementwise pass has no plan and touches the device
+  return nk_pixel_shuffle2x(ws, y, d->N, d->H, d->W, d->Cout, stream);
+}
+
+extern "C" int nk_conv2d_up2_dgrad(const NkConvDesc* d, const void* dy, const void* wd, void* dx, void* stream) {
+  // dx[N][H][W][Cin]: the 4 x 4 / stride 2 / padding 1 forward convolution of dy[N][2H][2W][Cout] with wd[Cin][16][Cout]
+  if (int e = check_up2(d)) return e;
+  NK_CHECK_ARG(dy && wd && dx);
+  NkConvDesc t = *d;
+  t.H = 2 * d->H; t.W = 2 * d->W; t.Cin = d->Cout; t.Cout = d->Cin;
+  t.KH = t.KW = 4; t.stride = 2; t.Ho = d->H; t.Wo = d->W; t.upsample = 0;
+  if (int e = check_conv(&t)) return e;
+  NkGemmParams p = conv_fwd_params(&t, dy, wd, nullptr, nullptr, nullptr, dx);
+  return nk_gemm_dispatch(p, NK_OP_KCG, NK_OP_KC, 0, 0, (hipStream_t)stream);
+}
+
+static int conv_up2_wgrad(const NkConvDesc* d, const void* dy, const void* x, float* dw, float* dbias, int accumulate, void* ws, void* stream) {
+  // the phases of dy into ws, each phase convolution's weight (and bias) gradient into fp32 scratch behind them, then the fold onto dw / dbias
+  if (int e = check_up2(d)) return e;
+  NK_CHECK_ARG(dy && x && dw && ws && nk_aligned16(ws) && accumulate >= 0 && accumulate <= 2);
+  const int plan_only = nk_launch_log_mode() == 3;
+  bf16_t* dyp = (bf16_t*)ws;
+  float* dwp = (float*)((char*)ws + up2_phase_image_bytes(d));
+  float* dbp = dbias ? (float*)((char*)dwp + up2_phase_wgrad_bytes(d)) : nullptr;
+  if (!plan_only)
+    if (int e = nk_pixel_unshuffle2x(dy, dyp, d->N, d->H, d->W, d->Cout, stream)) return e;
+  const size_t img = (size_t)d->N * d->H * d->W * d->Cout;
+  for (int ph = 0; ph < 4; ++ph) {
+    const NkConvDesc t = up2_phase_desc(d, ph);
+    if (int e = conv_wgrad(&t, dyp + ph * img, x, dwp + (size_t)ph * d->Cout * 4 * d->Cin, dbp ? dbp + (size_t)ph * d->Cout : nullptr, 0, stream)) return e;
+  }
+  if (plan_only) return NK_OK;
+  return nk_up2_fold_wgrad(dwp, dbp, dw, dbias, d->Cout, d->Cin, accumulate, stream);
+}
+extern "C" int nk_conv2d_up2_wgrad(const NkConvDesc* d, const void* dy, const void* x, float* dw, int accumulate, void* ws, void* stream) {
+  return conv_up2_wgrad(d, dy, x, dw, nullptr, accumulate, ws, stream);
+}
+extern "C" int nk_conv2d_up2_wgrad_bias(const NkConvDesc* d, const void* dy, const void* x, float* dw, float* dbias, int accumulate, void* ws,
+                                        void* stream) {
+  NK_CHECK_ARG(dbias != nullptr);
+  return conv_up2_wgrad(d, dy, x, dw, dbias, accumulate, ws, stream);
+}

@@ -60,6 +60,14 @@ SIGNATURES: dict[str, list] = {
     "nk_conv2d_dgrad": [cdp, vp, vp, vp, vp],
     "nk_conv2d_dgrad_flipped": [cdp, vp, vp, vp, vp],
     "nk_conv2d_wgrad": [cdp, vp, vp, vp, i32, vp],
+    "nk_up2_phase_weights": [vp, vp, vp, i32, i32, vp],
+    "nk_conv2d_up2_fwd": [cdp, vp, vp, vp, vp, vp, vp],
+    "nk_conv2d_up2_dgrad": [cdp, vp, vp, vp, vp],
+    "nk_conv2d_up2_wgrad": [cdp, vp, vp, vp, i32, vp, vp],
+    "nk_conv2d_up2_wgrad_bias": [cdp, vp, vp, vp, vp, i32, vp, vp],
+    "nk_pixel_shuffle2x": [vp, vp, i32, i32, i32, i32, vp],
+    "nk_pixel_unshuffle2x": [vp, vp, i32, i32, i32, i32, vp],
+    "nk_up2_fold_wgrad": [vp, vp, vp, vp, i32, i32, i32, vp],
     "nk_attention_fwd": [adp, vp, vp, vp, vp, vp, vp],
     "nk_attention_bwd": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "nk_attention_bwd_causal": [adp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -171,6 +179,7 @@ SIZE_QUERIES: dict[str, list] = {
     "nk_groupnorm_sums_ws_floats": [i32, i32, i32],
     "nk_conv2d_stats_tiles": [cdp, i32],
     "nk_conv2d_dgrad_flipped_ok": [cdp],
+    "nk_conv2d_up2_ws_bytes": [cdp, i32],
     "nk_linear_fwd_geglu_ok": [i32, i32, i32],
     "nk_layernorm_ws_floats": [i32, i32],
     "nk_layernorm_part_rows": [i32],

@@ -611,6 +611,22 @@ def groupnorm_sums(x: Img, groups: int) -> Tensor:
     return sums
 
 
+UP2_PHASES_MIN_WORK = 1 << 28
+
+
+def up2_phases_take(pixels: int, Cin: int, Cout: int) -> bool:
+    """Does conv3x3(nearest_upsample_2x(x)) run as four 2 x 2 phase convolutions of x (nk_conv2d_up2_*: 4/9 of the fused gather's products)?
+    NK_UP2_PHASES, read per call: 0 = never (the fused-upsample gather), 2 = every qualifying call (tests), 1 / unset = by size.  The phase
+    path trades 5/9 of the products of forward, input gradient and weight gradient for about eight more launches and four passes over y / dy:
+    at ~800 TFLOP/s the saved products are worth those ~30 us from about pixels * Cin * Cout = 2e8 on (reasoned from the launch count, not
+    measured at the threshold; the UNet's layers are at 6.7e9, measured).  Below it the fused gather also keeps small models on one rounding
+    of the weights."""
+    mode = os.environ.get("NK_UP2_PHASES", "1")
+    if mode == "0":
+        return False
+    return mode == "2" or pixels * Cin * Cout >= UP2_PHASES_MIN_WORK
+
+
 def conv2d_fwd(x: Img, weight: Tensor, bias: Optional[Tensor], stride: int = 1, padding=1, upsample: bool = False,
                rowvec: Optional[Tensor] = None, residual: Optional[Tensor] = None, need_dx: bool = True,
                asym_pad: bool = False, stats_groups: Optional[int] = None, cin_real: Optional[int] = None):
@@ -620,6 +636,8 @@ def conv2d_fwd(x: Img, weight: Tensor, bias: Optional[Tensor], stride: int = 1, 
     stats_groups = G: the output Img carries `.sums` (its GroupNorm sums over G groups) when the kernel can emit them.
     cin_real = 3 | 4: x's 8 channels are 3 or 4 real ones plus zero padding (image / latent inputs): the forward of a plain 3 x 3
     stride-1 convolution then runs as the register-resident FMA kernel instead of a K = 72 implicit GEMM.
+    upsample=True: the convolution of the nearest-2x upsampling of x, which is never written; a 3 x 3 / stride 1 / padding 1 one without
+    rowvec or residual runs as four 2 x 2 phase convolutions of x where up2_phases_take() says so (nk_conv2d_up2_*; NK_UP2_PHASES).
     bwd(dy) -> (dx Img | None, d_rowvec | None)."""
     Cout, Cin, KH, KW = weight.shape
     if x.C != Cin:
@@ -640,6 +658,8 @@ def conv2d_fwd(x: Img, weight: Tensor, bias: Optional[Tensor], stride: int = 1, 
         raise ValueError("conv2d: x must be dense channels-last")
     tiles = query("nk_conv2d_stats_tiles", C.byref(d), stats_groups) if stats_groups else 0
     sums_out = None
+    up2 = (upsample and KH == 3 and KW == 3 and stride == 1 and pad_t == 1 and not asym_pad and rowvec is None and residual is None and not tiles
+           and up2_phases_take(x.N * x.H * x.W, Cin, Cout))
     if tiles:
         dev = x.t.device
         part = torch.empty(x.N, tiles, 2 * stats_groups, dtype=torch.float32, device=dev)
@@ -651,9 +671,26 @@ def conv2d_fwd(x: Img, weight: Tensor, bias: Optional[Tensor], stride: int = 1, 
     elif (cin_real in (3, 4) and Cin == 8 and KH == 3 and KW == 3 and stride == 1 and pad_t == 1 and not asym_pad and not upsample and rowvec is None
           and residual is None and Cout % 8 == 0):
         call("nk_conv3x3_few_channels_fwd", x.t.data_ptr(), w2d(weight).data_ptr(), _p(bias), y.data_ptr(), x.N, x.H, x.W, Cout, cin_real, _stream())
+    elif up2:
+        # the four 2 x 2 phase convolutions of x (nk_conv2d_up2_*): wp / wd are the summed weights of this step, wd kept for the input gradient
+        dev = x.t.device
+        wp = torch.empty(16 * Cout * Cin, dtype=BF16, device=dev)
+        wd = torch.empty(16 * Cout * Cin, dtype=BF16, device=dev) if need_dx else None
+        call("nk_up2_phase_weights", w2d(weight).data_ptr(), wp.data_ptr(), _p(wd), Cout, Cin, _stream())
+        ws = torch.empty(query("nk_conv2d_up2_ws_bytes", C.byref(d), 0), dtype=torch.uint8, device=dev)
+        call("nk_conv2d_up2_fwd", C.byref(d), x.t.data_ptr(), wp.data_ptr(), _p(bias), y.data_ptr(), ws.data_ptr(), _stream())
+        del wp, ws
     else:
         call("nk_conv2d_fwd", C.byref(d), x.t.data_ptr(), w2d(weight).data_ptr(), _p(bias), _p(rowvec), _p(residual), y.data_ptr(), _stream())
     out = Img(y, x.N, Ho, Wo, sums_out)
+
+    def up2_wgrad(dy: Tensor):
+        ws = torch.empty(query("nk_conv2d_up2_ws_bytes", C.byref(d), 2), dtype=torch.uint8, device=dy.device)
+        if bias is not None:
+            call("nk_conv2d_up2_wgrad_bias", C.byref(d), dy.data_ptr(), x.t.data_ptr(), g2d(weight).data_ptr(), grad_flat(bias).data_ptr(), wgrad_mode(weight),
+                 ws.data_ptr(), _stream())
+        else:
+            call("nk_conv2d_up2_wgrad", C.byref(d), dy.data_ptr(), x.t.data_ptr(), g2d(weight).data_ptr(), wgrad_mode(weight), ws.data_ptr(), _stream())
 
     def bwd(dy: Tensor):
         _check2d(dy, "dy")
@@ -661,7 +698,9 @@ def conv2d_fwd(x: Img, weight: Tensor, bias: Optional[Tensor], stride: int = 1, 
             raise ValueError("conv2d bwd: dy must be dense")
         acc = state_of(weight).grad_accumulate
 
-        if weight.requires_grad:          # frozen convolutions (the LPIPS trunk) only pass the gradient through
+        if weight.requires_grad and up2:
+            on_wgrad_stream(lambda: up2_wgrad(dy), dy, x.t, owner=weight)
+        elif weight.requires_grad:          # frozen convolutions (the LPIPS trunk) only pass the gradient through
             if bias is not None:       # the bias gradient rides in the weight-gradient launch
                 on_wgrad_stream(lambda: call("nk_conv2d_wgrad_bias", C.byref(d), dy.data_ptr(), x.t.data_ptr(), g2d(weight).data_ptr(), grad_flat(bias).data_ptr(),
                                              wgrad_mode(weight), _stream()), dy, x.t, owner=weight)
@@ -675,7 +714,11 @@ def conv2d_fwd(x: Img, weight: Tensor, bias: Optional[Tensor], stride: int = 1, 
             call("nk_colsum_batched", dy.data_ptr(), drow32.data_ptr(), ws.data_ptr(), Ho * Wo, Cout, dy.stride(0), x.N, 0, _stream())   # one pair of launches, not one per image
             drow = cast_bf16(drow32)
         dx = None
-        if need_dx:
+        if need_dx and up2:       # one 4 x 4 / stride 2 convolution of dy straight onto the low-resolution grid
+            dxt = torch.empty(x.N * x.H * x.W, Cin, dtype=BF16, device=dy.device)
+            call("nk_conv2d_up2_dgrad", C.byref(d), dy.data_ptr(), wd.data_ptr(), dxt.data_ptr(), _stream())
+            dx = Img(dxt, x.N, x.H, x.W)
+        elif need_dx:
             dxt = torch.empty(x.N * Hin * Win, Cin, dtype=BF16, device=dy.device)
             # the input gradient of a stride-1 3 x 3 "same" convolution is such a convolution of dy with the mirrored, channel-swapped
             # weights: where the halo-tile forward kernel takes that shape it runs there (one small transposing pass over the weights,
