@@ -560,6 +560,10 @@ typedef struct NkAdafactorArgs {
 long nk_adafactor_tensor_bytes(void);
 int nk_adafactor_init(const NkAdafactorArgs* args, void* stream);
 int nk_adafactor_chunk(const NkAdafactorArgs* args, void* stream);
+/* The same step with the reference's first moment (beta1, adafactor.py:194-196, 242-245): the apply pass keeps
+ * exp_avg = beta1 * exp_avg + (1 - beta1) * scale * u and subtracts that instead of scale * u.  `exp_avg` is one flat fp32 buffer with the
+ * masters' physical layout and element offsets (NkAfTensor.off), zero before the first step; no bias correction.  0 <= beta1 < 1. */
+int nk_adafactor_chunk_momentum(const NkAdafactorArgs* args, float* exp_avg, float beta1, void* stream);
 
 /* Fused multi-tensor CAME on the flat buffers.  Replaces CAME.step, reference optimizers/came.py:115-224: per tensor, Adafactor's
  * factored second moment of g^2+eps1 (R, C; vectors: v), the update u clipped by its RMS (u_hat), a first moment m, and for factored

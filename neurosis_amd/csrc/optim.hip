@@ -17,6 +17,13 @@
 // Infinity Cache for small chunks: the default chunk is 128 MB (NK_AF_CHUNK_MB).  Every reduction goes through per-tile
 // partials combined in a fixed order: no atomics on values, bitwise reproducible.  The tile walk, the strip finish, the conv pairs and the
 // vector loop are optim_common.h's, shared with CAME.
+//
+// First moment (beta1, reference adafactor.py:194-196, 242-245; nk_adafactor_chunk_momentum): passes A and B as above, then pass C as
+// af_apply_momentum_kernel, which keeps m = beta1*m + (1-beta1)*scale*u per element and applies p -= wd*lr*p + m.  m is one flat fp32 buffer
+// with the masters' layout and offsets, read and written once in pass C: 22 B of that pass against 14, 30 B per parameter and step against
+// 22, and 4 B of state per parameter (+10.3 GB for the SDXL UNet).  It is a kernel of its own and not a template parameter of
+// af_apply_kernel: as one template the momentum-free instantiation came out of the compiler with another schedule (packed multiplies,
+// other registers), and that pass is the benchmark's.
 #include "../../include/neurosis_hip.h"
 #include "nk_common.h"
 #include "optim_common.h"
@@ -207,6 +214,93 @@ __global__ __launch_bounds__(256) void af_apply_kernel(const NkAfArgs a) {
   if (tid == 0) a.p2_part[a.item_lo + blockIdx.x] = acc;
 }
 
+// ---- pass C with the first moment: m = beta1 m + (1 - beta1) scale u,  p = p decay - m -------------------------------------------------
+struct AfMoment { float* m; float b1, omb1; };      // the buffer (the masters' layout and offsets), beta1 and 1 - beta1
+
+template <class CV>
+__device__ __forceinline__ float af_conv_apply_momentum(const NkAfArgs& a, const AfMoment& mo, const NkAfTensor& t, const CV& cv, int tr, int tid, float gs,
+                                                        float sc, float decay) {
+  float acc = 0.f;
+  fac_for_pairs(tr, tid, t.d0, t.d1, [&](int o, int i) {
+    float g[3][3], row[3], col[3], f[3][3];
+    fac_conv_load(cv, a.state, t.row_off, t.col_off, o, i, row, col);
+    cv.taps([&](int x, int y) { g[x][y] = a.grad[t.off + cv.tap(o, i, x, y)] * gs; });
+    fac_conv_factor(cv, row, col, f);
+    cv.taps([&](int x, int y) {
+      const long e = t.off + cv.tap(o, i, x, y);
+      const float mn = fac_ema(mo.m[e], mo.b1, sc * (f[x][y] * g[x][y]), mo.omb1);
+      const float pn = a.master[e] * decay - mn;
+      mo.m[e] = mn;
+      a.master[e] = pn;
+      a.shadow[e] = f2bf(pn);
+      acc += pn * pn;
+    });
+  });
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void af_apply_momentum_kernel(const NkAfArgs a, const AfMoment mo) {
+  AF_HEALTH_GATE(a);
+  __shared__ float red[4];
+  const NkAfItem it = a.items[a.item_lo + blockIdx.x];
+  const NkAfTensor t = a.tensors[it.tensor];
+  const int tid = threadIdx.x;
+  const float gs = a.grad_scale;
+  const float sc = a.scale[it.tensor];
+  const float decay = 1.0f - a.weight_decay * a.lr_t[it.tensor];
+  float acc = 0.f;
+  if (t.kind == 1) {
+    const FacTile T(it, t.d0, t.d1, tid);
+    const float mr = fac_mean_slots(a.mean_row, t.mr0, t.d0);
+    float ci[4];
+    T.col_factors(a.state + t.col_off, ci);
+#pragma unroll 1
+    for (int i0 = 0; i0 < AF_TR / 16; i0 += 4) {
+      float4_t g[4], p[4], m[4];
+      float rf[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int r = T.row(i0 + u);
+        const bool ok = T.ok(r);
+        const long o = t.off + T.at(r);
+        g[u] = T.load(ok, a.grad + o);
+        p[u] = T.load(ok, a.master + o);
+        m[u] = T.load(ok, mo.m + o);
+        rf[u] = ok ? rsqrtf(a.state[t.row_off + r] / mr) : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int r = T.row(i0 + u);
+        if (!T.ok(r)) continue;
+        float4_t pn;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          m[u][e] = fac_ema(m[u][e], mo.b1, sc * (rf[u] * ci[e] * (g[u][e] * gs)), mo.omb1);
+          pn[e] = p[u][e] * decay - m[u][e];
+          acc += pn[e] * pn[e];
+        }
+        *(float4_t*)(mo.m + t.off + T.at(r)) = m[u];
+        T.store(a.master, a.shadow, t.off, r, pn);
+      }
+    }
+  } else if (t.kind == 2) {
+    fac_conv_dispatch(t, [&](auto cv) { acc = af_conv_apply_momentum(a, mo, t, cv, it.tr, tid, gs, sc, decay); });
+  } else {
+    fac_for_elems(it.tr, tid, t.d0, [&](long e) {
+      const float g = a.grad[t.off + e] * gs;
+      const float u = g * rsqrtf(a.state[t.row_off + e]);
+      const float mn = fac_ema(mo.m[t.off + e], mo.b1, sc * u, mo.omb1);
+      const float pn = a.master[t.off + e] * decay - mn;
+      mo.m[t.off + e] = mn;
+      a.master[t.off + e] = pn;
+      a.shadow[t.off + e] = f2bf(pn);
+      acc += pn * pn;
+    });
+  }
+  acc = block_sum_256(acc, red);
+  if (tid == 0) a.p2_part[a.item_lo + blockIdx.x] = acc;
+}
+
 // partial sums of p^2 for the FIRST step (afterwards pass C leaves them behind); the item partition is pass C's
 __global__ __launch_bounds__(256) void af_init_p2_kernel(const NkAfArgs a) {
   __shared__ float red[4];
@@ -265,16 +359,29 @@ extern "C" int nk_adafactor_init(const NkAdafactorArgs* h, void* stream) {
   return NK_OK;
 }
 
-extern "C" int nk_adafactor_chunk(const NkAdafactorArgs* h, void* stream_) {
+// one step of a chunk; mo: the first moment of nk_adafactor_chunk_momentum, or null
+static int af_chunk(const NkAdafactorArgs* h, const AfMoment* mo, hipStream_t stream) {
   if (int e = af_check(h)) return e;
-  hipStream_t stream = (hipStream_t)stream_;
   NkAfArgs a = af_args(h);
   if (int e = nk_opt_begin(h->tensor_lo == 0, &a.health)) return e;
   const int nitems = a.item_hi - a.item_lo;
   NK_OPT_LAUNCH(af_stats_kernel, nitems, stream, a);
   if (h->has_matrix) NK_OPT_LAUNCH(af_u2_kernel, nitems, stream, a);
-  NK_OPT_LAUNCH(af_apply_kernel, nitems, stream, a);
+  if (mo) {
+    hipLaunchKernelGGL(af_apply_momentum_kernel, dim3(nitems), dim3(256), 0, stream, a, *mo);
+    if (int e = nk_check_launch("af_apply_momentum_kernel")) return e;
+  } else {
+    NK_OPT_LAUNCH(af_apply_kernel, nitems, stream, a);
+  }
   return nk_opt_end(stream);
+}
+
+extern "C" int nk_adafactor_chunk(const NkAdafactorArgs* h, void* stream) { return af_chunk(h, nullptr, (hipStream_t)stream); }
+
+extern "C" int nk_adafactor_chunk_momentum(const NkAdafactorArgs* h, float* exp_avg, float beta1, void* stream) {
+  NK_CHECK_ARG(exp_avg && beta1 >= 0.0f && beta1 < 1.0f);
+  const AfMoment mo{exp_avg, beta1, 1.0f - beta1};
+  return af_chunk(h, &mo, (hipStream_t)stream);
 }
 
 // ---- LitEma.forward (modules/ema.py:40-59) over the flat buffer: shadow -= (1 - decay) * (shadow - p) -------------------

@@ -169,6 +169,7 @@ SIGNATURES: dict[str, list] = {
     "nk_health_import": [vp, vp],
     "nk_adafactor_init": [vp, vp],
     "nk_adafactor_chunk": [vp, vp],
+    "nk_adafactor_chunk_momentum": [vp, vp, f32, vp],
     "nk_came_chunk": [vp, vp],
     "nk_adamw8bit_step": [vp, vp],
 }

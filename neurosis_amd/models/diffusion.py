@@ -359,11 +359,11 @@ class DiffusionEngine(nn.Module):
         configs/sdxl/sdxl.example.yaml:158-169) for optimizer_step().  kwargs as the reference class's; returns it."""
         if self.store is None:
             raise RuntimeError("call setup_flat_params() first")
-        from ..optim import FlatAdafactor
+        from ..optim import FlatAdafactor, FlatAdafactorMomentum
 
         # block-aligned chunks only when the update is streamed behind backward: otherwise few, large chunks are faster (DESIGN 3.3)
         kwargs.setdefault("boundaries", self._block_boundaries() if self.stream_optimizer else None)
-        self.adafactor = FlatAdafactor(self.store, **kwargs)
+        self.adafactor = (FlatAdafactor if kwargs.get("beta1") is None else FlatAdafactorMomentum)(self.store, **kwargs)
         return self.adafactor
 
     def configure_ema(self, decay: float = 0.9999, use_num_updates: bool = True):
@@ -399,6 +399,8 @@ class DiffusionEngine(nn.Module):
         if sharded and (getattr(self, "model_ema", None) is not None or getattr(self, "adafactor", None) is None or self._streaming_step):
             raise NotImplementedError("the sharded exchange (NK_DP_MODE=rs_ag) needs the fused Adafactor and supports neither EMA (its update reads "
                                       "every fp32 master) nor the streamed update")
+        if sharded and getattr(self.adafactor, "beta1", None) is not None:
+            self.adafactor.restrict_ranges(())          # refuses, by name: the shard gather knows one state span per tensor range
         overlap = self.overlap_optimizer and self.store.master.is_cuda
         scope = nullcontext()
         if overlap:

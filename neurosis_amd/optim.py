@@ -5,10 +5,12 @@ arguments and the same per-tensor rule -- factored second moments over the LAST 
 RMS-scaled relative step, update clipping) but runs as a handful of multi-tensor HIP launches on the flat fp32 master /
 gradient buffers (`csrc/optim.hip`), rewriting the bf16 shadows in the same pass.  `AdafactorScheduler` mirrors :258-291.
 
-Differences, all deliberate: `beta1` (first moment) is not implemented -- the example configs leave it `None`
-(`configs/sdxl/sdxl.example.yaml:158-164`) -- and asking for it raises; state lives in two flat buffers instead of a
+`FlatAdafactorMomentum` is the same optimizer with the reference's first moment (`beta1`, adafactor.py:194-196, 242-245): one more flat
+fp32 buffer, read and written in the apply pass; `FlatAdafactor` itself refuses `beta1` and names the subclass.
+
+Differences, all deliberate: state lives in flat buffers instead of a
 per-parameter dict; `state_dict()` / `load_state_dict()` speak the reference optimizer's checkpoint format (per-parameter
-`step`, `exp_avg_sq_row`, `exp_avg_sq_col` / `exp_avg_sq`, `RMS`) so a run resumes with its second moments, step count
+`step`, `exp_avg_sq_row`, `exp_avg_sq_col` / `exp_avg_sq`, `RMS`, with a first moment `exp_avg`) so a run resumes with its moments, step count
 (relative-step warm-up, beta2_t) and per-tensor RMS intact.  `FlatEma` is an `nn.Module` carrying `LitEma`'s buffer names
 (`decay`, `num_updates`, one shadow per parameter), so `model_ema.*` keys of a reference checkpoint load and save unchanged.
 `FlatCAME` mirrors `neurosis.optimizers.came.CAME` (`optimizers/came.py`) the same way, on `csrc/came.hip`.  `FlatAdamW8bit` is
@@ -230,8 +232,7 @@ class FlatAdafactor(_FlatFactored):
             raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
         if warmup_init and not relative_step:
             raise ValueError("`warmup_init=True` requires `relative_step=True`")
-        if beta1 is not None:
-            raise NotImplementedError("FlatAdafactor: beta1 (first moment) is not implemented; the reference configs use beta1=None")
+        self.beta1 = self._check_beta1(beta1)
         if query("nk_adafactor_tensor_bytes") != AF_TENSOR_DTYPE.itemsize:
             raise RuntimeError("FlatAdafactor: tensor table layout differs from the HIP library's")
         self.lr, self.eps, self.clip_threshold, self.decay_rate = lr, eps, clip_threshold, decay_rate
@@ -252,6 +253,11 @@ class FlatAdafactor(_FlatFactored):
         self._p2_valid = False
         self.owned = None          # restrict_ranges(): [(tensor_lo, tensor_hi), ...] this process updates; None = everything
         store.add_listener(self)
+
+    def _check_beta1(self, beta1: Optional[float]) -> Optional[float]:
+        if beta1 is not None:
+            raise NotImplementedError("FlatAdafactor: beta1 (first moment) is FlatAdafactorMomentum's: this class keeps no exp_avg buffer")
+        return None
 
     def restrict(self, tensor_lo: int, tensor_hi: int) -> None:
         self.restrict_ranges([(tensor_lo, tensor_hi)])
@@ -348,9 +354,11 @@ class FlatAdafactor(_FlatFactored):
         if not self._mine(ci):          # another rank's shard
             self._done[ci] = True
             return
-        a = self._args(self.chunks[ci], self._beta2t, self._rel, grad_scale, ws_slot)
-        call("nk_adafactor_chunk", C.byref(a), ops._stream())
+        self._launch_chunk(self._args(self.chunks[ci], self._beta2t, self._rel, grad_scale, ws_slot))
         self._done[ci] = True
+
+    def _launch_chunk(self, a: _Args) -> None:
+        call("nk_adafactor_chunk", C.byref(a), ops._stream())
 
     def chunks_in(self, tensor_lo: int, tensor_hi: int) -> list:
         """indices of the chunks that lie entirely inside tensors [tensor_lo, tensor_hi)"""
@@ -392,7 +400,7 @@ class FlatAdafactor(_FlatFactored):
         return st
 
     def _group_dict(self) -> dict:
-        return dict(lr=self.lr, eps=self.eps, clip_threshold=self.clip_threshold, decay_rate=self.decay_rate, beta1=None,
+        return dict(lr=self.lr, eps=self.eps, clip_threshold=self.clip_threshold, decay_rate=self.decay_rate, beta1=self.beta1,
                     weight_decay=self.weight_decay, scale_parameter=self.scale_parameter, relative_step=self.relative_step,
                     warmup_init=self.warmup_init)
 
@@ -400,13 +408,55 @@ class FlatAdafactor(_FlatFactored):
         return True
 
     def _check_entry(self, i: int, st: dict, mine: dict) -> None:
+        who = f"{type(self).__name__}.load_state_dict"
+        if ("exp_avg" in mine) != ("exp_avg" in st):
+            raise ValueError(f"{who}: parameter {i} has {'a' if 'exp_avg' in mine else 'no'} first moment here (beta1={self.beta1}) but the "
+                             f"checkpoint has {'none' if 'exp_avg' in mine else 'one'} (exp_avg)")
         for k in ("exp_avg_sq_row", "exp_avg_sq_col", "exp_avg_sq"):
             if (k in mine) != (k in st):
-                raise ValueError(f"FlatAdafactor.load_state_dict: parameter {i} is {'not ' if k not in mine else ''}factored here but the checkpoint disagrees ({k})")
+                raise ValueError(f"{who}: parameter {i} is {'not ' if k not in mine else ''}factored here but the checkpoint disagrees ({k})")
 
     def _copy_state(self, state: dict) -> None:
         super()._copy_state(state)
         self._p2_valid = False       # RMS(p) is recomputed from the (separately restored) parameters
+
+
+class FlatAdafactorMomentum(FlatAdafactor):
+    """FlatAdafactor with the reference's first moment (adafactor.py:194-196, 242-245): after the clipped, scaled update u~ = scale u has
+    been formed, exp_avg = beta1 exp_avg + (1 - beta1) u~ (fp32, zero at the first step, no bias correction) and p = p (1 - wd lr_t) - exp_avg.
+    Same constructor with a mandatory `beta1` in [0, 1).  `exp_avg` is one flat fp32 buffer with the masters' physical layout and element
+    offsets, read and written by the apply pass (`nk_adafactor_chunk_momentum`): 4 B of state and 8 B of traffic more per parameter.  It never
+    crosses a tensor, so chunks may go in any order, on one stream or two.  The sharded exchange is refused: its shard gather knows one
+    state span per tensor range."""
+
+    def __init__(self, store, *args, **kwargs):
+        super().__init__(store, *args, **kwargs)
+        self.exp_avg = torch.zeros(store.master.numel(), dtype=torch.float32, device=store.master.device)
+
+    def _check_beta1(self, beta1: Optional[float]) -> float:
+        if beta1 is None:
+            raise ValueError("FlatAdafactorMomentum: beta1 is required (FlatAdafactor is the optimizer without a first moment)")
+        if not 0.0 <= beta1 < 1.0:
+            raise ValueError(f"FlatAdafactorMomentum: beta1 must be in [0, 1), got {beta1}")
+        return float(beta1)
+
+    def reset_state(self) -> None:
+        super().reset_state()
+        self.exp_avg.zero_()
+
+    def restrict_ranges(self, ranges) -> None:
+        raise NotImplementedError("FlatAdafactorMomentum: the sharded exchange (rs_ag) with a first moment (beta1) is not built: the shard "
+                                  "gather knows one state span per tensor range")
+
+    def _launch_chunk(self, a: _Args) -> None:
+        call("nk_adafactor_chunk_momentum", C.byref(a), self.exp_avg.data_ptr(), self.beta1, ops._stream())
+
+    def param_state(self, index: int) -> dict:
+        """FlatAdafactor's entries and `exp_avg` in the parameter's logical shape (conv weights: an OIHW view of the physical
+        [O][KH][KW][I] slice)"""
+        st = super().param_state(index)
+        st["exp_avg"] = self.store._view(self.exp_avg, int(self._tens_np[index]["off"]), self.store.params[index])
+        return st
 
 
 class AdafactorScheduler:

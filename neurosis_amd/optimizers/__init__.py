@@ -7,8 +7,10 @@ Every class here is a real `torch.optim.Optimizer` (so LightningCLI's `Optimizer
 checkpointing accept it) under its upstream constructor, whose `step()` is a fused update on the flat fp32 master / gradient buffers of
 a `FlatParamStore`; `_base._FusedOptimizer` holds what they share, and says what happens to parameters that have no store yet.
 
-`Adafactor` keeps the reference class's constructor (`optimizers/adafactor.py:100-131`) over `neurosis_amd.optim.FlatAdafactor`.  Its
-hyper-parameters are read when the flat optimizer is built, not at every step, and `step` is kept per parameter.
+`Adafactor` keeps the reference class's constructor (`optimizers/adafactor.py:100-131`) over `neurosis_amd.optim.FlatAdafactor`, or, when
+the group sets `beta1`, over `neurosis_amd.optim.FlatAdafactorMomentum`: the reference's first moment (`exp_avg`, one more fp32 value per
+parameter) kept by the same fused update.  Its hyper-parameters are read when the flat optimizer is built, not at every step, and `step`
+is kept per parameter.
 
 `CAME` (`neurosis.optimizers.came.CAME`, reference `optimizers/came.py`) is the fused `neurosis_amd.optim.FlatCAME` under the
 reference class's constructor: Adafactor's factored second moment plus a first moment and a factored confidence statistic, 4 B of
@@ -34,7 +36,7 @@ from typing import Optional
 from torch.optim import Optimizer
 from torch.optim.lr_scheduler import LambdaLR
 
-from ..optim import FlatAdafactor
+from ..optim import FlatAdafactor, FlatAdafactorMomentum
 from ._base import _FusedOptimizer, _group_store
 from .adamw8bit import AdamW8bit
 from .came import CAME
@@ -54,18 +56,19 @@ class Adafactor(_FusedOptimizer):
             raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
         if warmup_init and not relative_step:
             raise ValueError("`warmup_init=True` requires `relative_step=True`")
-        if beta1 is not None:
-            raise NotImplementedError("neurosis_amd.optimizers.Adafactor: beta1 (first moment) is not fused; the reference configs use beta1=None")
+        if beta1 is not None and not 0.0 <= beta1 < 1.0:
+            raise ValueError(f"beta1 must be None or in [0, 1), got {beta1}")
         defaults = dict(lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1, weight_decay=weight_decay,
                         scale_parameter=scale_parameter, relative_step=relative_step, warmup_init=warmup_init, differentiable=False)
         super().__init__(params, defaults)
 
     def _make_flat(self, g: dict) -> FlatAdafactor:
         """Built once from the group's hyper-parameters: step() does not read them again (only `grad_scale` reaches the update)."""
-        return FlatAdafactor(_group_store(g, "Adafactor"), lr=g["lr"] if not g["relative_step"] else None, eps=tuple(g["eps"]),
-                             clip_threshold=g["clip_threshold"], decay_rate=g["decay_rate"], beta1=g["beta1"],
-                             weight_decay=g["weight_decay"], scale_parameter=g["scale_parameter"],
-                             relative_step=g["relative_step"], warmup_init=g["warmup_init"], boundaries=g.get("chunk_boundaries"))
+        flat = FlatAdafactor if g["beta1"] is None else FlatAdafactorMomentum
+        return flat(_group_store(g, "Adafactor"), lr=g["lr"] if not g["relative_step"] else None, eps=tuple(g["eps"]),
+                    clip_threshold=g["clip_threshold"], decay_rate=g["decay_rate"], beta1=g["beta1"], weight_decay=g["weight_decay"],
+                    scale_parameter=g["scale_parameter"], relative_step=g["relative_step"], warmup_init=g["warmup_init"],
+                    boundaries=g.get("chunk_boundaries"))
 
     @staticmethod
     def _get_lr(param_group: dict, param_state: dict) -> float:

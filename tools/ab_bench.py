@@ -1,7 +1,8 @@
 """Alternating A/B of the metric's own command on ONE box: every variant is a fresh `python bench.py` process (graph replay, all streams, as
 the driver runs it), variants interleaved round by round so that box-to-box and drift effects cancel.
 usage: python tools/ab_bench.py [--rounds 2] [--steps 8] [--args "--precomputed-te"] VARIANT [VARIANT ...]
-       a VARIANT is ENV=VALUE[,ENV=VALUE...] or the word base.   (The parent never touches the GPU.)"""
+       a VARIANT is ENV=VALUE[,ENV=VALUE...], the word base, or tree:PATH (the bench.py of another source tree, built, e.g. the parent commit's).
+       (The parent never touches the GPU.)"""
 import argparse
 import json
 import os
@@ -19,11 +20,14 @@ res = {v: [] for v in a.variants}
 for rnd in range(a.rounds):
     for v in a.variants:
         env = dict(os.environ)
-        if v != "base":
+        tree = root
+        if v.startswith("tree:"):
+            tree = os.path.abspath(v[5:])
+        elif v != "base":
             for kv in v.split(","):
                 k, val = kv.split("=", 1)
                 env[k] = val
-        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(a.steps), "--no-cpu-baseline", "--no-roofline"] + a.args.split(),
+        p = subprocess.run([sys.executable, os.path.join(tree, "bench.py"), "--steps", str(a.steps), "--no-cpu-baseline", "--no-roofline"] + a.args.split(),
                            env=env, capture_output=True, text=True)
         line = next((l for l in p.stdout.splitlines() if l.startswith("{")), None)
         if line is None:
