@@ -3,9 +3,11 @@
 selection and return conventions of `neurosis.models.text_encoder.clip` (:22-388).
 
 The reference delegates the transformer itself to third-party code (transformers' CLIPTextModel, open_clip's CLIP); here both
-towers are one pre-LN causal transformer over the HIP kernels -- LayerNorm, QKV / out / MLP GEMMs with fused bias and
-residual, the fused attention kernel with its causal flag (77 tokens: one key tile), GELU -- that differ only in parameter
-names and activation, so that either checkpoint layout loads unchanged:
+towers are the pre-norm block of transformer.py (shared with the T5 towers) over the HIP kernels -- LayerNorm, QKV / out / MLP GEMMs
+with fused bias and residual, the fused attention kernel with its causal flag (77 tokens: one key tile), GELU (`_clip_ops`).  Each
+layer module describes itself to the block by a `Block` record (`.spec`); the HF layout's q / k / v projections run as ONE GEMM through
+a `Packed` copy.  What is left here is what differs: parameter names, so that either checkpoint layout loads unchanged, the embedding
+and the output selection (hidden-state taps, the final LayerNorm, the end-of-text gather, bigG's projection):
 
     HF        text_model.embeddings.{token,position}_embedding.weight, text_model.encoder.layers.N.{self_attn.{q,k,v,out}_proj,
               layer_norm1, layer_norm2, mlp.fc1, mlp.fc2}, text_model.final_layer_norm          (transformers 4.x naming;
@@ -15,7 +17,7 @@ names and activation, so that either checkpoint layout loads unchanged:
 
 Frozen towers (the SDXL configs) run their forward under no_grad, replayed from hipGraphs.  An embedder built with is_trainable=True
 (configs/sdxl/sdxl-te.example.yaml) returns outputs that autograd connects, through nn.apply_module, to ONE closure chain per tower: the
-embedding, every layer's LayerNorms, GEMMs, causal attention (ops.attention_causal_fwd) and GELU (ops.gelu_fwd), and for bigG's pooled
+embedding, every layer's transformer.block_train (LayerNorms, GEMMs, ops.attention_causal_fwd, ops.gelu_fwd), and for bigG's pooled
 output ln_final, the end-of-text gather and text_projection -- all HIP kernels forward and backward.  Only the layers the selected
 outputs depend on run; parameters they do not depend on get no gradient (trained_parameters(): what DiffusionEngine puts in the tower's
 flat store and optimizer group).
@@ -32,57 +34,21 @@ import torch
 from torch import Tensor, nn
 
 from ... import ops
-from ...graphs import ForwardGraphs, frozen_stamp, graphs_enabled
-from ...nn import apply_module, as_tokens
+from ...graphs import frozen_stamp
+from ...nn import apply_module
 from ...modules.encoders.embedding import AbstractEmbModel
+from .transformer import (Block, Packed, _chain_train, _check_ids, _decode_text, _forward_graphs, _graphable, _out_grads, _trainable, block_forward,
+                          block_train, norm)
 
 logger = logging.getLogger(__name__)
 LN_EPS = 1e-5
 
 
-# ---------------------------------------------------------------------------------------------------
-# the transformer both towers share
-# ---------------------------------------------------------------------------------------------------
-def _linear(x: Tensor, layer: nn.Linear, residual: Optional[Tensor] = None) -> Tensor:
-    return ops.gemm_nt(x, ops.w2d(layer.weight), layer.bias, residual=residual)
-
-
-def _norm(x: Tensor, layer: nn.LayerNorm) -> Tensor:
-    return ops.layernorm_fwd(x, layer.weight, layer.bias, layer.eps)[0]
-
-
-def _residual_block(x: Tensor, batch: int, heads: int, ln_1, qkv, out_proj, ln_2, fc_in, fc_out, quick_gelu: bool) -> Tensor:
-    """x + attn(ln_1 x), then x + mlp(ln_2 x), on a dense bf16 token matrix [batch * L, width].  `qkv` maps the normed
-    tokens to the (q, k, v) token matrices (column slices of one fused projection where the checkpoint stores it fused)."""
-    width = x.shape[1]
-    q, k, v = qkv(_norm(x, ln_1))
-    attended = ops.attention_fwd(q, k, v, batch, heads, width // heads, causal=True)[0]
-    x = _linear(attended, out_proj, residual=x)
-    hidden = ops.gelu(_linear(_norm(x, ln_2), fc_in), quick=quick_gelu)
-    return _linear(hidden, fc_out, residual=x)
-
-
-def _residual_block_train(x: Tensor, batch: int, heads: int, ln_1, qkv, out_proj, ln_2, fc_in, fc_out, quick_gelu: bool):
-    """_residual_block with its backward: (x', bwd(dx') -> dx).  `qkv(h)` returns (fused [M, 3 width] = [q | k | v], bwd(dfused) -> dh).
-    Parameter gradients go to .grad in their engine's mode (ops.linear_fwd / layernorm_fwd closures, the packed projection's own)."""
-    width = x.shape[1]
-    h1, b_ln1 = ops.layernorm_fwd(x, ln_1.weight, ln_1.bias, ln_1.eps)
-    fused, b_qkv = qkv(h1)
-    q, k, v = fused[:, :width], fused[:, width:2 * width], fused[:, 2 * width:]
-    attended, b_att = ops.attention_causal_fwd(q, k, v, batch, heads, width // heads)
-    x1, b_out = ops.linear_fwd(attended, out_proj.weight, out_proj.bias, residual=x)
-    h2, b_ln2 = ops.layernorm_fwd(x1, ln_2.weight, ln_2.bias, ln_2.eps)
-    u, b_fc1 = ops.linear_fwd(h2, fc_in.weight, fc_in.bias)
-    g, b_gelu = ops.gelu_fwd(u, quick_gelu)
-    x2, b_fc2 = ops.linear_fwd(g, fc_out.weight, fc_out.bias, residual=x1)
-
-    def bwd(dx2: Tensor) -> Tensor:
-        dx1 = b_ln2(b_fc1(b_gelu(b_fc2(dx2))), dx_add=dx2)
-        dfused = torch.empty_like(fused)
-        b_att(b_out(dx1), dq=dfused[:, :width], dk=dfused[:, width:2 * width], dv=dfused[:, 2 * width:])
-        return b_ln1(b_qkv(dfused), dx_add=dx1)
-
-    return x2, bwd
+def _clip_ops(B: int, heads: int, width: int, quick_gelu: bool, train: bool):
+    """(attend, act) of a CLIP block (transformer.block_forward / block_train): causal attention and GELU, forward-only or with a backward"""
+    if train:
+        return (lambda q, k, v: ops.attention_causal_fwd(q, k, v, B, heads, width // heads)), (lambda u: ops.gelu_fwd(u, quick_gelu))
+    return (lambda q, k, v: ops.attention_fwd(q, k, v, B, heads, width // heads, causal=True)[0]), (lambda u: ops.gelu(u, quick=quick_gelu))
 
 
 def _embed(ids: Tensor, table: Tensor, positions: Tensor) -> Tensor:
@@ -129,59 +95,6 @@ def _final_train(x: Tensor, B: int, L: int, ln, eot: Tensor, want_tokens: bool, 
     return outs, bwd
 
 
-def _chain_train(x: Tensor, blocks, taps):
-    """Run `blocks` (callables x -> (x', bwd)) from the embedding output x; returns ({i: state i for i in taps}, last state, bwd(grads, dtop)),
-    state i being the input of block i (state len(blocks) the last output).  bwd adds each tap's gradient where its state enters, walks the
-    blocks backwards and returns the gradient of x."""
-    states, closures = {0: x} if 0 in taps else {}, []
-    for i, block in enumerate(blocks):
-        x, b = block(x)
-        closures.append(b)
-        if i + 1 in taps:
-            states[i + 1] = x
-
-    def bwd(grads: dict, dtop: Optional[Tensor]) -> Tensor:
-        d = dtop
-        for i in range(len(closures), -1, -1):
-            g = grads.get(i)
-            if g is not None:
-                d = g if d is None else ops.add(d, g)
-            if i > 0:
-                d = closures[i - 1](d)
-        return d
-
-    return states, x, bwd
-
-
-def _trainable(embedder, tower: nn.Module) -> bool:
-    """the embedder's forward runs the autograd-connected training chain"""
-    return embedder.is_trainable and torch.is_grad_enabled() and any(p.requires_grad for p in tower.parameters())
-
-
-def _out_grads(gouts, n: int):
-    """the first n incoming gradients as dense bf16 token matrices (None where autograd passed none)"""
-    return [None if g is None else as_tokens(g.contiguous()) for g in gouts[:n]]
-
-
-def _graphable(tower: nn.Module, ids: Tensor) -> bool:
-    """A frozen tower on the GPU runs its ~250-450 dependent small launches from a hipGraph (neurosis_amd/graphs.py): they are
-    launch-latency, not work (4-5 ms of the SDXL step for both towers)."""
-    return ids.is_cuda and graphs_enabled("te") and not any(p.requires_grad for p in tower.parameters())
-
-
-def _forward_graphs(tower: nn.Module) -> ForwardGraphs:
-    fg = tower.__dict__.get("_nk_fgraphs")
-    if fg is None:
-        fg = tower.__dict__["_nk_fgraphs"] = ForwardGraphs(next(tower.parameters()).device)
-    return fg
-
-
-def _check_ids(ids: Tensor, device) -> Tensor:
-    if ids.dtype not in (torch.int64, torch.int32):
-        raise TypeError(f"token ids must be an integer tensor, got {ids.dtype}")
-    return ids.to(device=device, dtype=torch.int64)
-
-
 # ---------------------------------------------------------------------------------------------------
 # HuggingFace layout (CLIPTextModel)
 # ---------------------------------------------------------------------------------------------------
@@ -189,43 +102,6 @@ class _HFAttention(nn.Module):
     def __init__(self, width: int):
         super().__init__()
         self.k_proj, self.v_proj, self.q_proj, self.out_proj = (nn.Linear(width, width) for _ in range(4))
-        self._packed = None
-
-    def qkv(self, h: Tensor):
-        """q, k, v of the normed tokens from ONE GEMM: the three projections packed [q; k; v] (bf16 weight, fp32 bias), rebuilt
-        only when one of the six tensors changes -- 24 launches fewer per CLIP-L forward than three GEMMs per layer"""
-        width = self.q_proj.weight.shape[0]
-        fused = self._fused(h)
-        return fused[:, :width], fused[:, width:2 * width], fused[:, 2 * width:]
-
-    def _fused(self, h: Tensor) -> Tensor:
-        parts = (self.q_proj, self.k_proj, self.v_proj)
-        stamp = tuple(ops._param_stamp(t) for lin in parts for t in (lin.weight, lin.bias))
-        if self._packed is None or self._packed[0] != stamp:
-            weight = torch.cat([ops.w2d(lin.weight) for lin in parts], dim=0).contiguous()
-            bias = torch.cat([lin.bias.detach().float() for lin in parts]).contiguous()
-            self._packed = (stamp, weight, bias)
-        return ops.gemm_nt(h, self._packed[1], self._packed[2])
-
-
-    def qkv_train(self, h: Tensor):
-        """(fused [q | k | v], bwd(dfused) -> dh): the input gradient through the packed weight, the weight gradients split back to the three
-        projections (column slices of dfused)"""
-        fused = self._fused(h)
-        packed = self._packed[1]
-        parts = (self.q_proj, self.k_proj, self.v_proj)
-
-        def bwd(dfused: Tensor) -> Tensor:
-            width = parts[0].weight.shape[0]
-
-            def wgrads():
-                for i, lin in enumerate(parts):
-                    ops.gemm_tn_f32(dfused[:, i * width:(i + 1) * width], h, ops.g2d(lin.weight), ops.wgrad_mode(lin.weight), dbias=ops.grad_flat(lin.bias))
-
-            ops.on_wgrad_stream(wgrads, dfused, h, owner=parts[0].weight)
-            return ops.gemm_nn(dfused, packed)
-
-        return fused, bwd
 
 
 class _HFMLP(nn.Module):
@@ -241,6 +117,9 @@ class _HFLayer(nn.Module):
         self.layer_norm1 = nn.LayerNorm(width, eps=LN_EPS)
         self.mlp = _HFMLP(width, inner)
         self.layer_norm2 = nn.LayerNorm(width, eps=LN_EPS)
+        a = self.self_attn
+        self.__dict__["spec"] = Block(self.layer_norm1, Packed(a.q_proj, a.k_proj, a.v_proj), width, a.out_proj, self.layer_norm2,
+                                      Packed(self.mlp.fc1), self.mlp.fc2)
 
 
 class CLIPTextTower(nn.Module):
@@ -283,20 +162,18 @@ class CLIPTextTower(nn.Module):
         B, L = ids.shape
         x = _embed(ids, tm.embeddings.token_embedding.weight, tm.embeddings.position_embedding.weight)
         states = [x] if output_hidden_states else None
+        attend, act = _clip_ops(B, self.heads, x.shape[1], self.quick_gelu, train=False)
         for layer in tm.encoder.layers:
-            attn = layer.self_attn
-            x = _residual_block(x, B, self.heads, layer.layer_norm1, attn.qkv, attn.out_proj, layer.layer_norm2, layer.mlp.fc1, layer.mlp.fc2, self.quick_gelu)
+            x = block_forward(x, layer.spec, attend, act)
             if states is not None:
                 states.append(x)
-        last = _norm(x, tm.final_layer_norm).float().reshape(B, L, -1)
-        # the pooled vector is the end-of-text position: the highest id in the legacy vocabulary (eos_token_id == 2 configs),
-        # else the first occurrence of eos_token_id
-        eos = ids.argmax(-1) if self.eos_token_id == 2 else (ids == self.eos_token_id).int().argmax(-1)
-        return {"last_hidden_state": last, "pooler_output": last[torch.arange(B, device=last.device), eos],
+        last = norm(x, tm.final_layer_norm).float().reshape(B, L, -1)
+        return {"last_hidden_state": last, "pooler_output": last[torch.arange(B, device=last.device), self._eos(ids)],
                 "hidden_states": None if states is None else tuple(s.float().reshape(B, L, -1) for s in states)}
 
-
     def _eos(self, ids: Tensor) -> Tensor:
+        """the pooled vector's position, the end of text: the highest id in the legacy vocabulary (eos_token_id == 2 configs), else the
+        first occurrence of eos_token_id"""
         return ids.argmax(-1) if self.eos_token_id == 2 else (ids == self.eos_token_id).int().argmax(-1)
 
     def train_depth(self, state: Optional[int], want_last: bool, want_pooled: bool) -> int:
@@ -314,8 +191,8 @@ class CLIPTextTower(nn.Module):
             B, L = ids.shape
             emb = tm.embeddings
             x, b_emb = _embed_train(ids, emb.token_embedding.weight, emb.position_embedding.weight)
-            blocks = [lambda h, l=l: _residual_block_train(h, B, self.heads, l.layer_norm1, l.self_attn.qkv_train, l.self_attn.out_proj, l.layer_norm2,
-                                                          l.mlp.fc1, l.mlp.fc2, self.quick_gelu) for l in layers]
+            attend, act = _clip_ops(B, self.heads, x.shape[1], self.quick_gelu, train=True)
+            blocks = [lambda h, l=l: block_train(h, l.spec, attend, act) for l in layers]
             states, top, b_chain = _chain_train(x, blocks, set() if state is None else {state})
             outs = [] if state is None else [states[state].float().reshape(B, L, -1)]
             b_final = None
@@ -363,6 +240,9 @@ class _ResBlock(nn.Module):
         self.attn = _PackedAttention(width)
         self.ln_2 = nn.LayerNorm(width, eps=LN_EPS)
         self.mlp = _OpenCLIPMLP(width, inner)
+        a = self.attn
+        self.__dict__["spec"] = Block(self.ln_1, Packed((a.in_proj_weight, a.in_proj_bias)), width, a.out_proj, self.ln_2, Packed(self.mlp.c_fc),
+                                      self.mlp.c_proj)
 
 
 class OpenCLIPTextTower(nn.Module):
@@ -388,10 +268,9 @@ class OpenCLIPTextTower(nn.Module):
 
     def _projection_t(self) -> Tensor:
         """text_projection^T as the [embed_dim, width] bf16 matrix gemm_nt reads"""
-        cached = self._projection_cache
-        if cached is None or cached[0] != (ops.state.param_epoch, self.text_projection.data_ptr(), self.text_projection._version):
-            w = ops.cast_bf16(self.text_projection.detach().t().contiguous().float())
-            cached = self._projection_cache = ((ops.state.param_epoch, self.text_projection.data_ptr(), self.text_projection._version), w)
+        cached, stamp = self._projection_cache, ops._param_stamp(self.text_projection)
+        if cached is None or cached[0] != stamp:
+            cached = self._projection_cache = (stamp, ops.cast_bf16(self.text_projection.detach().t().contiguous().float()))
         return cached[1]
 
     @torch.no_grad()
@@ -408,20 +287,14 @@ class OpenCLIPTextTower(nn.Module):
         x = _embed(ids, self.token_embedding.weight, self.positional_embedding)
         width = x.shape[1]
         penultimate = x
+        attend, act = _clip_ops(B, self.heads, width, self.quick_gelu, train=False)
         for block in self.transformer.resblocks:
             penultimate = x
-            attn = block.attn
-
-            def packed_qkv(h, a=attn):
-                fused = ops.gemm_nt(h, ops.w2d(a.in_proj_weight), a.in_proj_bias)
-                return fused[:, :width], fused[:, width:2 * width], fused[:, 2 * width:]
-
-            x = _residual_block(x, B, self.heads, block.ln_1, packed_qkv, attn.out_proj, block.ln_2, block.mlp.c_fc, block.mlp.c_proj, self.quick_gelu)
-        normed = _norm(x, self.ln_final).reshape(B, L, width)
+            x = block_forward(x, block.spec, attend, act)
+        normed = norm(x, self.ln_final).reshape(B, L, width)
         eot = normed[torch.arange(B, device=ids.device), ids.argmax(dim=-1)].contiguous()       # highest id = end of text
         pooled = ops.gemm_nt(eot, self._projection_t())
         return {"last": x.float().reshape(B, L, width), "penultimate": penultimate.float().reshape(B, L, width), "pooled": pooled.float()}
-
 
     def train_depth(self, want_last: bool, want_pooled: bool) -> int:
         """blocks the training forward runs: all of them for "last" / "pooled", all but the last for "penultimate" alone"""
@@ -440,16 +313,8 @@ class OpenCLIPTextTower(nn.Module):
             B, L = ids.shape
             x, b_emb = _embed_train(ids, self.token_embedding.weight, self.positional_embedding)
             width = x.shape[1]
-
-            def block_fn(h, blk):
-                a = blk.attn
-
-                def packed_qkv(hn):
-                    return ops.linear_fwd(hn, a.in_proj_weight, a.in_proj_bias)
-
-                return _residual_block_train(h, B, self.heads, blk.ln_1, packed_qkv, a.out_proj, blk.ln_2, blk.mlp.c_fc, blk.mlp.c_proj, self.quick_gelu)
-
-            states, top, b_chain = _chain_train(x, [lambda h, blk=blk: block_fn(h, blk) for blk in blocks_], taps)
+            attend, act = _clip_ops(B, self.heads, width, self.quick_gelu, train=True)
+            states, top, b_chain = _chain_train(x, [lambda h, blk=blk: block_train(h, blk.spec, attend, act) for blk in blocks_], taps)
             outs = [states[i].float().reshape(B, L, width) for i in sorted(taps)]
             b_final = None
             if want_pooled:
@@ -471,12 +336,6 @@ class OpenCLIPTextTower(nn.Module):
 # ---------------------------------------------------------------------------------------------------
 # embedders
 # ---------------------------------------------------------------------------------------------------
-def _decode_text(text) -> list:
-    if isinstance(text, (str, bytes, np.bytes_)):
-        text = [text]
-    return [t.decode("utf-8") if isinstance(t, (bytes, np.bytes_)) else t for t in text]
-
-
 class _TokenizingEmbedder(AbstractEmbModel):
     """tokenisation shared by both embedders (reference :156-202 and :348-388 are the same code twice)"""
 
@@ -579,16 +438,11 @@ class FrozenCLIPEmbedder(_TokenizingEmbedder):
         return [p for p in self.parameters() if id(p) in ids]
 
     def _forward_trainable(self, text):
-        if self.extended_chunks > 1:
-            raise NotImplementedError("a trainable FrozenCLIPEmbedder does not support extended_chunks > 1")
         ids = _check_ids(self._ids_for(text), self.transformer.text_model.embeddings.token_embedding.weight.device)
         state, want_last, want_pooled = self._train_spec()
         outs = list(self.transformer.train_outputs(ids, state, want_last, want_pooled))
         pooled = outs[-1] if want_pooled else None
-        if self.layer == "pooled":
-            z = pooled[:, None, :]
-        else:
-            z = outs[0]
+        z = pooled[:, None, :] if self.layer == "pooled" else outs[0]
         return (z, pooled) if self.return_pooled else z
 
     def _select(self, out: dict) -> Tensor:
@@ -670,16 +524,10 @@ class FrozenOpenCLIPEmbedder2(_TokenizingEmbedder):
         return [p for p in self.parameters() if id(p) in ids]
 
     def _forward_trainable(self, text):
-        if self.legacy or self.extended_chunks > 1:
-            raise NotImplementedError("a trainable FrozenOpenCLIPEmbedder2 supports neither legacy=True nor extended_chunks > 1")
         ids = _check_ids(self._ids_for(text), self.model.token_embedding.weight.device)
         want = self._train_spec()
         outs = dict(zip([k for k, w in zip(("penultimate", "last", "pooled"), want) if w], self.model.train_outputs(ids, *want)))
-        if self.layer == "pooled":
-            z = outs["pooled"]
-        else:
-            z = outs[self.layer]
-        return (z, outs["pooled"]) if self.return_pooled else z
+        return (outs[self.layer], outs["pooled"]) if self.return_pooled else outs[self.layer]
 
     def encode_with_transformer(self, text: Tensor):
         out = self.model(text)
@@ -688,7 +536,7 @@ class FrozenOpenCLIPEmbedder2(_TokenizingEmbedder):
         # legacy: the chosen layer's tokens through ln_final, nothing else
         chosen = out[self.layer]
         B, L, width = chosen.shape
-        return _norm(ops.cast_bf16(chosen.reshape(B * L, width)), self.model.ln_final).float().reshape(B, L, width)
+        return norm(ops.cast_bf16(chosen.reshape(B * L, width)), self.model.ln_final).float().reshape(B, L, width)
 
     def forward(self, text: Union[str, list, Tensor]):
         if _trainable(self, self.model):

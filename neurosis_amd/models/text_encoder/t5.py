@@ -3,13 +3,15 @@ conventions of `neurosis.models.text_encoder.t5` (:14-101), over `T5EncoderTower
 on the HIP kernels.
 
 The reference delegates the transformer to transformers' T5EncoderModel and calls it with `input_ids` only (:38-53), so there is no padding
-mask: every position attends to every position.  What T5 needs and the CLIP towers do not:
+mask: every position attends to every position.  The block itself is transformer.py's, shared with the CLIP towers (each `_Block`
+describes itself by a `Block` record, `.spec`); this file holds T5's parameter names, `rel_table` and the embedders.  What T5 hands
+the block that the CLIP towers do not:
 
     T5LayerNorm           ops.rmsnorm: x * rsqrt(mean(x^2) + eps) * weight, no mean subtraction, no bias
     self-attention        ops.attention_relbias_fwd: softmax(q k^T + bias) v -- NO 1/sqrt(d) scaling, bidirectional, with block 0's
                           relative position bias shared by every layer.  The bias depends only on (key - query) position, so it is
                           handed to the kernel as one fp32 row of 2 L - 1 entries per head (`T5EncoderTower.rel_table`)
-    FeedForward           T5 v1.1 / ByT5 "gated-gelu": wo(gelu_new(wi_0 x) * wi_1 x), [wi_0; wi_1] as ONE stacked projection + ops.gated_act;
+    FeedForward           T5 v1.1 / ByT5 "gated-gelu": wo(gelu_new(wi_0 x) * wi_1 x), [wi_0; wi_1] as ONE `Packed` projection + ops.gated_act;
                           T5 v1.0 "relu": wo(relu(wi x))
 
 Projections carry no bias; num_heads * d_kv need not equal d_model (t5-v1.1-small, ByT5).  The state_dict is T5EncoderModel's:
@@ -24,8 +26,8 @@ encoder parameters).
 
 Trained with the UNet (`is_trainable: true` and `freeze: false` in the conditioner config, the reference's condition), the embedder's forward
 runs `T5EncoderTower.train_outputs`: the same kernels and the same bits as the frozen forward, autograd-connected through nn.apply_module to
-one closure chain -- per block rmsnorm_fwd, the stacked q / k / v projection, attention_relbias_train, the o projection with residual,
-rmsnorm_fwd, the stacked wi projection, gated_act_fwd, wo with residual; then the final rmsnorm.  Every layer's backward adds its gradient
+one closure chain -- per block transformer.block_train (rmsnorm_fwd, the packed q / k / v projection, attention_relbias_train, the o
+projection with residual, rmsnorm_fwd, the packed wi projection, gated_act_fwd, wo with residual); then the final rmsnorm.  Every layer's backward adds its gradient
 of the bias table into ONE d_rel [heads, 2 L - 1]; after block 0's backward ops.relbias_bucket_sum folds it into
 relative_attention_bias.weight's gradient, once, and ops.embedding_bwd writes the (tied) embedding's.  DiffusionEngine gives the tower a
 FlatParamStore and an optimizer group of its own, as it does for the CLIP towers.
@@ -45,7 +47,8 @@ from ... import ops
 from ...graphs import frozen_stamp
 from ...modules.encoders.embedding import AbstractEmbModel
 from ...nn import apply_module
-from .clip import _chain_train, _check_ids, _decode_text, _forward_graphs, _graphable, _out_grads, _trainable
+from .transformer import (Block, Packed, T5LayerNorm, _chain_train, _check_ids, _decode_text, _forward_graphs, _graphable, _out_grads, _trainable,
+                          block_forward, block_train, embed_tokens, norm_train)
 
 logger = logging.getLogger(__name__)
 
@@ -69,57 +72,6 @@ def relative_buckets(length: int, num_buckets: int, max_distance: int) -> Tensor
     return (rel > 0).to(torch.int64) * half + torch.where(dist < exact, dist, spread)
 
 
-def _bf16_rows(mats) -> Tensor:
-    """fp32 matrices [n_i, K] stacked by rows as one bf16 matrix (the cast is the kernels' own: round to nearest even)"""
-    stacked = mats[0].detach() if len(mats) == 1 else torch.cat([m.detach() for m in mats], dim=0)
-    return ops.cast_bf16(stacked.float().contiguous())
-
-
-class _Stacked:
-    """bf16 copy of one or more bias-free projections stacked by rows, rebuilt only when one of them changes (the only bf16 copy of these
-    weights: the single matrices get no shadow of their own)"""
-
-    def __init__(self, *layers: nn.Linear):
-        self.layers, self.stamp, self.weight = layers, None, None
-
-    def __call__(self) -> Tensor:
-        stamp = tuple(ops._param_stamp(l.weight) for l in self.layers)
-        if self.weight is None or self.stamp != stamp:
-            self.weight, self.stamp = _bf16_rows([l.weight for l in self.layers]), stamp
-        return self.weight
-
-
-def _stacked_train(h: Tensor, stacked: _Stacked):
-    """(h @ stacked^T, bwd(dy) -> dh) for the projections `stacked` holds by rows: ONE GEMM on the frozen forward's stacked bf16 matrix (so
-    the same bits), the input gradient through the same matrix, and each projection's weight gradient from its column slice of dy, written
-    to its own .grad in the parameter's engine mode"""
-    w = stacked()
-    y = ops.gemm_nt(h, w)
-
-    def bwd(dy: Tensor) -> Tensor:
-        def wgrads():
-            off = 0
-            for lin in stacked.layers:
-                n = lin.weight.shape[0]
-                ops.gemm_tn_f32(dy[:, off:off + n], h, ops.g2d(lin.weight), ops.wgrad_mode(lin.weight))
-                off += n
-
-        ops.on_wgrad_stream(wgrads, dy, h, owner=stacked.layers[0].weight)
-        return ops.gemm_nn(dy, w)
-
-    return y, bwd
-
-
-class T5LayerNorm(nn.Module):
-    def __init__(self, width: int, eps: float):
-        super().__init__()
-        self.weight = nn.Parameter(torch.ones(width))
-        self.variance_epsilon = eps
-
-    def forward(self, x: Tensor) -> Tensor:
-        return ops.rmsnorm(x, self.weight, self.variance_epsilon)
-
-
 class _SelfAttention(nn.Module):
     def __init__(self, d_model: int, heads: int, d_kv: int, num_buckets: Optional[int]):
         super().__init__()
@@ -128,7 +80,6 @@ class _SelfAttention(nn.Module):
         self.o = nn.Linear(inner, d_model, bias=False)
         if num_buckets is not None:
             self.relative_attention_bias = nn.Embedding(num_buckets, heads)
-        self.__dict__["_qkv"], self.__dict__["_o"] = _Stacked(self.q, self.k, self.v), _Stacked(self.o)
 
 
 class _Dense(nn.Module):
@@ -136,12 +87,9 @@ class _Dense(nn.Module):
         super().__init__()
         if gated:
             self.wi_0, self.wi_1 = nn.Linear(d_model, d_ff, bias=False), nn.Linear(d_model, d_ff, bias=False)
-            inputs = (self.wi_0, self.wi_1)
         else:
             self.wi = nn.Linear(d_model, d_ff, bias=False)
-            inputs = (self.wi,)
         self.wo = nn.Linear(d_ff, d_model, bias=False)
-        self.__dict__["_wi"], self.__dict__["_wo"] = _Stacked(*inputs), _Stacked(self.wo)
 
 
 class _AttentionLayer(nn.Module):
@@ -162,6 +110,10 @@ class _Block(nn.Module):
     def __init__(self, d_model: int, heads: int, d_kv: int, d_ff: int, gated: bool, num_buckets: Optional[int], eps: float):
         super().__init__()
         self.layer = nn.ModuleList([_AttentionLayer(d_model, heads, d_kv, num_buckets, eps), _DenseLayer(d_model, d_ff, gated, eps)])
+        att, ff = self.layer
+        sa, dense = att.SelfAttention, ff.DenseReluDense
+        wi = (dense.wi_0, dense.wi_1) if gated else (dense.wi,)       # [wi_0; wi_1] as ONE stacked projection
+        self.__dict__["spec"] = Block(att.layer_norm, Packed(sa.q, sa.k, sa.v), heads * d_kv, sa.o, ff.layer_norm, Packed(*wi), dense.wo)
 
 
 class T5EncoderTower(nn.Module):
@@ -215,40 +167,11 @@ class T5EncoderTower(nn.Module):
     def _forward_ids(self, ids: Tensor) -> dict:
         B, L = ids.shape
         rel = self.rel_table(L)
-        table = self.shared.weight
-        x = ops.cast_bf16(table[ids].reshape(-1, table.shape[1]).float())      # T5 neither scales the embeddings nor adds positions
-        inner = self.heads * self.d_kv
+        x = embed_tokens(ids, self.shared.weight)      # T5 neither scales the embeddings nor adds positions
+        attend, act = (lambda q, k, v: ops.attention_relbias_fwd(q, k, v, B, self.heads, self.d_kv, rel, scale=1.0)), (lambda u: ops.gated_act(u, self.act))
         for block in self.encoder.block:
-            att, ff = block.layer[0], block.layer[1]
-            sa, dense = att.SelfAttention, ff.DenseReluDense
-            fused = ops.gemm_nt(att.layer_norm(x), sa._qkv())
-            attended = ops.attention_relbias_fwd(fused[:, :inner], fused[:, inner:2 * inner], fused[:, 2 * inner:], B, self.heads, self.d_kv, rel, scale=1.0)
-            x = ops.gemm_nt(attended, sa._o(), residual=x)
-            hidden = ops.gated_act(ops.gemm_nt(ff.layer_norm(x), dense._wi()), self.act)
-            x = ops.gemm_nt(hidden, dense._wo(), residual=x)
+            x = block_forward(x, block.spec, attend, act)
         return {"last_hidden_state": self.encoder.final_layer_norm(x).float().reshape(B, L, -1)}
-
-    def _block_train(self, x: Tensor, block: _Block, B: int, rel: Tensor, d_rel: Tensor):
-        """one block of _forward_ids with its backward: (x', bwd(dx') -> dx); the attention's backward adds into d_rel"""
-        att, ff = block.layer[0], block.layer[1]
-        sa, dense = att.SelfAttention, ff.DenseReluDense
-        inner = self.heads * self.d_kv
-        h1, b_ln1 = ops.rmsnorm_fwd(x, att.layer_norm.weight, att.layer_norm.variance_epsilon)
-        fused, b_qkv = _stacked_train(h1, sa._qkv)
-        attended, b_att = ops.attention_relbias_train(fused[:, :inner], fused[:, inner:2 * inner], fused[:, 2 * inner:], B, self.heads, self.d_kv, rel, 1.0, d_rel)
-        x1, b_o = ops.linear_fwd(attended, sa.o.weight, None, residual=x)
-        h2, b_ln2 = ops.rmsnorm_fwd(x1, ff.layer_norm.weight, ff.layer_norm.variance_epsilon)
-        u, b_wi = _stacked_train(h2, dense._wi)
-        hidden, b_act = ops.gated_act_fwd(u, self.act)
-        x2, b_wo = ops.linear_fwd(hidden, dense.wo.weight, None, residual=x1)
-
-        def bwd(dx2: Tensor) -> Tensor:
-            dx1 = b_ln2(b_wi(b_act(b_wo(dx2))), dx_add=dx2)
-            dfused = torch.empty_like(fused)
-            b_att(b_o(dx1), dq=dfused[:, :inner], dk=dfused[:, inner:2 * inner], dv=dfused[:, 2 * inner:])
-            return b_ln1(b_qkv(dfused), dx_add=dx1)
-
-        return x2, bwd
 
     def train_outputs(self, input_ids: Tensor) -> Tensor:
         """The training forward, autograd-connected through nn.apply_module: fp32 [B, L, d_model] with forward()'s values (the same kernels
@@ -266,11 +189,10 @@ class T5EncoderTower(nn.Module):
             rel = self.rel_table(L)
             d_rel = torch.zeros_like(rel)      # every layer's backward adds into it
             table = self.shared.weight
-            x = ops.cast_bf16(table[ids].reshape(-1, table.shape[1]).float())
-            blocks = [lambda h, blk=blk: self._block_train(h, blk, B, rel, d_rel) for blk in self.encoder.block]
-            _, top, b_chain = _chain_train(x, blocks, set())
-            norm = self.encoder.final_layer_norm
-            y, b_final = ops.rmsnorm_fwd(top, norm.weight, norm.variance_epsilon)
+            x = embed_tokens(ids, table)
+            attend, act = (lambda q, k, v: ops.attention_relbias_train(q, k, v, B, self.heads, self.d_kv, rel, 1.0, d_rel)), (lambda u: ops.gated_act_fwd(u, self.act))
+            _, top, b_chain = _chain_train(x, [lambda h, blk=blk: block_train(h, blk.spec, attend, act) for blk in self.encoder.block], set())
+            y, b_final = norm_train(top, self.encoder.final_layer_norm)
 
             def bwd(gout):
                 dx = b_chain({}, b_final(_out_grads([gout], 1)[0]))

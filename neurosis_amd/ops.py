@@ -1303,6 +1303,36 @@ def cat_fwd(a: Img, b: Img):
 # ------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------
+def _attn_desc(q: Tensor, k: Tensor, v: Tensor, o: Tensor, B: int, heads: int, dim_head: int, scale: float, causal: bool) -> NkAttnDesc:
+    """the kernels' problem record for q / o [B*Lq, H*D], k / v [B*Lk, H*D] token matrices (the gradient side: _attn_grads)"""
+    d = NkAttnDesc()
+    Lq, Lk = q.shape[0] // B, k.shape[0] // B
+    d.B, d.H, d.Lq, d.Lk, d.D = B, heads, Lq, Lk, dim_head
+    d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
+    d.bq, d.bk, d.bv, d.bo = Lq * q.stride(0), Lk * k.stride(0), Lk * v.stride(0), Lq * o.stride(0)
+    d.scale = float(scale)
+    d.causal = int(causal)
+    return d
+
+
+def _attn_grads(d: NkAttnDesc, who: str, do: Tensor, dq: Optional[Tensor], dk: Optional[Tensor], dv: Optional[Tensor]):
+    """The gradient side of `d`: (dq, dk, dv), each allocated dense where not given (column slices of one buffer allowed where given) and
+    held to its shape like do, with their strides written into d."""
+    HD = d.H * d.D
+    grads = []
+    for n, t, L in (("do", do, d.Lq), ("dq", dq, d.Lq), ("dk", dk, d.Lk), ("dv", dv, d.Lk)):
+        if t is None:
+            t = torch.empty(d.B * L, HD, dtype=BF16, device=do.device)
+        _check2d(t, n)
+        if t.shape != (d.B * L, HD):
+            raise ValueError(f"{who}: {n} must be [{d.B * L}, {HD}], got {tuple(t.shape)}")
+        grads.append(t)
+    do, dq, dk, dv = grads
+    d.sdq, d.sdk, d.sdv, d.sdo = dq.stride(0), dk.stride(0), dv.stride(0), do.stride(0)
+    d.bdq, d.bdk, d.bdv, d.bdo = d.Lq * dq.stride(0), d.Lk * dk.stride(0), d.Lk * dv.stride(0), d.Lq * do.stride(0)
+    return dq, dk, dv
+
+
 def attention_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head: int, causal: bool = False, need_lse: bool = True,
                   return_lse: bool = False):
     """softmax(q k^T / sqrt(d)) v.  q [B*Lq, H*D], k/v [B*Lk, H*D] token matrices (column slices allowed).
@@ -1310,30 +1340,19 @@ def attention_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, dim_head:
     dim_head = 512 (the VAE mid block): csrc/attn512.h forward (need_lse=False skips the log-sum-exp output: inference), csrc/attn512_bwd.h backward."""
     for n, t in (("q", q), ("k", k), ("v", v)):
         _check2d(t, n)
-    Lq, Lk = q.shape[0] // B, k.shape[0] // B
-    HD = heads * dim_head
-    o = torch.empty(B * Lq, HD, dtype=BF16, device=q.device)
+    Lq = q.shape[0] // B
+    o = torch.empty(B * Lq, heads * dim_head, dtype=BF16, device=q.device)
     lse = torch.empty(B, heads, Lq, dtype=torch.float32, device=q.device) if (need_lse or dim_head != 512) else None
-    d = NkAttnDesc()
-    d.B, d.H, d.Lq, d.Lk, d.D = B, heads, Lq, Lk, dim_head
-    d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
-    d.bq, d.bk, d.bv, d.bo = Lq * q.stride(0), Lk * k.stride(0), Lk * v.stride(0), Lq * o.stride(0)
-    d.scale = float(dim_head) ** -0.5
-    d.causal = int(causal)
+    d = _attn_desc(q, k, v, o, B, heads, dim_head, float(dim_head) ** -0.5, causal)
     call("nk_attention_fwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr() if lse is not None else None,
          _stream())
 
     def bwd(do: Tensor, dq: Optional[Tensor] = None, dk: Optional[Tensor] = None, dv: Optional[Tensor] = None):
-        _check2d(do, "do")
         if dim_head > 160 and dim_head != 512:
             raise NotImplementedError("attention backward: head dim <= 160, or 512 (csrc/attn512_bwd.h)")
         if lse is None:
             raise ValueError("attention backward needs the forward's log-sum-exp: call attention_fwd(..., need_lse=True)")
-        dq = torch.empty(B * Lq, HD, dtype=BF16, device=do.device) if dq is None else dq
-        dk = torch.empty(B * Lk, HD, dtype=BF16, device=do.device) if dk is None else dk
-        dv = torch.empty(B * Lk, HD, dtype=BF16, device=do.device) if dv is None else dv
-        d.sdq, d.sdk, d.sdv, d.sdo = dq.stride(0), dk.stride(0), dv.stride(0), do.stride(0)
-        d.bdq, d.bdk, d.bdv, d.bdo = Lq * dq.stride(0), Lk * dk.stride(0), Lk * dv.stride(0), Lq * do.stride(0)
+        dq, dk, dv = _attn_grads(d, "attention_fwd bwd", do, dq, dk, dv)
         delta = _ws(query("nk_attention_bwd_ws_floats", C.byref(d)), do.device)
         call("nk_attention_bwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(),
              dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), _stream())
@@ -1361,12 +1380,7 @@ def attention_relbias_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, d
     if rel.dtype != torch.float32 or tuple(rel.shape) != (heads, 2 * L - 1) or not rel.is_contiguous() or rel.device != q.device:
         raise ValueError(f"attention_relbias_fwd: rel must be a dense fp32 [{heads}, {2 * L - 1}] tensor on {q.device}, got {rel.dtype} {tuple(rel.shape)}")
     o = torch.empty(B * L, heads * dim_head, dtype=BF16, device=q.device)
-    d = NkAttnDesc()
-    d.B, d.H, d.Lq, d.Lk, d.D = B, heads, L, L, dim_head
-    d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
-    d.bq, d.bk, d.bv, d.bo = L * q.stride(0), L * k.stride(0), L * v.stride(0), L * o.stride(0)
-    d.scale = float(scale)
-    d.causal = 0
+    d = _attn_desc(q, k, v, o, B, heads, dim_head, scale, False)
     call("nk_attention_relbias_fwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), rel.data_ptr(), _stream())
     return o
 
@@ -1379,7 +1393,6 @@ def attention_relbias_train(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int,
     for n, t in (("q", q), ("k", k), ("v", v)):
         _check2d(t, n)
     L = q.shape[0] // B
-    HD = heads * dim_head
     if k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
         raise ValueError("attention_relbias_train: self-attention (q, k and v over the same tokens)")
     if L > ATTN_RELBIAS_MAX_L:
@@ -1387,27 +1400,13 @@ def attention_relbias_train(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int,
     for n, t in (("rel", rel), ("d_rel", d_rel)):
         if t.dtype != torch.float32 or tuple(t.shape) != (heads, 2 * L - 1) or not t.is_contiguous() or t.device != q.device:
             raise ValueError(f"attention_relbias_train: {n} must be a dense fp32 [{heads}, {2 * L - 1}] tensor on {q.device}, got {t.dtype} {tuple(t.shape)}")
-    o = torch.empty(B * L, HD, dtype=BF16, device=q.device)
+    o = torch.empty(B * L, heads * dim_head, dtype=BF16, device=q.device)
     lse = torch.empty(B, heads, L, dtype=torch.float32, device=q.device)
-    d = NkAttnDesc()
-    d.B, d.H, d.Lq, d.Lk, d.D = B, heads, L, L, dim_head
-    d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
-    d.bq, d.bk, d.bv, d.bo = L * q.stride(0), L * k.stride(0), L * v.stride(0), L * o.stride(0)
-    d.scale = float(scale)
-    d.causal = 0
+    d = _attn_desc(q, k, v, o, B, heads, dim_head, scale, False)
     call("nk_attention_relbias_fwd_lse", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), rel.data_ptr(), _stream())
 
     def bwd(do: Tensor, dq: Optional[Tensor] = None, dk: Optional[Tensor] = None, dv: Optional[Tensor] = None, accumulate: bool = True):
-        _check2d(do, "do")
-        dq = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dq is None else dq
-        dk = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dk is None else dk
-        dv = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dv is None else dv
-        for n, t in (("do", do), ("dq", dq), ("dk", dk), ("dv", dv)):
-            _check2d(t, n)
-            if t.shape != (B * L, HD):
-                raise ValueError(f"attention_relbias_train bwd: {n} must be [{B * L}, {HD}], got {tuple(t.shape)}")
-        d.sdq, d.sdk, d.sdv, d.sdo = dq.stride(0), dk.stride(0), dv.stride(0), do.stride(0)
-        d.bdq, d.bdk, d.bdv, d.bdo = L * dq.stride(0), L * dk.stride(0), L * dv.stride(0), L * do.stride(0)
+        dq, dk, dv = _attn_grads(d, "attention_relbias_train bwd", do, dq, dk, dv)
         ws = _ws(query("nk_attention_relbias_bwd_ws_floats", C.byref(d)), do.device)
         call("nk_attention_relbias_bwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(),
              dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), rel.data_ptr(), d_rel.data_ptr(), ws.data_ptr(), int(accumulate), _stream())
@@ -1438,25 +1437,10 @@ def attention_causal_fwd(q: Tensor, k: Tensor, v: Tensor, B: int, heads: int, di
     if dim_head != 64 or L > 96 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
         raise NotImplementedError(f"attention_causal_fwd: the backward takes head dim 64 and at most 96 tokens (self-attention), got D = {dim_head}, L = {L}")
     o, _, lse = attention_fwd(q, k, v, B, heads, dim_head, causal=True, return_lse=True)
-    HD = heads * dim_head
 
     def bwd(do: Tensor, dq: Optional[Tensor] = None, dk: Optional[Tensor] = None, dv: Optional[Tensor] = None):
-        _check2d(do, "do")
-        dq = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dq is None else dq
-        dk = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dk is None else dk
-        dv = torch.empty(B * L, HD, dtype=BF16, device=do.device) if dv is None else dv
-        for n, t in (("dq", dq), ("dk", dk), ("dv", dv)):
-            _check2d(t, n)
-            if t.shape != (B * L, HD):
-                raise ValueError(f"attention_causal_fwd bwd: {n} must be [{B * L}, {HD}], got {tuple(t.shape)}")
-        d = NkAttnDesc()
-        d.B, d.H, d.Lq, d.Lk, d.D = B, heads, L, L, dim_head
-        d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
-        d.bq, d.bk, d.bv, d.bo = L * q.stride(0), L * k.stride(0), L * v.stride(0), L * o.stride(0)
-        d.sdq, d.sdk, d.sdv, d.sdo = dq.stride(0), dk.stride(0), dv.stride(0), do.stride(0)
-        d.bdq, d.bdk, d.bdv, d.bdo = L * dq.stride(0), L * dk.stride(0), L * dv.stride(0), L * do.stride(0)
-        d.scale = float(dim_head) ** -0.5
-        d.causal = 1
+        d = _attn_desc(q, k, v, o, B, heads, dim_head, float(dim_head) ** -0.5, True)
+        dq, dk, dv = _attn_grads(d, "attention_causal_fwd bwd", do, dq, dk, dv)
         call("nk_attention_bwd_causal", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(),
              dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _stream())
         return dq, dk, dv
@@ -1989,21 +1973,15 @@ def attention_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, lse: Tensor, do: T
                   dv: Tensor) -> None:
     """The backward of the non-causal attention_fwd from its saved tensors (or the row slices of them that belong to B whole samples):
     q / o / do / dq [B*Lq, H*D], k / v / dk / dv [B*Lk, H*D] token matrices (column slices allowed), lse fp32 [B, heads, Lq] dense."""
-    for n, t in (("q", q), ("k", k), ("v", v), ("o", o), ("do", do), ("dq", dq), ("dk", dk), ("dv", dv)):
+    for n, t in (("q", q), ("k", k), ("v", v), ("o", o)):
         _check2d(t, n)
     if dim_head > 160:
         raise NotImplementedError("attention_bwd: head dim <= 160")
-    Lq, Lk = q.shape[0] // B, k.shape[0] // B
+    Lq = q.shape[0] // B
     if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * heads * Lq:
         raise ValueError(f"attention_bwd: lse must be a dense fp32 [{B}, {heads}, {Lq}] tensor")
-    d = NkAttnDesc()
-    d.B, d.H, d.Lq, d.Lk, d.D = B, heads, Lq, Lk, dim_head
-    d.sq, d.sk, d.sv, d.so = q.stride(0), k.stride(0), v.stride(0), o.stride(0)
-    d.bq, d.bk, d.bv, d.bo = Lq * q.stride(0), Lk * k.stride(0), Lk * v.stride(0), Lq * o.stride(0)
-    d.scale = float(dim_head) ** -0.5
-    d.causal = 0
-    d.sdq, d.sdk, d.sdv, d.sdo = dq.stride(0), dk.stride(0), dv.stride(0), do.stride(0)
-    d.bdq, d.bdk, d.bdv, d.bdo = Lq * dq.stride(0), Lk * dk.stride(0), Lk * dv.stride(0), Lq * do.stride(0)
+    d = _attn_desc(q, k, v, o, B, heads, dim_head, float(dim_head) ** -0.5, False)
+    _attn_grads(d, "attention_bwd", do, dq, dk, dv)
     delta = _ws(query("nk_attention_bwd_ws_floats", C.byref(d)), do.device)
     call("nk_attention_bwd", C.byref(d), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), do.data_ptr(),
          dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), _stream())
