@@ -428,6 +428,22 @@ int nk_gated_gelu_tanh_bwd(const void* dy, const void* u, void* du, long M, int 
 #define NK_EMBEDDING_BWD_MAX_TOKENS 8192
 int nk_embedding_bwd(const long long* ids, const void* dx, long ldx, float* dtable, float* dpos, int B, int L, int V, int P, int C,
                      int accumulate, void* stream);
+/* Label embeddings of a class-conditional UNet (modules/diffusion/openaimodel.py:574-590: num_classes an int or "continuous") and
+ * ClassEmbedder (modules/encoders/classed.py:9-32).
+ * label_rows_fwd: out[b][:] = table[ids[b]][:] (+ add[b][:]); table fp32 [V][D] dense, ids int64 [B], add bf16 [B][D] dense or NULL, out
+ *                 [B][D] dense, fp32 (out_is_f32) or bf16 (fp32 sum, one round-to-nearest-even).  An id outside [0, V) is never used as an
+ *                 address: its output row is NaN.  D % 8 == 0.
+ * label_rows_bwd: dtable[v][:] = sum of d[b][:] over the b with ids[b] = v, in ascending b, fp32; d [B][D] bf16 or fp32 (d_is_f32), row stride
+ *                 ldd.  nk_embedding_bwd's kernel with L = 1 and no position table: the same accumulate modes (0: the whole table is
+ *                 overwritten, rows no sample hit are zero; 1: the new sum is formed first and added once; 2: written, the caller's
+ *                 table is zero already), the same bits on every run, the same cap B <= NK_EMBEDDING_BWD_MAX_TOKENS.
+ * linear1_fwd:    nn.Linear(1, D): out[b][j] = bf16(y[b] w[j] + bias[j] (+ add[b][j])); y fp32 [B], w / bias fp32 [D], add / out bf16 [B][D].
+ * linear1_bwd:    dw[j] = sum_b y[b] d[b][j], db[j] = sum_b d[b][j] in ascending b, fp32 (accumulate 0 / 2: written, 1: added to);
+ *                 dy[b] = sum_j d[b][j] w[j] (fixed order) unless dy is NULL.  d bf16 [B][D] dense. */
+int nk_label_rows_fwd(const float* table, const long long* ids, const void* add, void* out, int out_is_f32, int B, int V, int D, void* stream);
+int nk_label_rows_bwd(const long long* ids, const void* d, long ldd, int d_is_f32, float* dtable, int B, int V, int D, int accumulate, void* stream);
+int nk_linear1_fwd(const float* y, const float* w, const float* bias, const void* add, void* out, int B, int D, void* stream);
+int nk_linear1_bwd(const void* d, const float* y, const float* w, float* dw, float* db, float* dy, int B, int D, int accumulate, void* stream);
 /* backward of a row gather sel[b] = x[b * L + idx[b]]: dx [B * L][C] bf16 (dense) = 0 except those rows = dsel[b] (row stride ldsel) */
 int nk_gather_rows_bwd(const void* dsel, long ldsel, const long long* idx, void* dx, int B, int L, int C, void* stream);
 /* dw [K][N] fp32 (row stride lddw) (+)= x^T dy over M <= 256 rows (x [M][K], dy [M][N] bf16): weight gradients the tile engine does not take

@@ -233,7 +233,8 @@ extern "C" int nk_gated_gelu_tanh_bwd(const void* dy, const void* u, void* du, l
 // order and writes (or adds) table row v; later tokens with the same id do nothing.  Workgroup N + l sums position l over the batch, b = 0 .. B-1.
 // Fixed-order sums, no atomics: the result does not depend on scheduling (a padded prompt repeats one id some 60 times).  Each lane owns
 // 8 columns.  The ids are wave-uniform loads; the O(N^2) id scan is nothing at N = 308.
-__global__ void embedding_bwd_kernel(const long long* __restrict__ ids, const bf16_t* __restrict__ dx, long ldx, float* __restrict__ dtab,
+template <class T>
+__global__ void embedding_bwd_kernel(const long long* __restrict__ ids, const T* __restrict__ dx, long ldx, float* __restrict__ dtab,
                                      float* __restrict__ dpos, int N, int L, int V, int C, int accumulate) {
   const int w = blockIdx.x;
   const int c8 = C >> 3;
@@ -248,7 +249,7 @@ __global__ void embedding_bwd_kernel(const long long* __restrict__ ids, const bf
       for (int t = w; t < N; ++t) {
         if (ids[t] != v) continue;
         float f[8];
-        unpack8(*(const uint4_t*)(dx + (long)t * ldx + ch * 8), f);
+        ew_load(dx + (long)t * ldx + ch * 8, f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] += f[e];
       }
@@ -264,7 +265,7 @@ __global__ void embedding_bwd_kernel(const long long* __restrict__ ids, const bf
       float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       for (int b = 0; b < B; ++b) {
         float f[8];
-        unpack8(*(const uint4_t*)(dx + ((long)b * L + l) * ldx + ch * 8), f);
+        ew_load(dx + ((long)b * L + l) * ldx + ch * 8, f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] += f[e];
       }
@@ -276,6 +277,17 @@ __global__ void embedding_bwd_kernel(const long long* __restrict__ ids, const bf
     }
   }
 }
+// the clearing pass and the launch, for the text towers' entry and for the label embedding's (T = float: fp32 gradient rows)
+template <class T>
+static int embedding_bwd_launch(const char* name, const long long* ids, const T* dx, long ldx, float* dtable, float* dpos, int B, int L, int V, int P, int C,
+                                int accumulate, hipStream_t stream) {
+  if (accumulate == 0) {     // overwrite: rows no token (no position) hit are zero; (2: the caller's buffers are zero already)
+    if (hipMemsetAsync(dtable, 0, (size_t)V * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
+    if (dpos && hipMemsetAsync(dpos, 0, (size_t)P * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
+  }
+  hipLaunchKernelGGL(embedding_bwd_kernel<T>, dim3(B * L + (dpos ? L : 0)), dim3(128), 0, stream, ids, dx, ldx, dtable, dpos, B * L, L, V, C, accumulate == 1);
+  return nk_check_launch(name);
+}
 extern "C" int nk_embedding_bwd(const long long* ids, const void* dx, long ldx, float* dtable, float* dpos, int B, int L, int V, int P, int C,
                                 int accumulate, void* stream_) {
   // (dpos == NULL with P == 0: an embedding without a position table -- the T5 encoders -- so no position workgroups are launched)
@@ -283,14 +295,103 @@ extern "C" int nk_embedding_bwd(const long long* ids, const void* dx, long ldx, 
   NK_CHECK_ARG(dpos ? L <= P : P == 0);
   NK_CHECK_ARG(nk_aligned16(dx) && nk_aligned16(dtable) && nk_aligned16(dpos));
   NK_CHECK_ARG((long)B * L <= NK_EMBEDDING_BWD_MAX_TOKENS && accumulate >= 0 && accumulate <= 2);     // (the id scans are quadratic in B * L)
-  hipStream_t stream = (hipStream_t)stream_;
-  if (accumulate == 0) {     // overwrite: rows no token (no position) hit are zero; (2: the caller's buffers are zero already)
-    if (hipMemsetAsync(dtable, 0, (size_t)V * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
-    if (dpos && hipMemsetAsync(dpos, 0, (size_t)P * C * sizeof(float), stream) != hipSuccess) return nk_check_launch("embedding_bwd memset");
+  return embedding_bwd_launch("embedding_bwd", ids, (const bf16_t*)dx, ldx, dtable, dpos, B, L, V, P, C, accumulate, (hipStream_t)stream_);
+}
+
+// ---- label embeddings of a class-conditional UNet (openaimodel.py:574-590) and ClassEmbedder (encoders/classed.py) ------------------------------
+// lookup: out[b, :] = table[ids[b], :] (+ add[b, :]), fp32 arithmetic, one rounding when out is bf16.  An id outside [0, V) is never an
+// address: its row comes out NaN (nn.Embedding raises; a kernel cannot, and a clamped id would train the wrong class in silence)
+template <bool F32OUT>
+struct LabelRows {
+  const float* table; const long long* ids; const bf16_t* add; void* out; int V, D;
+  __device__ void operator()(long i, long row, int ch) const {
+    const long long v = ids[row];
+    float f[8];
+    if (v < 0 || v >= V) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] = __builtin_nanf("");
+    } else {
+      ew_load(table + v * (long)D + ch * 8, f);
+      if (add) {
+        float a[8];
+        ew_load(add + row * D + ch * 8, a);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] += a[e];
+      }
+    }
+    if constexpr (F32OUT) ew_store((float*)out + i * 8, f);
+    else ew_store((bf16_t*)out + i * 8, f);
   }
-  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(B * L + (dpos ? L : 0)), dim3(128), 0, stream, ids, (const bf16_t*)dx, ldx, dtable, dpos, B * L, L, V, C,
-                     accumulate == 1);
-  return nk_check_launch("embedding_bwd");
+};
+extern "C" int nk_label_rows_fwd(const float* table, const long long* ids, const void* add, void* out, int out_is_f32, int B, int V, int D, void* stream) {
+  NK_CHECK_ARG(table && ids && out && B > 0 && V > 0 && D > 0 && (D & 7) == 0);
+  NK_CHECK_ARG(nk_aligned16(table) && nk_aligned16(add) && nk_aligned16(out));     // 16-byte accesses
+  if (out_is_f32) return nk_ew_rows("label_rows_fwd", stream, B, D >> 3, LabelRows<true>{table, ids, (const bf16_t*)add, out, V, D});
+  return nk_ew_rows("label_rows_fwd", stream, B, D >> 3, LabelRows<false>{table, ids, (const bf16_t*)add, out, V, D});
+}
+// gradient: dtable[v, :] = sum of d[b, :] over the samples with ids[b] = v in ascending b -- nk_embedding_bwd's kernel with one token per
+// sample and no position table, on bf16 or fp32 rows
+extern "C" int nk_label_rows_bwd(const long long* ids, const void* d, long ldd, int d_is_f32, float* dtable, int B, int V, int D, int accumulate,
+                                 void* stream) {
+  NK_CHECK_ARG(ids && d && dtable && B > 0 && V > 0 && D > 0 && (D & 7) == 0 && (ldd & 7) == 0 && ldd >= D);
+  NK_CHECK_ARG(nk_aligned16(d) && nk_aligned16(dtable));
+  NK_CHECK_ARG(B <= NK_EMBEDDING_BWD_MAX_TOKENS && accumulate >= 0 && accumulate <= 2);     // (the id scans are quadratic in B)
+  if (d_is_f32) return embedding_bwd_launch("label_rows_bwd", ids, (const float*)d, ldd, dtable, nullptr, B, 1, V, 0, D, accumulate, (hipStream_t)stream);
+  return embedding_bwd_launch("label_rows_bwd", ids, (const bf16_t*)d, ldd, dtable, nullptr, B, 1, V, 0, D, accumulate, (hipStream_t)stream);
+}
+
+// nn.Linear(1, D), the "continuous" label embedding: K = 1 is an outer product, not a shape for the matrix pipe.
+// forward: out[b, j] = bf16(y[b] w[j] + bias[j] (+ add[b, j]))
+struct Linear1Fwd {
+  const float *y, *w, *bias; const bf16_t* add; bf16_t* out; int D;
+  __device__ void operator()(long i, long row, int ch) const {
+    const float yb = y[row];
+    float f[8], b[8];
+    ew_load(w + ch * 8, f);
+    ew_load(bias + ch * 8, b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = yb * f[e] + b[e];
+    if (add) {
+      ew_load(add + i * 8, b);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] += b[e];
+    }
+    ew_store(out + i * 8, f);
+  }
+};
+extern "C" int nk_linear1_fwd(const float* y, const float* w, const float* bias, const void* add, void* out, int B, int D, void* stream) {
+  NK_CHECK_ARG(y && w && bias && out && B > 0 && D > 0 && (D & 7) == 0);
+  NK_CHECK_ARG(nk_aligned16(w) && nk_aligned16(bias) && nk_aligned16(add) && nk_aligned16(out));     // 16-byte accesses
+  return nk_ew_rows("linear1_fwd", stream, B, D >> 3, Linear1Fwd{y, w, bias, (const bf16_t*)add, (bf16_t*)out, D});
+}
+// backward: dw[j] = sum_b y[b] d[b, j] and db[j] = sum_b d[b, j], one thread per column adding b = 0 .. B - 1 in order (nk_reduce_rows with one
+// row group); dy[b] = sum_j d[b, j] w[j], one thread column per sample, 16 row groups over j in the reducer's order
+__global__ void __launch_bounds__(256) linear1_bwd_params_kernel(const bf16_t* __restrict__ d, const float* __restrict__ y, float* __restrict__ dw,
+                                                                 float* __restrict__ db, int B, int D, int accumulate) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  nk_reduce_rows<1, 256, 2, 0, 4>(
+      j < D, B,
+      [&](int b, float* acc) {
+        const float g = bf2f(d[(long)b * D + j]);
+        acc[0] += y[b] * g;
+        acc[1] += g;
+      },
+      [&](const float* acc) {
+        dw[j] = accumulate ? dw[j] + acc[0] : acc[0];
+        db[j] = accumulate ? db[j] + acc[1] : acc[1];
+      });
+}
+__global__ void __launch_bounds__(256) linear1_bwd_dy_kernel(const bf16_t* __restrict__ d, const float* __restrict__ w, float* __restrict__ dy, int B, int D) {
+  const int b = blockIdx.x * 16 + threadIdx.x % 16;
+  nk_reduce_rows<16, 16, 1, 1, 4>(
+      b < B, D, [&](int j, float* acc) { acc[0] += bf2f(d[(long)b * D + j]) * w[j]; }, [&](const float* acc) { dy[b] = acc[0]; });
+}
+extern "C" int nk_linear1_bwd(const void* d, const float* y, const float* w, float* dw, float* db, float* dy, int B, int D, int accumulate, void* stream_) {
+  NK_CHECK_ARG(d && y && w && dw && db && B > 0 && D > 0 && (D & 7) == 0 && accumulate >= 0 && accumulate <= 2);
+  hipStream_t stream = (hipStream_t)stream_;
+  hipLaunchKernelGGL(linear1_bwd_params_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, (const bf16_t*)d, y, dw, db, B, D, accumulate == 1);
+  if (dy) hipLaunchKernelGGL(linear1_bwd_dy_kernel, dim3((B + 15) / 16), dim3(256), 0, stream, (const bf16_t*)d, w, dy, B, D);
+  return nk_check_launch("linear1_bwd");
 }
 
 // ---- backward of a row gather: dx[B * L][C] = 0 except row b * L + idx[b] = dsel[b] (idx read on the device; 0 <= idx[b] < L) ----

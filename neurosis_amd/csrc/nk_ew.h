@@ -19,6 +19,16 @@ static inline int nk_ew_grid(long items, int cap = NK_EW_CAP) {
 
 __device__ __forceinline__ void ew_load(const bf16_t* p, float* f) { unpack8(*(const uint4_t*)p, f); }
 __device__ __forceinline__ void ew_store(bf16_t* p, const float* f) { *(uint4_t*)p = pack8(f); }
+// the same chunk of 8 values in fp32 storage (32 B, 16-byte aligned): no conversion
+__device__ __forceinline__ void ew_load(const float* p, float* f) {
+  const float4_t lo = *(const float4_t*)p, hi = *(const float4_t*)(p + 4);
+  f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w;
+  f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
+}
+__device__ __forceinline__ void ew_store(float* p, const float* f) {
+  *(float4_t*)p = float4_t{f[0], f[1], f[2], f[3]};
+  *(float4_t*)(p + 4) = float4_t{f[4], f[5], f[6], f[7]};
+}
 
 // the grid-stride loop.  The block size is the launcher's constant, not blockDim.x: read in a device function, blockDim.x costs a vector
 // load and a wait at the head of every kernel (in a __global__ body the compiler folds it into a scalar kernarg load)

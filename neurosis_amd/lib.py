@@ -105,6 +105,10 @@ SIGNATURES: dict[str, list] = {
     "nk_act_bwd": [vp, vp, vp, i64, i32, vp],
     "nk_gated_gelu_tanh_bwd": [vp, vp, vp, i64, i32, vp],
     "nk_embedding_bwd": [vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "nk_label_rows_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "nk_label_rows_bwd": [vp, vp, i64, i32, vp, i32, i32, i32, i32, vp],
+    "nk_linear1_fwd": [vp, vp, vp, vp, vp, i32, i32, vp],
+    "nk_linear1_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "nk_gather_rows_bwd": [vp, i64, vp, vp, i32, i32, i32, vp],
     "nk_wgrad_few_rows": [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp],
     "nk_vq_search": [vp, i64, vp, vp, vp, i64, i32, i32, vp],

@@ -393,13 +393,27 @@ class UNetModel(nn.Module):
         time_embed_dim = model_channels * 4
         self.time_embed = nn.Sequential(nn.Linear(model_channels, time_embed_dim), nn.SiLU(), nn.Linear(time_embed_dim, time_embed_dim))
 
+        # the label embedding's kind (openaimodel.py:574-590): None, "sequential" (SDXL: an MLP over the vector conditioning), "int" (one
+        # learned row per class), "continuous" (a Linear over one scalar), "timestep" (the sinusoid of a scalar, then time_embed's MLP shape)
+        self.label_kind = None
         if self.num_classes is not None:
-            if self.num_classes == "sequential":
+            if isinstance(self.num_classes, int) and not isinstance(self.num_classes, bool):
+                self.label_kind = "int"
+                self.label_emb = nn.Embedding(num_classes, time_embed_dim)
+            elif self.num_classes == "continuous":
+                self.label_kind = "continuous"
+                self.label_emb = nn.Linear(1, time_embed_dim)
+            elif self.num_classes == "timestep":
+                self.label_kind = "timestep"
+                self.label_emb = nn.Sequential(Timestep(model_channels),
+                                               nn.Sequential(nn.Linear(model_channels, time_embed_dim), nn.SiLU(), nn.Linear(time_embed_dim, time_embed_dim)))
+            elif self.num_classes == "sequential":
+                self.label_kind = "sequential"
                 if adm_in_channels is None:
                     raise ValueError("UNetModel: num_classes='sequential' needs adm_in_channels (the width of the vector conditioning)")
                 self.label_emb = nn.Sequential(nn.Sequential(nn.Linear(adm_in_channels, time_embed_dim), nn.SiLU(), nn.Linear(time_embed_dim, time_embed_dim)))
             else:
-                raise NotImplementedError(f"num_classes={self.num_classes!r}: only 'sequential' (SDXL) and None (SD1.5) are on the path")
+                raise NotImplementedError(f"num_classes={self.num_classes!r}: an int, 'continuous', 'timestep', 'sequential' (SDXL) and None (SD1.5) are on the path")
 
         def make_st(ch, level_depth, disabled_sa):
             if num_head_channels == -1:
@@ -472,6 +486,46 @@ class UNetModel(nn.Module):
         o, b2 = linear_module_fwd(seq[2], s)
         return o, (lambda g: b0(b1(b2(g))))
 
+    def label_input(self, y: Optional[Tensor]) -> Optional[Tensor]:
+        """`y` (the "vector" conditioning) in the form `fwd` takes it for this network's label embedding, checked by name: "sequential" a bf16
+        token matrix [B, adm_in_channels]; an int num_classes int64 ids [B]; "continuous" fp32 [B, 1]; "timestep" fp32 [B].  A tensor already in
+        that form comes back as it is (no launch), so the chain calls this again on what its callers made."""
+        if y is None or self.label_kind is None:
+            return y
+        kind = self.label_kind
+        if kind == "sequential":
+            return as_tokens(y)
+        if kind == "int":
+            if y.dtype != torch.int64 or y.dim() != 1:
+                raise ValueError(f"UNetModel(num_classes={self.num_classes}): y must be int64 class ids of shape [B], got {tuple(y.shape)} {y.dtype}")
+            return y.contiguous()
+        if kind == "continuous":
+            if not y.is_floating_point() or y.dim() != 2 or y.shape[1] != 1:
+                raise ValueError(f"UNetModel(num_classes='continuous'): y must be a float tensor of shape [B, 1], got {tuple(y.shape)} {y.dtype}")
+        elif not y.is_floating_point() or y.dim() != 1:
+            raise ValueError(f"UNetModel(num_classes='timestep'): y must be a float tensor of shape [B], got {tuple(y.shape)} {y.dtype}")
+        return y.to(torch.float32).contiguous()
+
+    def _label_fwd(self, y: Tensor, emb: Tensor, need_dy: bool):
+        """emb + label_emb(y) with its backward: (bf16 [B, 4 * model_channels], bwd(demb) -> dy | None).  The int and continuous kinds add
+        time_embed's output inside their own kernel; ids have no gradient and the timestep kind's sinusoid is not differentiated."""
+        kind = self.label_kind
+        if kind == "int":
+            table = self.label_emb.weight
+
+            def b_rows(demb: Tensor):
+                ops.label_rows_bwd(y, demb, table)
+                return None
+
+            return ops.label_rows(table, y, add=emb, out_dtype=BF16), b_rows
+        if kind == "continuous":
+            return ops.linear1_fwd(y, self.label_emb.weight, self.label_emb.bias, add=emb, need_dy=need_dy)
+        if kind == "timestep":
+            lab, b_mlp = self._mlp_fwd(self.label_emb[1], ops.timestep_embedding(y, self.label_emb[0].dim), need_dx=False)
+        else:
+            lab, b_mlp = self._mlp_fwd(self.label_emb[0], y, need_dx=need_dy)
+        return ops.add(emb, lab), b_mlp
+
     def set_recompute(self, policy: Optional[str]) -> "UNetModel":
         """Selective activation recompute for every transformer block (BasicTransformerBlock.recompute): None keeps everything (default: 58 GB
         at SDXL batch 4 on a 288 GB part), "norms" rebuilds LayerNorm outputs and GEGLU products in backward instead of holding them.  The
@@ -516,6 +570,7 @@ class UNetModel(nn.Module):
         data-parallel exchange) is called between the backward's per-block graph segments, as the eager chain calls it."""
         from ...graphs import ChainGraphs, frozen_stamp, graphs_enabled
 
+        y = self.label_input(y)          # (checked and converted out here: the graph's input is the form the chain reads)
         if not x.t.is_cuda or not graphs_enabled():
             return self.fwd(x, timesteps, context, y, need_dctx, need_dy)
         if self._nk_graphs is None:
@@ -529,7 +584,8 @@ class UNetModel(nn.Module):
     def fwd(self, x: Img, timesteps: Tensor, context: Optional[Tensor], y: Optional[Tensor], need_dctx: bool = False, need_dy: bool = False):
         """x: Img with channels padded to a multiple of 8.  Returns (out Img (padded channels), bwd);
         bwd(dout tokens) -> dx tokens or None; with need_dctx or need_dy (a trained conditioner) -> (dx, dcontext | None, dy | None):
-        dcontext [B*Lc, Cc] the sum over every cross-attention of its K / V projections' input gradients, dy [B, adm] through label_emb."""
+        dcontext [B*Lc, Cc] the sum over every cross-attention of its K / V projections' input gradients, dy through label_emb ("sequential":
+        [B, adm]; "continuous": fp32 [B, 1]; class ids and the "timestep" kind's scalar have none).  y: see label_input."""
         hook_raw = self.grad_ready_hook
         need_dctx = bool(need_dctx) and context is not None
         need_dy = bool(need_dy) and y is not None and self.num_classes is not None
@@ -539,8 +595,7 @@ class UNetModel(nn.Module):
         emb, b_time = self._mlp_fwd(self.time_embed, t_emb, need_dx=False)
         b_label = None
         if self.num_classes is not None:
-            lab, b_label = self._mlp_fwd(self.label_emb[0], y, need_dx=need_dy)
-            emb = ops.add(emb, lab)
+            emb, b_label = self._label_fwd(self.label_input(y), emb, need_dy)
         if context is not None:
             self._project_context(context)
         dctx = [None]
@@ -625,11 +680,14 @@ class UNetModel(nn.Module):
         return out, bwd
 
     def forward(self, x: Tensor, timesteps: Optional[Tensor] = None, context: Optional[Tensor] = None, y: Optional[Tensor] = None, **kwargs) -> Tensor:
-        """openaimodel.py:803-840: x [N, C, H, W], timesteps [N], context [N, L, context_dim], y [N, adm_in_channels]."""
+        """openaimodel.py:803-840: x [N, C, H, W], timesteps [N], context [N, L, context_dim], y [N, adm_in_channels] ("sequential"), int64 class
+        ids [N] (an int num_classes), a float [N, 1] ("continuous") or a float [N] ("timestep")."""
         if (y is not None) != (self.num_classes is not None):
             raise ValueError(f"UNetModel.forward: this network has no label embedding (num_classes=None) but was given y of shape {tuple(y.shape)}")
         if y is not None:
             assert y.shape[0] == x.shape[0]
+            if self.label_kind != "sequential":
+                y = self.label_input(y)          # a wrong dtype or shape is refused by name before anything is launched
         N, Cin, H, W = x.shape
         ins = [x, timesteps, context, y]
 
@@ -641,7 +699,7 @@ class UNetModel(nn.Module):
                 img = Img(ops.nchw_to_tokens(x, cpad), N, H, W)
             need_dctx = context is not None and context.requires_grad
             need_dy = y is not None and y.requires_grad
-            out, bwd = self.fwd(img, timesteps, None if context is None else as_tokens(context), None if y is None else as_tokens(y), need_dctx, need_dy)
+            out, bwd = self.fwd(img, timesteps, None if context is None else as_tokens(context), self.label_input(y), need_dctx, need_dy)
             o = ops.tokens_to_nchw(out.t, N, self.out_channels, out.H, out.W, dtype=x.dtype if x.dtype in (torch.float32, BF16) else torch.float32)
 
             def bwd2(g):

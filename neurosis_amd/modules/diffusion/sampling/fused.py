@@ -124,7 +124,8 @@ class FusedDenoiser:
             value = cond.get(key)
             if value is None:
                 return None
-            return as_tokens(value if rep == 1 else torch.cat((uc[key], value), 0))
+            value = value if rep == 1 else torch.cat((uc[key], value), 0)
+            return unet.label_input(value) if key == "vector" else as_tokens(value)
 
         timesteps = c_noise if rep == 1 else torch.cat((c_noise, c_noise))
         out, _ = unet.fwd(Img(net_in, rep * B, H, W), timesteps, stacked("crossattn"), stacked("vector"))

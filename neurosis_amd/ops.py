@@ -972,6 +972,80 @@ def embedding_bwd(ids: Tensor, dx: Tensor, table: Tensor, positions: Optional[Te
          grad_flat(positions).data_ptr() if positions is not None else None, B, L, V, P, Cc, wgrad_mode(table), _stream())
 
 
+def _label_ids(ids: Tensor, op: str) -> Tensor:
+    if not ids.is_cuda:
+        raise NotImplementedError(f"{op}: ids is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    if ids.dim() != 1 or ids.dtype != torch.int64:
+        raise ValueError(f"{op}: ids must be an int64 [B] tensor, got {tuple(ids.shape)} {ids.dtype}")
+    return ids.contiguous()
+
+
+def label_rows(table: Tensor, ids: Tensor, add: Optional[Tensor] = None, out_dtype=torch.float32) -> Tensor:
+    """out[b] = table[ids[b]] (+ add[b]) (nk_label_rows_fwd): the label embedding of a class-conditional UNet and ClassEmbedder.  table fp32
+    [V, D] (the master itself: one rounding, at the end), ids int64 [B], add bf16 [B, D]; out [B, D] fp32 or bf16.  An id outside [0, V) gives
+    a NaN row: it is never an address and cannot pass unnoticed."""
+    ids = _label_ids(ids, "label_rows")
+    t = table.detach()
+    if not t.is_cuda:
+        raise NotImplementedError("label_rows: table is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or t.shape[1] % 8:
+        raise ValueError(f"label_rows: table must be a dense fp32 [V, D] matrix with D % 8 == 0, got {tuple(t.shape)} {t.dtype}")
+    if out_dtype not in (torch.float32, BF16):
+        raise ValueError(f"label_rows: out_dtype is torch.float32 or torch.bfloat16, got {out_dtype}")
+    V, D = t.shape
+    B = ids.shape[0]
+    if add is not None and (add.shape != (B, D) or add.dtype != BF16 or not add.is_contiguous() or not add.is_cuda):
+        raise ValueError(f"label_rows: add must be a dense bf16 [{B}, {D}] tensor, got {tuple(add.shape)} {add.dtype}")
+    out = torch.empty(B, D, dtype=out_dtype, device=t.device)
+    call("nk_label_rows_fwd", t.data_ptr(), ids.data_ptr(), _p(add), out.data_ptr(), int(out_dtype == torch.float32), B, V, D, _stream())
+    return out
+
+
+def label_rows_bwd(ids: Tensor, d: Tensor, table: Tensor) -> None:
+    """The gradient of label_rows written into table.grad (fp32) in the parameter's engine mode, as embedding_bwd does (whose kernel this is,
+    with one token per sample and no position table): the first micro-batch overwrites the whole table -- rows no sample hit come out zero --,
+    later ones add.  Each row is the fp32 sum of its samples' rows of d in ascending b: the same bits on every run.  d [B, D] bf16 or fp32."""
+    ids = _label_ids(ids, "label_rows_bwd")
+    if not d.is_cuda:
+        raise NotImplementedError("label_rows_bwd: d is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    B = ids.shape[0]
+    V, D = table.shape
+    if d.dim() != 2 or d.shape != (B, D) or d.dtype not in (torch.float32, BF16) or d.stride(1) != 1:
+        raise ValueError(f"label_rows_bwd: d must be a bf16 or fp32 [{B}, {D}] matrix with unit inner stride, got {tuple(d.shape)} {d.dtype}")
+    if B > EMBEDDING_BWD_MAX_TOKENS:
+        raise NotImplementedError(f"label_rows_bwd: at most {EMBEDDING_BWD_MAX_TOKENS} samples per call (the duplicate-id scans are quadratic), got {B}")
+    call("nk_label_rows_bwd", ids.data_ptr(), d.data_ptr(), d.stride(0), int(d.dtype == torch.float32), grad_flat(table).data_ptr(), B, V, D,
+         wgrad_mode(table), _stream())
+
+
+def linear1_fwd(y: Tensor, weight: Tensor, bias: Tensor, add: Optional[Tensor] = None, need_dy: bool = False):
+    """nn.Linear(1, D) on y fp32 [B, 1] (the "continuous" label embedding): out bf16 [B, D] = y weight^T + bias (+ add), fp32 arithmetic on the
+    fp32 masters, one rounding (nk_linear1_fwd; K = 1 is no shape for the MFMA GEMMs).  bwd(d) -> dy fp32 [B, 1] (None unless need_dy) and
+    writes weight.grad [D, 1] / bias.grad [D] in the parameters' engine mode: sums over b in ascending order."""
+    if not y.is_cuda:
+        raise NotImplementedError("linear1_fwd: y is a CPU tensor; the HIP kernels run on the GPU only, there is no CPU path")
+    D = weight.shape[0]
+    if y.dim() != 2 or y.shape[1] != 1 or y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError(f"linear1_fwd: y must be a dense fp32 [B, 1] tensor, got {tuple(y.shape)} {y.dtype}")
+    if tuple(weight.shape) != (D, 1) or tuple(bias.shape) != (D,) or weight.dtype != torch.float32 or bias.dtype != torch.float32 or D % 8:
+        raise ValueError(f"linear1_fwd: weight fp32 [D, 1] and bias fp32 [D] with D % 8 == 0 expected, got {tuple(weight.shape)} {tuple(bias.shape)}")
+    B = y.shape[0]
+    if add is not None and (add.shape != (B, D) or add.dtype != BF16 or not add.is_contiguous()):
+        raise ValueError(f"linear1_fwd: add must be a dense bf16 [{B}, {D}] tensor, got {tuple(add.shape)} {add.dtype}")
+    out = torch.empty(B, D, dtype=BF16, device=y.device)
+    call("nk_linear1_fwd", y.data_ptr(), weight.data_ptr(), bias.data_ptr(), _p(add), out.data_ptr(), B, D, _stream())
+
+    def bwd(d: Tensor) -> Optional[Tensor]:
+        if d.shape != (B, D) or d.dtype != BF16 or not d.is_contiguous():
+            raise ValueError(f"linear1 bwd: d must be a dense bf16 [{B}, {D}] tensor, got {tuple(d.shape)} {d.dtype}")
+        dy = torch.empty(B, 1, dtype=torch.float32, device=d.device) if need_dy else None
+        call("nk_linear1_bwd", d.data_ptr(), y.data_ptr(), weight.data_ptr(), grad_flat(weight).data_ptr(), grad_flat(bias).data_ptr(), _p(dy), B, D,
+             wgrad_mode(weight), _stream())
+        return dy
+
+    return out, bwd
+
+
 def gather_rows_bwd(dsel: Tensor, idx: Tensor, L: int) -> Tensor:
     """backward of sel[b] = x[b * L + idx[b]]: the dense [B * L, C] gradient of x, zero except the gathered rows (nk_gather_rows_bwd)"""
     _check2d(dsel, "dsel")

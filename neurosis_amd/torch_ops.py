@@ -517,6 +517,99 @@ def _(t, dim, max_period=10000.0):
     return t.new_empty(t.shape[0], dim, dtype=BF16)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# label embeddings (openaimodel.py:574-590 num_classes an int / "continuous"; encoders/classed.py ClassEmbedder)
+# ---------------------------------------------------------------------------------------------------------------
+@_op("label_rows")
+def label_rows(table: Tensor, ids: Tensor, add: Optional[Tensor] = None, out_f32: bool = True) -> Tensor:
+    return ops.label_rows(table, ids, add, torch.float32 if out_f32 else BF16)
+
+
+@label_rows.register_fake
+def _(table, ids, add=None, out_f32=True):
+    return table.new_empty(ids.shape[0], table.shape[1], dtype=torch.float32 if out_f32 else BF16)
+
+
+@_op("label_rows_bwd")
+def label_rows_bwd(ids: Tensor, d: Tensor, V: int) -> Tensor:
+    B, D = d.shape
+    d = d.contiguous()
+    dtable = torch.empty(V, D, dtype=torch.float32, device=d.device)
+    ops.call("nk_label_rows_bwd", ids.contiguous().data_ptr(), d.data_ptr(), D, int(d.dtype == torch.float32), dtable.data_ptr(), B, V, D, 0, ops._stream())
+    return dtable
+
+
+@label_rows_bwd.register_fake
+def _(ids, d, V):
+    return d.new_empty(V, d.shape[1], dtype=torch.float32)
+
+
+def _label_rows_setup(ctx, inputs, output):
+    table, ids, add, _ = inputs
+    ctx.save_for_backward(ids)
+    ctx.V = table.shape[0]
+
+
+def _label_rows_bwd(ctx, d):
+    (ids,) = ctx.saved_tensors
+    need = tuple(ctx.needs_input_grad) + (False,) * 4      # (an absent optional input may have no entry)
+    dt = torch.ops.neurosis_hip.label_rows_bwd(ids, d.contiguous(), ctx.V) if need[0] else None
+    return dt, None, (d.to(BF16) if need[2] else None), None
+
+
+label_rows.register_autograd(_label_rows_bwd, setup_context=_label_rows_setup)
+
+
+@_op("linear1_fwd")
+def linear1_fwd(y: Tensor, w: Tensor, bias: Tensor, add: Optional[Tensor] = None) -> Tensor:
+    return ops.linear1_fwd(y, w, bias, add)[0]
+
+
+@linear1_fwd.register_fake
+def _(y, w, bias, add=None):
+    return y.new_empty(y.shape[0], w.shape[0], dtype=BF16)
+
+
+@_op("linear1_bwd")
+def linear1_bwd(d: Tensor, y: Tensor, w: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    B, D = d.shape
+    dw, db = torch.empty(D, 1, dtype=torch.float32, device=d.device), torch.empty(D, dtype=torch.float32, device=d.device)
+    dy = torch.empty(B, 1, dtype=torch.float32, device=d.device)
+    ops.call("nk_linear1_bwd", d.data_ptr(), y.data_ptr(), w.data_ptr(), dw.data_ptr(), db.data_ptr(), dy.data_ptr(), B, D, 0, ops._stream())
+    return dy, dw, db
+
+
+@linear1_bwd.register_fake
+def _(d, y, w):
+    return y.new_empty(y.shape), w.new_empty(w.shape), w.new_empty(w.shape[0])
+
+
+@_op("linear1")
+def linear1(y: Tensor, w: Tensor, bias: Tensor, add: Optional[Tensor] = None) -> Tensor:
+    return ops.linear1_fwd(y, w, bias, add)[0]
+
+
+@linear1.register_fake
+def _(y, w, bias, add=None):
+    return y.new_empty(y.shape[0], w.shape[0], dtype=BF16)
+
+
+def _linear1_setup(ctx, inputs, output):
+    y, w, bias, add = inputs
+    ctx.save_for_backward(y, w)
+
+
+def _linear1_bwd(ctx, d):
+    y, w = ctx.saved_tensors
+    d = d.contiguous()
+    dy, dw, db = torch.ops.neurosis_hip.linear1_bwd(d, y, w)
+    need = tuple(ctx.needs_input_grad) + (False,) * 4      # (an absent optional input may have no entry)
+    return (dy if need[0] else None), (dw if need[1] else None), (db if need[2] else None), (d if need[3] else None)
+
+
+linear1.register_autograd(_linear1_bwd, setup_context=_linear1_setup)
+
+
 @_op("nchw_to_nlc")
 def nchw_to_nlc(x: Tensor, cpad: int) -> Tensor:
     return ops.nchw_to_tokens(x, cpad)
